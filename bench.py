@@ -30,6 +30,9 @@ under their own names (the runs that are not the headline with `--side-steps` ti
 
 A worker that fails - an exception, a wrong decryption, a collective that does not come back within
 `--leg-timeout` seconds - ends with a non-zero exit code and its error in the line; nothing is retried.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed - the output ciphertexts of every block and their
+decryptions - as DIR/<name>.npy (dump_outputs); keys and inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -93,7 +96,15 @@ def parse_args(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=3300.0, help="launcher: seconds before the worker group is stopped")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="CPU baseline: stop after the level that passes this time")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0 = the cores this process may use)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed (rank 0's wire table: the output "
+                         "ciphertexts of every block and their decryptions) as DIR/<name>.npy, float64 / float32, at most 64 MB")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -304,6 +315,32 @@ class PowerSampler:
             # above 0.9 of the cap the held clock IS the power limit's doing, and frac_at_held_clock is the kernel's figure
             res["at_power_limit"] = bool(frac >= 0.9)
         return res
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, ck, wires, index, nw, blocks, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as DIR/<name>.npy -
+      aes_ct_lwe.npy        [blocks, 128, n + 1] float64: the LWE ciphertexts of ct[0..127] of every block (u32 torus words,
+                            exact in float64)
+      aes_ct_bits.npy       [blocks, 128] float32: their decryptions (bit i of block b = bit i of AES(key_b, pt_b))
+      aes_ct_lwe_blocks.npy [blocks kept] float64: the blocks aes_ct_lwe.npy holds
+    The inputs are seeded, so the same arguments give the same arrays on every build.  If the ciphertexts of every block do
+    not fit in `limit` bytes together with the rest, a fixed seeded sample of blocks is kept.  -> {name: shape}"""
+    import numpy as np
+    rows = np.array([b * nw + index[f"ct[{i}]"] for b in range(blocks) for i in range(128)], np.int32)
+    lwe = wires.download(rows).reshape(blocks, 128, -1)
+    bits = ck.decrypt(lwe.reshape(blocks * 128, -1)).reshape(blocks, 128).astype(np.float32)
+    per_block = 128 * lwe.shape[2] * 8
+    room = max(0, (limit - bits.nbytes - 8 * blocks) // per_block)
+    keep = np.arange(blocks) if room >= blocks else np.sort(np.random.default_rng(0x44554D50).choice(blocks, room, replace=False))
+    arrays = {"aes_ct_lwe": lwe[keep].astype(np.float64), "aes_ct_bits": bits, "aes_ct_lwe_blocks": keep.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= limit
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def check_outputs(ck, wires, index, nw, keys_pt, what):
@@ -790,6 +827,11 @@ def fill_result(bench, result):
         say(f"plan: {head_kind} (headline) {args.warmup} + {args.steps} steps x ~{planned[head_kind]['s_per_step']} s + set-up and check "
             f"~{planned[head_kind]['setup_and_check_s']} s = ~{planned[head_kind]['wall_s']} s; budget for the whole run {args.wall_budget:.0f} s")
     head = guarded(bench, result, f"{head_kind} run", lambda: bench.run(head_kind, args.steps, args.warmup, keep=True))
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the headline's wire table (single_block below evaluates block 0 in it again)
+        with bench.setup_lock():
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(
+                args.dump_outputs, bench.ck, head["wires"], bench.index, bench.nw, head["blocks_per_table"])}
     tm, clock_ghz, quantum = head["tm"], head["clock_ghz"], bench.quantum
     sharded = head_kind != "weak" and world > 1
 
