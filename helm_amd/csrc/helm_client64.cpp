@@ -70,6 +70,22 @@ int helm_si_client_named_params(const char *name, helm_si_params *p, double *lwe
         p->message_modulus = 2; p->carry_modulus = 2;
         *lwe_std = 0.00002043357207216175;
         *glwe_std = 0.0000000000038;
+    } else if (s == "shortint_m2c1") {
+        // tfhe shortint PARAM_MESSAGE_2_CARRY_1_KS_PBS, the set of the reference's LUT-mode test (tests/circuit_test.rs:13):
+        // k = 2, N = 1024, one PBS level, message_modulus = 4, carry_modulus = 2 [shape recalled; n, the decompositions and
+        // both noise values recalled with LOW confidence - SURVEY.md App. B lists them as unknown.  Taken here: m2c2's LWE
+        // side (n, sigma, KS 5 x 3) and PBS base, and tfhe's GLWE noise for k N = 2048, the same GLWE dimension as m2c2's.
+        // The TFHE formulas of tests/test_gpu_noise.py give 2^-72 per look-up, 4x + 2y + z of three outputs included
+        // (DESIGN.md 2): an approximate set]
+        p->n = 742; p->k = 2; p->N = 1024; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 5; p->ks_logB = 3;
+        p->carry_modulus = 2;
+        *lwe_std = 0.000007069849454709433;
+        *glwe_std = 0.00000000000000029403601535432533;
+    } else if (s == "si_toy_1024_k2") { // shortint_m2c1's shape at toy size (oracle-sized)
+        p->n = 10; p->k = 2; p->N = 1024; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 5; p->ks_logB = 3;
+        p->carry_modulus = 2;
+        *lwe_std = 1e-9;
+        *glwe_std = 1e-15;
     } else if (s == "si_toy_512_k3") { // the k = 3 kernel at toy size (oracle-sized; 16 plaintext values like the other toys)
         p->n = 10; p->k = 3; p->N = 512; p->pbs_l = 1; p->pbs_logB = 18; p->ks_l = 3; p->ks_logB = 4;
         *lwe_std = 1e-9;

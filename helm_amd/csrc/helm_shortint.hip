@@ -404,23 +404,37 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64(const Pbs64Job *__restr
 #ifndef HELM_SI_K_GATHER
 #define HELM_SI_K_GATHER 1 // k_pbs64k: column sums gathered by the owner of the column instead of scattered with ds_add_f64
 #endif
+//
+// N = 1024 (k = 2, the 3-bit set shortint_m2c1): the same six waves and two ciphertexts per CU, but the LDS of the N = 512
+// layout would be 93 KB (scratch 51 KB + twiddles 16 KB + accumulator 24 KB, 48 KB as [acc | -acc]).  So the accumulator
+// has no region of its own (ACC_X): wave (p, f) keeps the half of polynomial p it lifts in the CRT (slots f H .. f H + H,
+// coefficients f N/2 .. f N/2 + N/2) in registers, and publishes it in the upper half of its own transform scratch, which is
+// free from the CRT of one step to the decomposition of the next.  The digit hand-over moves to the lower halves.  LDS
+// 70.4 KB per ciphertext.
 template <int LOGN_, int K_>
 struct Pbs64kCfg {
     static constexpr int LOGN = LOGN_, L = 1, K = K_, K1 = K_ + 1, NW = 2 * K1;
     using G = Geo<LOGN>;
     static constexpr int MAX_SMALL_N = 1024;
+    static constexpr bool ACC_X = LOGN >= 10;                                     // the accumulator lives in the scratch
     static constexpr size_t X_OFF = 0;                                            // double [NW][XPAD]: transform scratch,
                                                                                   // and between two barriers the column sums
     static constexpr int TW_IDX = G::N >> G::BC, TW_FIELD = TW_IDX + G::TWC * 64;
     static constexpr size_t TW_OFF = X_OFF + sizeof(double) * NW * G::XPAD;       // double [2][TW_FIELD]
-    static constexpr size_t ACC_OFF = TW_OFF + sizeof(double) * 2 * TW_FIELD;     // u64 [K1][N]
+    static constexpr size_t ACC_OFF = TW_OFF + sizeof(double) * 2 * TW_FIELD;     // u64 [K1][N] (none: ACC_X)
     // HELM_SI_K_ACC2: every polynomial is stored as [acc | -acc] (2N words): a rotated read X^a acc is then ONE indexed read,
     // no sign logic (5 vector instructions per coefficient in a kernel that is bound by its instruction stream)
-    static constexpr int ACC_LEN = HELM_SI_K_ACC2 ? 2 * G::N : G::N;
-    static constexpr size_t MS_OFF = ACC_OFF + sizeof(uint64_t) * K1 * ACC_LEN;   // u16 [n+1]
+    static constexpr int ACC_LEN = (HELM_SI_K_ACC2 && !ACC_X) ? 2 * G::N : G::N;
+    static constexpr size_t MS_OFF = ACC_OFF + (ACC_X ? 0 : sizeof(uint64_t) * K1 * ACC_LEN); // u16 [n+1]
     static constexpr size_t BYTES = (MS_OFF + sizeof(uint16_t) * (MAX_SMALL_N + 1) + 15) / 16 * 16;
     static_assert(NW <= 16, "a workgroup holds at most 16 waves");
     static_assert(2 * BYTES <= 160 * 1024, "two ciphertexts per CU");
+    static_assert(!ACC_X || (HELM_SI_K_GATHER && HELM_SI_K_SPLIT_DIGITS), "ACC_X is built on the gather form with split digits");
+    // ACC_X: coefficient j of polynomial p, in the upper half of the scratch of wave (p, j >= N/2)
+    __device__ static __forceinline__ int acc_x(int p, int j)
+    {
+        return (p * 2 + (j >> (LOGN - 1))) * G::XPAD + G::N / 2 + (j & (G::N / 2 - 1));
+    }
 };
 
 // F: this wave's field; FA, FB: the CRT pair (F is one of them)
@@ -455,6 +469,14 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
     kb.init(bsk, (size_t)n * step_bytes, lane);
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
     [[maybe_unused]] const uint32_t bmask = (1u << logB) - 1u;
+    // ACC_X: the accumulator as published in the scratch upper halves (Pbs64kCfg::acc_x), and this wave's half in registers
+    [[maybe_unused]] const uint64_t *Xu = reinterpret_cast<const uint64_t *>(X);
+    [[maybe_unused]] uint64_t *xb_acc = reinterpret_cast<uint64_t *>(xb) + N / 2 + lane;
+    [[maybe_unused]] uint64_t acc_own[C::ACC_X ? H : 1];
+    if constexpr (C::ACC_X) {
+#pragma unroll
+        for (int e = 0; e < H; e++) acc_own[e] = xb_acc[e * 64];
+    }
     for (int i = 0; i < n; i++) {
         const int a = __builtin_amdgcn_readfirstlane((int)MS[i]);
         if (a == 0) continue; // uniform over the workgroup
@@ -474,34 +496,42 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
         double mine[E];
         {
             double x[1][E];
-            auto digit = [&](int e) {
+            auto digit = [&](int e, [[maybe_unused]] int eo) { // eo: slot e - f H of acc_own (ACC_X)
                 const int j = G::jA(lane, e);
                 const int src = (j - a) & (2 * N - 1);
                 uint64_t v;
-                if constexpr (HELM_SI_K_ACC2) v = acc_p[src];
-                else {
-                    v = acc_p[src & (N - 1)];
+                if constexpr (C::ACC_X) {
+                    v = Xu[C::acc_x(p, src & (N - 1))];
                     if (src >= N) v = 0ull - v;
+                    v -= acc_own[eo];
+                } else {
+                    if constexpr (HELM_SI_K_ACC2) v = acc_p[src];
+                    else {
+                        v = acc_p[src & (N - 1)];
+                        if (src >= N) v = 0ull - v;
+                    }
+                    v -= acc_p[j];
                 }
-                v -= acc_p[j];
                 const uint32_t st = (uint32_t)((v + (1ull << (63 - logB))) >> (64 - logB));
                 return (double)((int)((st + half_m1) & bmask) - (int)half_m1); // st <= B/2 stays, above it st - B
             };
 #if HELM_SI_K_SPLIT_DIGITS
             // the two field waves of a polynomial need the same digits: each makes half of them and hands them to the other
             // through the other's (free) transform scratch - one more barrier, half the decomposition work
+            // (ACC_X: through the lower halves - the upper ones hold the accumulator until the barrier)
             double *xb_field = X + (size_t)(p * 2 + (1 - f)) * G::XPAD;
+            constexpr int XO = C::ACC_X ? 0 : 1; // slot offset of the hand-over: (XO f H + e) * 64
 #pragma unroll
             for (int e = 0; e < H; e++) {
-                x[0][f * H + e] = digit(f * H + e);
-                xb_field[(f * H + e) * 64 + lane] = x[0][f * H + e];
+                x[0][f * H + e] = digit(f * H + e, e);
+                xb_field[(XO * f * H + e) * 64 + lane] = x[0][f * H + e];
             }
             lds_block_sync();
 #pragma unroll
-            for (int e = 0; e < H; e++) x[0][(1 - f) * H + e] = xb[((1 - f) * H + e) * 64 + lane];
+            for (int e = 0; e < H; e++) x[0][(1 - f) * H + e] = xb[(XO * (1 - f) * H + e) * 64 + lane];
 #else
 #pragma unroll
-            for (int e = 0; e < E; e++) x[0][e] = digit(e);
+            for (int e = 0; e < E; e++) x[0][e] = digit(e, 0);
 #endif
             ntt_forward<F, LOGN, 1, decltype(twf), 0, NoHook, DIG>(x, xb, twf, lane); // (digits: stage 1 - 46-bit pair: stages 1 and 2 - plain)
 #pragma unroll
@@ -606,9 +636,14 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
             const double t = mulmod<FB>(WIDE ? reduce<FB>(r1 - r0) : r1 - r0, p0inv_mod_p1);
             const uint64_t xv = (uint64_t)to_int64(r0) + FA::P_U64 * (uint64_t)to_int64(t);
             const int j = G::jA(lane, f * H + e);
-            const uint64_t nv = acc_p[j] + xv;
-            acc_p[j] = nv;
-            if constexpr (HELM_SI_K_ACC2) acc_p[j + N] = 0ull - nv;
+            if constexpr (C::ACC_X) { // (the upper half of the own scratch: the other waves read only lower halves here)
+                acc_own[e] += xv;
+                xb_acc[e * 64] = acc_own[e];
+            } else {
+                const uint64_t nv = acc_p[j] + xv;
+                acc_p[j] = nv;
+                if constexpr (HELM_SI_K_ACC2) acc_p[j + N] = 0ull - nv;
+            }
         }
         lds_block_sync(); // accumulator complete before the next step's rotated reads; scratch free again
     }
@@ -657,8 +692,11 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
                 if (idx >= N) v = 0ull - v;
             }
             const int pp = j / N, jj = j - pp * N;
-            ACC[(size_t)pp * C::ACC_LEN + jj] = v;
-            if constexpr (HELM_SI_K_ACC2) ACC[(size_t)pp * C::ACC_LEN + N + jj] = 0ull - v;
+            if constexpr (C::ACC_X) reinterpret_cast<uint64_t *>(smem + C::X_OFF)[C::acc_x(pp, jj)] = v;
+            else {
+                ACC[(size_t)pp * C::ACC_LEN + jj] = v;
+                if constexpr (HELM_SI_K_ACC2) ACC[(size_t)pp * C::ACC_LEN + N + jj] = 0ull - v;
+            }
         }
     }
     __syncthreads();
@@ -666,17 +704,19 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
     else pbs64k_body<C, FB, FA, FB>(smem, bsk, n, logB, p0inv_mod_p1, p, 1, lane);
     // ---- sample extract (coefficient 0); wave (p, f) writes its half of the slots ------
     const uint64_t *acc_p = ACC + (size_t)p * C::ACC_LEN;
+    const uint64_t *acc_xp = reinterpret_cast<const uint64_t *>(smem + C::X_OFF);
+    auto acc_at = [&](int j) { return C::ACC_X ? acc_xp[C::acc_x(p, j)] : acc_p[j]; };
     uint64_t *ob = out + (size_t)job.out_row * ((size_t)K * N + 1);
     if (p < K) {
 #pragma unroll
         for (int e = 0; e < H; e++) {
             const int j = G::jA(lane, f * H + e);
-            const uint64_t v = acc_p[j];
+            const uint64_t v = acc_at(j);
             if (j == 0) ob[p * N] = v;
             else ob[p * N + (N - j)] = 0ull - v;
         }
     } else if (f == 0 && lane == 0) {
-        ob[K * N] = acc_p[0];
+        ob[K * N] = acc_at(0);
     }
 }
 
@@ -1885,8 +1925,10 @@ struct Timed {
 
 bool si_supported(const helm_si_params &P)
 {
-    // k > 1: k_pbs64k, one level, N = 512 (PARAM_MESSAGE_1_CARRY_1_KS_PBS of helm.rs:301 has k = 3)
-    if (P.k == 2 || P.k == 3) return P.N == 512 && P.pbs_l == 1 && P.grouping_factor <= 1;
+    // k > 1: k_pbs64k, one level, N = 512 (PARAM_MESSAGE_1_CARRY_1_KS_PBS of helm.rs:301 has k = 3); k = 2 also at
+    // N = 1024 (the 3-bit set shortint_m2c1)
+    if (P.k == 2 || P.k == 3)
+        return (P.N == 512 || (P.k == 2 && P.N == 1024)) && P.pbs_l == 1 && P.grouping_factor <= 1;
     if (P.k != 1) return false;
     if (!(P.N == 512 || P.N == 1024 || P.N == 2048)) return false;
     return P.pbs_l == 1 || P.pbs_l == 2;
@@ -1900,9 +1942,15 @@ hipError_t launch_pbs64k_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count
     // the CRT pair follows the key loaded into the PRIMARY context (a lane shares its key and tables: helm_si_ctx_fork; a key
     // loaded after the fork may have moved the pair)
     const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx;
-    auto kern = root->pair ? k_pbs64k<C, J0, J1> : k_pbs64k<C, F0, F1>;
+    // (the 46-bit pair is built for N = 512 only: helm_si_load_bootstrap_key never chooses it at another N)
+    auto kern_j = [] {
+        if constexpr (C::LOGN == 9) return k_pbs64k<C, J0, J1>;
+        else return k_pbs64k<C, F0, F1>;
+    }();
+    if (root->pair && C::LOGN != 9) return hipErrorInvalidValue;
+    auto kern = root->pair ? kern_j : k_pbs64k<C, F0, F1>;
     if (!attr_done[ctx->device & 63]) {
-        for (auto kk : {k_pbs64k<C, F0, F1>, k_pbs64k<C, J0, J1>}) {
+        for (auto kk : {k_pbs64k<C, F0, F1>, kern_j}) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)C::BYTES);
             if (e != hipSuccess) return e;
@@ -1994,6 +2042,7 @@ hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_
     const Pbs64Job *jobs = static_cast<const Pbs64Job *>(jobs_v);
     const helm_si_params &P = ctx->P;
     if (P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
+    if (P.k == 2 && ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
     if (P.k == 2) return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
     if (ctx->use_split && ctx->group > 1) {
         if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, true>(ctx, jobs, count, small, luts, out, per_cu);
@@ -2014,6 +2063,7 @@ hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, c
         return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu);
 #endif
     if (P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
+    if (P.k == 2 && ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
     if (P.k == 2) return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
     if (ctx->use_split) {
         if (ctx->group > 1) {
@@ -2405,7 +2455,7 @@ int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx 
     *out = nullptr;
     const helm_si_params &P = *params;
     if (!si_supported(P))
-        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1");
+        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1; k = 2, N = 1024, pbs_l = 1");
     if (P.n < 1 || P.n > 1024) return fail(HELM_ERR_INVALID, "n must be in [1,1024]");
     // (pbs_logB <= 24: the kernels multiply digits by the field's fourth root of unity, 25 bits, without a reduction)
     if (P.pbs_logB < 2 || P.pbs_logB > 24 || P.pbs_logB * P.pbs_l > 31)
@@ -2652,7 +2702,8 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
     if (!ctx->bsk && ctx->group == 1) HIP_TRY(hipMalloc(&ctx->bsk, n_words * 2 * sizeof(double)));
     if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && ctx->group == 1 && !ctx->lane_of) {
-        // k_pbs64k contexts: the CRT pair follows the key at hand.  An exact product of a blind-rotation step is at most
+        // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
+        // every k = 1 set's): the CRT pair follows the key at hand.  An exact product of a blind-rotation step is at most
         // B/2 x the largest l1-norm over the key polynomials that meet in one output column (or, transposed, in one row) - an
         // exact guarantee for this key and every input.  Below p p' / 2 of the 46-bit pair (and with digits of at most 17 bits,
         // whose products with b^3 stay exact doubles): FpJ / FpJ2, whose headroom drops stage 2's modular multiplications and
