@@ -176,7 +176,7 @@ static __device__ unsigned long long g_wide_stamps[2 * 16 * 6];
 // them), that level's key words fetched around its transform, only two partial sums in registers (the third accumulates in
 // LDS), twiddles from the LDS lane table (the forward direction's per-lane twiddles copied into registers once), NB = 4
 // bootstraps per workgroup, one bootstrap per SIMD (see NB below), issue priorities that fall as a wave advances through the
-// step; 162 registers, 138 KB LDS at N = 512 -> one workgroup per CU, three waves on every SIMD doing the same work at the same
+// step; 168 registers, 138 KB LDS at N = 512 -> one workgroup per CU, three waves on every SIMD doing the same work at the same
 // time.  The full rounds of every wide launch: the dominant kernel of the benchmark.  (Rounds 1-5 also carried a latency, a
 // balanced and a throughput build of this kernel - all levels transformed together, key words prefetched a step ahead,
 // twiddles in registers - and k_pbs_sym; the size dispatch stopped selecting them in round 4 and they were removed in
@@ -215,6 +215,12 @@ struct PbsCfg {
     static constexpr int WAVE_STRIDE = WAVE_STRIDE_X > (ACC3 + 1) / 2 ? WAVE_STRIDE_X : (ACC3 + 1) / 2;
     static constexpr int slot_off(int s) { return s == 0 ? 0 : G::XPAD + (s - 1) * SLOT_STRIDE; }
     static constexpr int TW_ROWS = G::TWB + G::TWC;
+    // the 8-point block form of the N = 512 transforms (ntt_fp64.h fwd_blk8 / inv_blk8; -DHELM_BLK8=0: the radix-2 blocks)
+#ifndef HELM_BLK8
+#define HELM_BLK8 1
+#endif
+    static constexpr bool BLK8 = HELM_BLK8 != 0 && blk8_field<F>::value && LOGN == 9 && TW == TW_LANE_FREG;
+    static_assert(!BLK8 || TW_ROWS == 14, "the table holds the 2 x 7 block-form twiddles of the inverse");
     static constexpr size_t X_OFF = 0;                                                // double [K1][WAVE_STRIDE]
     static constexpr size_t TW_OFF = X_OFF + sizeof(double) * K1 * WAVE_STRIDE;       // double [TW_ROWS][64]
     static constexpr size_t MS_OFF = TW_OFF + sizeof(double) * TW_ROWS * 64;          // u16 [n+1]
@@ -269,23 +275,32 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
         }
     }
     // ---- twiddles: the lane-major LDS table (block A: lane-uniform scalars) ---------------
+    // C::BLK8 (N = 512 in FpG): blocks B and C of both transforms in the 8-point block form - the lane's seven powers w^t of
+    // its group root per block in registers (forward), the w^-t in the LDS table (inverse), the same 14 rows
     using TwF0 = TwLane<LOGN, false>;
-    using TwF = typename std::conditional<C::TW == TW_LANE_FREG, TwLaneFwdReg<LOGN>, TwF0>::type;
-    using TwI = TwLane<LOGN, true>;
+    using TwF = typename std::conditional<C::BLK8, TwBlk8Fwd<LOGN>,
+                                          typename std::conditional<C::TW == TW_LANE_FREG, TwLaneFwdReg<LOGN>, TwF0>::type>::type;
+    using TwI = typename std::conditional<C::BLK8, TwBlk8Inv<LOGN>, TwLane<LOGN, true>>::type;
     TwF0 twf0;
     TwF twf;
     TwI twi;
     {
         double *TW = reinterpret_cast<double *>(smem + C::TW_OFF);
-        for (int r = p; r < C::TW_ROWS; r += K1) TW[r * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(r, lane)];
+        for (int r = p; r < C::TW_ROWS; r += K1) {
+            if constexpr (C::BLK8) TW[r * 64 + lane] = tw_blk8_row<LOGN, -1>(tw_fwd, r, lane);
+            else TW[r * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(r, lane)];
+        }
         twf0.base = TW + lane;
         twi.base = TW + (63 - lane);
         twf0.fill_uniform(tw_fwd);
         twi.fill_uniform(tw_fwd);
-        if constexpr (C::TW == TW_LANE) twf = twf0;
+        if constexpr (C::BLK8) {
+            twi.row = TW + lane;
+            twf.load(tw_fwd, lane);
+        } else if constexpr (C::TW == TW_LANE) twf = twf0;
     }
     __syncthreads();
-    if constexpr (C::TW == TW_LANE_FREG) twf.load(twf0); // the table is complete: this lane's forward twiddles into registers
+    if constexpr (!C::BLK8 && C::TW == TW_LANE_FREG) twf.load(twf0); // the table is complete: this lane's forward twiddles into registers
 
     // ---- accumulator init: (0,...,0, X^{-b~} * tv) ------------------------------------
     double *xb = X + (size_t)p * C::WAVE_STRIDE; // this wave's exchange slots

@@ -41,7 +41,8 @@ namespace helm {
 // the radix-4 butterfly on four digits is 10 plain operations instead of 6 modular multiplications and 8 additions
 // (fwd_top2_digits: 20 instead of 56 per transform and polynomial at N = 512).  p / 2 = 2^48.23 still covers tfhe boolean
 // DEFAULT's exact products (2^48.17); 2^53 / p = 13.6 against forward outputs <= 4.9 p, hand-over sums <= 9.4 p, inverse
-// sums <= 8 p (tests/test_lazy_bounds.py).
+// sums <= 8 p (tests/test_lazy_bounds.py) - in the 8-point block form of the lockstep kernel (fwd_blk8 / inv_blk8) forward
+// outputs <= 7.4 p, hand-over sums <= 11.8 p, inverse sums <= 10.7 p (tests/test_short_root_blocks.py).
 struct FpG {
     static constexpr double P = 661785091833857.0;
     static constexpr uint64_t P_U64 = 661785091833857ull;
@@ -127,6 +128,10 @@ template <> struct has_short_roots<FpJ> : std::true_type {};
 template <> struct has_short_roots<FpJ2> : std::true_type {};
 template <> struct lean_inverse_ok<FpG> : std::true_type {};
 template <> struct lean_inverse_ok<FpG2> : std::true_type {};
+// fields whose bounds tests/test_short_root_blocks.py derives for the 8-point block form of the N = 512 transforms
+// (fwd_blk8 / inv_blk8 below): a twiddle source of that form (TwBlk8Fwd, TwBlk8Inv) is refused for any other field
+template <typename F> struct blk8_field : std::false_type {};
+template <> struct blk8_field<FpG> : std::true_type {};
 
 // -DHELM_CHECK_BOUNDS: the contracts the lazy arithmetic rests on, checked at run time (a debug build, one translation unit:
 // `make libhelm_hip_check.so`, tests/test_gpu_bounds_check.py).  Every value is an exact integer held in a double, which is
@@ -167,6 +172,23 @@ __device__ __forceinline__ double reduce(double a)
     double q = __builtin_rint(a * PINV);
     return __builtin_fma(-q, F::P, a);
 }
+// x b^K mod p in a field p = b^4 + 1 (K = 1..7, K != 4; b^K = -b^(K-4) for K > 4), for any |x| < 2^53.  With j = K mod 4:
+// x = q b^(4-j) + x0, |x0| <= b^(4-j) / 2, so x b^j = q b^4 + x0 b^j = x0 b^j - q.  Four operations instead of mulmod's six,
+// every one exact, and the result is nearly recentred: |r| <= p/2 + |x| / b^(4-j) + 1 (tests/test_short_root_blocks.py).
+template <typename F, int K>
+__device__ __forceinline__ double mul_broot(double x)
+{
+    static_assert(has_short_roots<F>::value && K >= 1 && K <= 7 && K != 4, "b^K, K = 1..7 except -1");
+    constexpr int J = K & 3;
+    constexpr double BJ = J == 1 ? F::B1 : J == 2 ? F::B2 : F::B3;  // b^j
+    constexpr double BC = J == 1 ? F::B3 : J == 2 ? F::B2 : F::B1;  // b^(4-j)
+    constexpr double BC_INV = 1.0 / BC;
+    HELM_BOUND(__builtin_fabs(x) < 0x1p53, 0);
+    const double q = __builtin_rint(x * BC_INV);
+    const double x0 = __builtin_fma(-q, BC, x);
+    return K < 4 ? __builtin_fma(x0, BJ, -q) : __builtin_fma(x0, -BJ, q);
+}
+
 // recentre only where the field has no headroom to skip it
 template <typename F>
 __device__ __forceinline__ double reduce_unless_lazy(double a)
@@ -434,6 +456,67 @@ struct TwHybridC {
     }
 };
 
+// Twiddles of the 8-point block form (N = 512: blocks B and C as fwd_blk8 / inv_blk8).  The eight values of a lane in
+// block B or C are one 8-group of the transform; its root w = psi^a is the twiddle the block's last radix-2 stage would
+// use for hi = 0, and the block needs w^t (forward) or w^-t (inverse) for t = 1..7.  They are read from the bit-reversed
+// forward table, which holds psi^x for 0 <= x < N (psi^N = -1).
+template <int LOGN>
+__device__ __forceinline__ double tw_pow(const double *__restrict__ tw_fwd, int x)
+{
+    constexpr int N = 1 << LOGN;
+    x &= 2 * N - 1;
+    const double v = tw_fwd[__builtin_bitreverse32((unsigned)(x & (N - 1))) >> (32 - LOGN)];
+    return (x & N) ? -v : v;
+}
+// row r (0 .. 13) of a lane's block-form twiddles: w^(SIGN t) of block B (r < 7) or C, t = r % 7 + 1
+template <int LOGN, int SIGN>
+__device__ inline double tw_blk8_row(const double *__restrict__ tw_fwd, int r, int lane)
+{
+    using G = Geo<LOGN>;
+    static_assert(G::E == 8 && G::BB == 3 && G::BC == 3, "blocks B and C are 8-groups");
+    const int blk = r >= 7, t = r - 7 * blk + 1;
+    const int s = blk ? 0 : G::BC; // the block's lowest stride bit
+    const int j = blk ? G::jC(lane, 0) : G::jB(lane, 0);
+    const int a = (int)(__builtin_bitreverse32((unsigned)((G::N >> (s + 1)) + (j >> (s + 1)))) >> (32 - LOGN));
+    return tw_pow<LOGN>(tw_fwd, SIGN * t * a);
+}
+// forward: block A as TwLane's lane-uniform part, the lane's 14 block-form twiddles in registers (they do not change
+// from step to step: loaded once per kernel, in place of TwLaneFwdReg's 14 radix-2 twiddles)
+template <int LOGN>
+struct TwBlk8Fwd {
+    static constexpr bool MIRROR = false;
+    static constexpr bool BLK8 = true;
+    using G = Geo<LOGN>;
+    double ua[G::TWA];
+    double w[14];
+    __device__ __forceinline__ void load(const double *__restrict__ tw_fwd, int lane)
+    {
+        TwLane<LOGN, false> u;
+        u.fill_uniform(tw_fwd);
+#pragma unroll
+        for (int r = 0; r < G::TWA; r++) ua[r] = u.ua[r];
+#pragma unroll
+        for (int r = 0; r < 14; r++) w[r] = tw_blk8_row<LOGN, 1>(tw_fwd, r, lane);
+    }
+    __device__ __forceinline__ double get(int sb, int hi, int, int, int) const
+    {
+        const int fs = tw_fwd_slot<LOGN>(sb, hi);
+        return ua[fs < G::TWA ? fs : 0]; // (block A only)
+    }
+    // w^t of block B (BLK = 0) or C (1)
+    __device__ __forceinline__ double pw(int blk, int t) const { return w[7 * blk + t - 1]; }
+};
+// inverse: block A's general stage as TwLane<LOGN, true> (lane-uniform, mirrored), blocks B and C from a lane-major LDS
+// table of the w^-t (rows tw_blk8_row<LOGN, -1>)
+template <int LOGN>
+struct TwBlk8Inv : TwLane<LOGN, true> {
+    static constexpr bool BLK8 = true;
+    const double *row; // LDS table + lane
+    __device__ __forceinline__ double pw(int blk, int t) const { return row[(7 * blk + t - 1) * 64]; }
+};
+template <typename TW, typename = void> struct is_blk8 : std::false_type {};
+template <typename TW> struct is_blk8<TW, std::void_t<decltype(TW::BLK8)>> : std::bool_constant<TW::BLK8> {};
+
 // Fused radix-2 Cooley-Tukey stages on stride bits SB_HI..SB_LO (descending), all of
 // which are register-slot bits (slot bit = stride bit - SHIFT), for M polynomials.
 // PLAIN_TOP: the block starts with the transform's FIRST stage (stride bit LOGN-1, the one twiddle psi^(N/2) = +-b^2 of a
@@ -467,9 +550,12 @@ __device__ __forceinline__ void fwd_block(double (&x)[M][Geo<LOGN>::E], const TW
 }
 
 // Gentleman-Sande stages on stride bits SB_LO..SB_HI (ascending).
-template <typename F, int LOGN, int SHIFT, int SB_LO, int SB_HI, int SLOT0, typename TW>
+// SHORT_TOP (block A of a table normalised to psi^(N/4) = b): the twiddles of stride bits LOGN-1 and LOGN-2 are
+// psi^-(N/2) = b^6 and psi^-(N/4), psi^-(3N/4) = b^7, b^5 - multiplications by mul_broot.
+template <typename F, int LOGN, int SHIFT, int SB_LO, int SB_HI, int SLOT0, typename TW, bool SHORT_TOP = false>
 __device__ __forceinline__ void inv_block(double (&x)[Geo<LOGN>::E], const TW &tw, int jbase)
 {
+    static_assert(!SHORT_TOP || (SHIFT == 6 && SB_HI == LOGN - 1 && SB_LO <= LOGN - 2), "block A: twiddles lane-uniform");
     constexpr int E = Geo<LOGN>::E, N = Geo<LOGN>::N;
     int slot = SLOT0;
 #pragma unroll
@@ -485,17 +571,115 @@ __device__ __forceinline__ void inv_block(double (&x)[Geo<LOGN>::E], const TW &t
 #pragma unroll
         for (int hi = 0; hi < (E >> (eb + 1)); hi++) {
             const int jh = jbase | (hi << (eb + 1 + SHIFT));
-            const double w = tw.get(sb, hi, E >> (eb + 1), (N >> (sb + 1)) + (jh >> (sb + 1)), slot++);
+            const bool short_stage = SHORT_TOP && sb >= LOGN - 2;
+            const double w = short_stage ? 0.0 : tw.get(sb, hi, E >> (eb + 1), (N >> (sb + 1)) + (jh >> (sb + 1)), slot);
+            slot++;
 #pragma unroll
             for (int lo = 0; lo < (1 << eb); lo++) {
                 const int e0 = (hi << (eb + 1)) | lo, e1 = e0 | (1 << eb);
                 double U = x[e0], V = x[e1];
                 x[e0] = U + V;
                 HELM_BOUND(__builtin_fabs(x[e0]) < 0x1p53 && __builtin_fabs(U - V) < 0x1p53, 2);
+                if constexpr (SHORT_TOP) {
+                    if (short_stage) {
+                        x[e1] = sb == LOGN - 1 ? mul_broot<F, 6>(U - V) : hi == 0 ? mul_broot<F, 7>(U - V) : mul_broot<F, 5>(U - V);
+                        continue;
+                    }
+                }
                 x[e1] = mulmod<F>(TW::MIRROR ? V - U : U - V, w);
             }
         }
     }
+}
+
+// The 8-point block form of a block of three stages on an 8-group (N = 512, blocks B and C; tests/test_short_root_blocks.py
+// proves it equal to the radix-2 stages mod p).  The eight values of a lane are the coefficients x_e of one 8-group, and the
+// block evaluates sum_e x_e y^e at y = w z, w the group's root (TwBlk8Fwd), z the eighth roots of unity in the slot order
+// fwd_block leaves them: slot 2q + s holds z = (-1)^s (1, b^2, b, b^3)[q].  So: the diagonal x_e w^e (seven mulmod), then a
+// DFT8 over the powers of b - radix-2 stages whose twiddles are 1 (slot bit 2), 1 and b^2 (bit 1), 1, b^2, b, b^3 (bit 0):
+// 24 additions and five mul_broot.  86 operations per lane and polynomial instead of 96.
+// X0C: recentre x_0, the one input no twiddle multiplies (block C: it would carry block B's pure-sum slot into every output).
+template <typename F, int LOGN, int M, int BLK, bool X0C, typename TW>
+__device__ __forceinline__ void fwd_blk8(double (&x)[M][Geo<LOGN>::E], const TW &tw)
+{
+    static_assert(Geo<LOGN>::E == 8, "one 8-group per lane");
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        double z[8];
+        z[0] = X0C ? reduce<F>(x[m][0]) : x[m][0];
+#pragma unroll
+        for (int t = 1; t < 8; t++) z[t] = mulmod<F>(x[m][t], tw.pw(BLK, t));
+        double a[8], c[8];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            a[e] = z[e] + z[e + 4];
+            a[e + 4] = z[e] - z[e + 4];
+        }
+        const double t6 = mul_broot<F, 2>(a[6]), t7 = mul_broot<F, 2>(a[7]);
+        c[0] = a[0] + a[2];
+        c[2] = a[0] - a[2];
+        c[1] = a[1] + a[3];
+        c[3] = a[1] - a[3];
+        c[4] = a[4] + t6;
+        c[6] = a[4] - t6;
+        c[5] = a[5] + t7;
+        c[7] = a[5] - t7;
+        const double u3 = mul_broot<F, 2>(c[3]), u5 = mul_broot<F, 1>(c[5]), u7 = mul_broot<F, 3>(c[7]);
+        x[m][0] = c[0] + c[1];
+        x[m][1] = c[0] - c[1];
+        x[m][2] = c[2] + u3;
+        x[m][3] = c[2] - u3;
+        x[m][4] = c[4] + u5;
+        x[m][5] = c[4] - u5;
+        x[m][6] = c[6] + u7;
+        x[m][7] = c[6] - u7;
+#ifdef HELM_CHECK_BOUNDS
+        bool ok = true;
+        for (int e = 0; e < 8; e++)
+            ok = ok && __builtin_fabs(a[e]) < 0x1p53 && __builtin_fabs(c[e]) < 0x1p53 && __builtin_fabs(x[m][e]) < 0x1p53;
+        HELM_BOUND(ok, 2);
+#endif
+    }
+}
+
+// The inverse: the DFT8 over b^-k (Gentleman-Sande stages: slot bit 0 with 1, b^6, b^7, b^5; bit 1 with 1 and b^6; bit 2
+// with 1), then the diagonal w^-e (TwBlk8Inv).
+template <typename F, int LOGN, int BLK, typename TW>
+__device__ __forceinline__ void inv_blk8(double (&x)[Geo<LOGN>::E], const TW &tw)
+{
+    static_assert(Geo<LOGN>::E == 8, "one 8-group per lane");
+    double c[8], a[8];
+    c[0] = x[0] + x[1];
+    c[1] = x[0] - x[1];
+    c[2] = x[2] + x[3];
+    c[3] = mul_broot<F, 6>(x[2] - x[3]);
+    c[4] = x[4] + x[5];
+    c[5] = mul_broot<F, 7>(x[4] - x[5]);
+    c[6] = x[6] + x[7];
+    c[7] = mul_broot<F, 5>(x[6] - x[7]);
+    a[0] = c[0] + c[2];
+    a[2] = c[0] - c[2];
+    a[1] = c[1] + c[3];
+    a[3] = c[1] - c[3];
+    a[4] = c[4] + c[6];
+    a[6] = mul_broot<F, 6>(c[4] - c[6]);
+    a[5] = c[5] + c[7];
+    a[7] = mul_broot<F, 6>(c[5] - c[7]);
+#ifdef HELM_CHECK_BOUNDS
+    bool ok = true;
+    for (int e = 0; e < 8; e++) ok = ok && __builtin_fabs(c[e]) < 0x1p53 && __builtin_fabs(a[e]) < 0x1p53;
+    HELM_BOUND(ok && __builtin_fabs(x[2] - x[3]) < 0x1p53 && __builtin_fabs(x[4] - x[5]) < 0x1p53 &&
+                   __builtin_fabs(x[6] - x[7]) < 0x1p53 && __builtin_fabs(c[4] - c[6]) < 0x1p53 && __builtin_fabs(c[5] - c[7]) < 0x1p53,
+               2);
+#endif
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        x[e] = a[e] + a[e + 4];
+        x[e + 4] = a[e] - a[e + 4];
+        HELM_BOUND(__builtin_fabs(x[e]) < 0x1p53 && __builtin_fabs(x[e + 4]) < 0x1p53, 2);
+    }
+#pragma unroll
+    for (int t = 1; t < 8; t++) x[t] = mulmod<F>(x[t], tw.pw(BLK, t));
 }
 
 // Forward negacyclic NTT of M polynomials held by one wave.
@@ -553,6 +737,11 @@ __device__ __forceinline__ void ntt_forward(double (&x)[M][Geo<LOGN>::E], double
                                             const HOOK &before_last = HOOK())
 {
     using G = Geo<LOGN>;
+    // blocks B and C in the 8-point block form (twiddle sources TwBlk8Fwd): bounds proven for digit inputs (DIGITS = 2) in the
+    // fields of blk8_field only
+    constexpr bool BLK8 = is_blk8<TW>::value;
+    static_assert(!BLK8 || (blk8_field<F>::value && F::LAZY && DIGITS == 2 && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3),
+                  "8-point block form: N = 512 transforms of digits in a field of blk8_field");
     if constexpr (DIGITS == 1 && has_short_roots<F>::value)
         fwd_block<F, LOGN, M, 6, LOGN - 1, LOGN - G::BA, 0, TW, true>(x, tw, G::jA(lane, 0));
     else if constexpr (DIGITS == 2 && has_short_roots<F>::value) {
@@ -580,7 +769,8 @@ __device__ __forceinline__ void ntt_forward(double (&x)[M][Geo<LOGN>::E], double
 #pragma unroll
         for (int e = 0; e < G::E; e++) x[m][e] = pB[m * G::XPAD + G::offB1(e)];
     lds_wave_sync();
-    fwd_block<F, LOGN, M, G::BC, G::BC + G::BB - 1, G::BC, G::TWA>(x, tw, G::jB(lane, 0));
+    if constexpr (BLK8) fwd_blk8<F, LOGN, M, 0, false>(x, tw);
+    else fwd_block<F, LOGN, M, G::BC, G::BC + G::BB - 1, G::BC, G::TWA>(x, tw, G::jB(lane, 0));
     if constexpr (PRIO > 1) __builtin_amdgcn_s_setprio(PRIO - 2);
 #pragma unroll
     for (int m = 0; m < M; m++)
@@ -593,7 +783,8 @@ __device__ __forceinline__ void ntt_forward(double (&x)[M][Geo<LOGN>::E], double
         for (int e = 0; e < G::E; e++) x[m][e] = pC[m * G::XPAD + e];
     lds_wave_sync();
     before_last();
-    fwd_block<F, LOGN, M, 0, G::BC - 1, 0, G::TWA + G::TWB>(x, tw, G::jC(lane, 0));
+    if constexpr (BLK8) fwd_blk8<F, LOGN, M, 1, true>(x, tw);
+    else fwd_block<F, LOGN, M, 0, G::BC - 1, 0, G::TWA + G::TWB>(x, tw, G::jC(lane, 0));
 }
 
 // ntt_forward on decomposition digits (see DIGITS above).  -DHELM_SHORT_ROOT_STAGES=0 keeps the general stages (A/B).
@@ -627,7 +818,14 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
 #ifndef HELM_LEAN_INVERSE
 #define HELM_LEAN_INVERSE 1
 #endif
-    constexpr bool LEAN = HELM_LEAN_INVERSE != 0 && F::LAZY && lean_inverse_ok<F>::value && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3;
+    // BLK8 (twiddle source TwBlk8Inv): blocks C and B in the 8-point block form, block A with its two short-root stages as
+    // mul_broot.  A block-form block ends with the diagonal: slots 1-7 are fresh products (<= 0.94 p from inputs <= p/2),
+    // slot 0 the pure sum (<= 4 p).  Recentring slot 0 alone at each transpose keeps every sum below 10.7 p of 2^53 = 13.6 p
+    // (tests/test_short_root_blocks.py): 2 recentrings per transform instead of the radix-2 LEAN form's 8.
+    constexpr bool BLK8 = is_blk8<TW>::value;
+    static_assert(!BLK8 || (blk8_field<F>::value && F::LAZY && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3),
+                  "8-point block form: N = 512, centred output, a field of blk8_field");
+    constexpr bool LEAN = !BLK8 && HELM_LEAN_INVERSE != 0 && F::LAZY && lean_inverse_ok<F>::value && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3;
     // what the slot classes above assume of the layout: eight values per lane, three blocks of three stages, so that a
     // transpose hands a lane eight values of ONE slot of the block before (tests/test_lazy_bounds.py recomputes the bounds)
     static_assert(!LEAN || (G::E == 8 && G::BA + G::BB + G::BC == LOGN), "LEAN inverse: slot-class bounds are derived for Geo<9>");
@@ -637,7 +835,7 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
     // block's inputs <= 2.6 p and every sum <= 8 x 4.5 p = 36 p, a quarter of what a double holds exactly.
     // (CENTRE = false: the outputs stay as the last block leaves them, <= 8 x 2.6 p = 21 p - for a caller that reduces downstream)
     constexpr bool WIDE = wide_headroom<F>::value && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3;
-    if constexpr (LEAN) {
+    if constexpr (LEAN || BLK8) {
 #pragma unroll
         for (int e = 0; e < G::E; e++) HELM_BOUND(__builtin_fabs(x[e]) <= F::P * 0.5000001, 3);
     }
@@ -645,25 +843,27 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
 #pragma unroll
         for (int e = 0; e < G::E; e++) HELM_BOUND(__builtin_fabs(x[e]) <= F::P * 4.5, 3);
     }
-    inv_block<F, LOGN, 0, 0, G::BC - 1, 0>(x, tw, G::jC(lane, 0));
+    if constexpr (BLK8) inv_blk8<F, LOGN, 1>(x, tw);
+    else inv_block<F, LOGN, 0, 0, G::BC - 1, 0>(x, tw, G::jC(lane, 0));
     before_write();
     if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO - 1);
     double *pA = xbuf + G::baseA(lane), *pB = xbuf + G::baseB(lane), *pC = xbuf + G::baseC(lane);
 #pragma unroll
-    for (int e = 0; e < G::E; e++) pC[e] = ((LEAN && e >= 3) || (WIDE && e >= 1)) ? x[e] : reduce<F>(x[e]);
+    for (int e = 0; e < G::E; e++) pC[e] = ((LEAN && e >= 3) || ((WIDE || BLK8) && e >= 1)) ? x[e] : reduce<F>(x[e]);
     lds_wave_sync();
 #pragma unroll
     for (int e = 0; e < G::E; e++) x[e] = pB[G::offB2(e)];
     lds_wave_sync();
-    inv_block<F, LOGN, G::BC, G::BC, G::BC + G::BB - 1, G::TWC>(x, tw, G::jB(lane, 0));
+    if constexpr (BLK8) inv_blk8<F, LOGN, 0>(x, tw);
+    else inv_block<F, LOGN, G::BC, G::BC, G::BC + G::BB - 1, G::TWC>(x, tw, G::jB(lane, 0));
     if constexpr (PRIO > 1) __builtin_amdgcn_s_setprio(PRIO - 2);
 #pragma unroll
-    for (int e = 0; e < G::E; e++) pB[G::offB1(e)] = ((LEAN && e >= 5) || (WIDE && e >= 1)) ? x[e] : reduce<F>(x[e]);
+    for (int e = 0; e < G::E; e++) pB[G::offB1(e)] = ((LEAN && e >= 5) || ((WIDE || BLK8) && e >= 1)) ? x[e] : reduce<F>(x[e]);
     lds_wave_sync();
 #pragma unroll
     for (int e = 0; e < G::E; e++) x[e] = pA[G::offA1(e)];
     lds_wave_sync();
-    inv_block<F, LOGN, 6, LOGN - G::BA, LOGN - 1, G::TWC + G::TWB>(x, tw, G::jA(lane, 0));
+    inv_block<F, LOGN, 6, LOGN - G::BA, LOGN - 1, G::TWC + G::TWB, TW, BLK8>(x, tw, G::jA(lane, 0));
     if constexpr (CENTRE) {
 #pragma unroll
         for (int e = 0; e < G::E; e++) x[e] = reduce<F>(x[e]);
