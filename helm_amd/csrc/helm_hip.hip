@@ -197,10 +197,6 @@ struct PbsCfg {
     // level-at-a-time path: key columns fetched before the level's transform (the rest after it)
     // (2 of k+1 = 3: fetching the third one early as well measured the same in the lockstep build)
     static constexpr int EARLY_COLS = 2;
-#ifndef HELM_PRIO_STAGES
-#define HELM_PRIO_STAGES 1 /* 0: plain oldest-first issue (109 k instead of 116 k gates/s) */
-#endif
-    static constexpr bool PRIO_STAGES = HELM_PRIO_STAGES != 0;
     using G = Geo<LOGN>;
     static constexpr int K1 = K + 1;
     static constexpr int SLOTS = K > 1 ? K : 1; // exchange slots per wave (also carry the hand-over)
@@ -215,11 +211,8 @@ struct PbsCfg {
     static constexpr int WAVE_STRIDE = WAVE_STRIDE_X > (ACC3 + 1) / 2 ? WAVE_STRIDE_X : (ACC3 + 1) / 2;
     static constexpr int slot_off(int s) { return s == 0 ? 0 : G::XPAD + (s - 1) * SLOT_STRIDE; }
     static constexpr int TW_ROWS = G::TWB + G::TWC;
-    // the 8-point block form of the N = 512 transforms (ntt_fp64.h fwd_blk8 / inv_blk8; -DHELM_BLK8=0: the radix-2 blocks)
-#ifndef HELM_BLK8
-#define HELM_BLK8 1
-#endif
-    static constexpr bool BLK8 = HELM_BLK8 != 0 && blk8_field<F>::value && LOGN == 9 && TW == TW_LANE_FREG;
+    // the 8-point block form of the N = 512 transforms (ntt_fp64.h fwd_blk8 / inv_blk8; profiles/r07/ab_gates_blk8.txt)
+    static constexpr bool BLK8 = blk8_field<F>::value && LOGN == 9 && TW == TW_LANE_FREG;
     static_assert(!BLK8 || TW_ROWS == 14, "the table holds the 2 x 7 block-form twiddles of the inverse");
     static constexpr size_t X_OFF = 0;                                                // double [K1][WAVE_STRIDE]
     static constexpr size_t TW_OFF = X_OFF + sizeof(double) * K1 * WAVE_STRIDE;       // double [TW_ROWS][64]
@@ -360,8 +353,9 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
     // lowers its priority as it advances through the step - 3 from the second barrier through the
     // inverse transform and the first level, 2 for the second level, 1 for the last level's digits and
     // transform, 0 for its products - so whoever is behind goes first and the three reach the first
-    // barrier within one short stage of each other (finer stages towards the end, where it matters).
-    constexpr bool PRIO = NB > 1 && C::PRIO_STAGES;
+    // barrier within one short stage of each other (finer stages towards the end, where it matters).  Plain oldest-first
+    // issue measured 109 k instead of 116 k gates/s.
+    constexpr bool PRIO = NB > 1;
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
     STAMP_DECL
     while (i < n) {
@@ -521,10 +515,6 @@ struct WideCfg {
     static constexpr int LOGN = LOGN_, K = K_, L = L_, K1 = K_ + 1, NW = (K_ + 1) * L_;
     using G = Geo<LOGN>;
     static constexpr int MAX_SMALL_N = 1024;
-#ifndef HELM_WIDE_PRIO
-#define HELM_WIDE_PRIO 1
-#endif
-    static constexpr bool PRIO = HELM_WIDE_PRIO != 0;
     static constexpr int ACC3 = (3 * G::N - 64 + 1) / 2 * 2; // u32 entries per polynomial (see PbsCfg)
     static constexpr int TW_ROWS = G::TWB + G::TWC;
     static constexpr size_t X_OFF = 0;                                              // double [NW][XPAD]
@@ -542,7 +532,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
                                                             const uint32_t *__restrict__ tvs,
                                                             const double *__restrict__ bsk,
                                                             const double *__restrict__ tw_fwd,
-                                                            uint32_t *__restrict__ out_big, int n, int logB, int wave_map)
+                                                            uint32_t *__restrict__ out_big, int n, int logB)
 {
     constexpr int LOGN = C::LOGN, K = C::K, L = C::L, K1 = C::K1, NW = C::NW;
     using F = typename C::F;
@@ -562,23 +552,22 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     // three of them and bounds the forward phase.  A unit's cost grows with the depth of its digit (the carry
     // chain runs from the last level down to the wave's own): the three cheapest units - the last level of each
     // polynomial - go to SIMD 0, and the three level-0 waves, which also run the inverse transforms, to three
-    // different SIMDs (wave_map = 0 keeps the plain (polynomial, level) order: 3.6 - 4.6 % slower, same-process
-    // A/B in tools/ab_wide.py).
+    // different SIMDs (the plain (polynomial, level) order measured 3.6 - 4.6 % slower,
+    // profiles/r02/wide_kernel_experiments.txt).
     int r = w / L, lev = w - r * L;
-    if (K1 == 3 && L == 3 && (wave_map & 1)) {
+    if constexpr (K1 == 3 && L == 3) {
         // w:  0  1  2  3  4  5  6  7  8      (two bits per wave, packed: a table indexed by w would live in scratch)
         // r:  0  0  1  2  1  0  1  2  2      lev:  2  0  0  0  2  1  1  1  2
         constexpr unsigned RR = 0u | 0u << 2 | 1u << 4 | 2u << 6 | 1u << 8 | 0u << 10 | 1u << 12 | 2u << 14 | 2u << 16;
         constexpr unsigned LL = 2u | 0u << 2 | 0u << 4 | 0u << 6 | 2u << 8 | 1u << 10 | 1u << 12 | 1u << 14 | 2u << 16;
         r = (int)((RR >> (2 * w)) & 3u);
         lev = (int)((LL >> (2 * w)) & 3u);
-    } else if (K1 == 2 && L == 3 && (wave_map & 1)) {
+    } else if constexpr (K1 == 2 && L == 3) {
         // six waves sit 2 / 2 / 1 / 1 on the SIMDs: the two inverse waves (level 0) alone on SIMDs 2 and 3, the
-        // last-level units on SIMD 0, the level-1 units on SIMD 1
+        // last-level units on SIMD 0, the level-1 units on SIMD 1.  The polynomial stays r = w / L; only the levels are
+        // permuted (a table for r as well costs 9 - 10 more registers at the same occupancy)
         // w:  0  1  2  3  4  5        r:  0  0  0  1  1  1        lev:  2  1  0  0  2  1
-        constexpr unsigned RR = 0u | 0u << 2 | 0u << 4 | 1u << 6 | 1u << 8 | 1u << 10;
         constexpr unsigned LL = 2u | 1u << 2 | 0u << 4 | 0u << 6 | 2u << 8 | 1u << 10;
-        r = (int)((RR >> (2 * w)) & 3u);
         lev = (int)((LL >> (2 * w)) & 3u);
     }
     const PbsJob job = jobs[blockIdx.x];
@@ -604,11 +593,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     // kernel (2 x 14 doubles: 110 -> 166 registers, the limit for the three waves of SIMD 0 is 168) instead of read from the
     // LDS lane table in every transform - the reads sat on the latency chain of a step: 3.5 % faster (64 bootstraps: 3.136
     // -> 3.024 ms, 256: 3.444 -> 3.324 ms, same box, alternating, identical ciphertexts; forward direction alone: 1.4 %).
-    // N = 1024 keeps the table (2 x 28 doubles spill).  -DHELM_WIDE_TW_REG=0 is round 3's form.
-#ifndef HELM_WIDE_TW_REG
-#define HELM_WIDE_TW_REG 3 /* bit 0: forward twiddles in registers, bit 1: inverse */
-#endif
-    constexpr int TWR = LOGN == 9 ? HELM_WIDE_TW_REG : 0;
+    // N = 1024 keeps the table (2 x 28 doubles spill).
+    constexpr int TWR = LOGN == 9 ? 3 : 0; // bit 0: forward twiddles in registers, bit 1: inverse
     TwLane<LOGN, false> twf0;
     TwLane<LOGN, true> twi0;
     twf0.base = TW + lane;
@@ -664,13 +650,14 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     const int rep = logB * L;
 
     STAMP_DECL
-    if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     // Key words (k+1 polynomials of this wave's row and level).  Nine waves x 12 loads of 1 KiB per step keep the CU's
     // vector-memory path busy for ~1.7 k cycles, and a wave cannot start its arithmetic until its loads are accepted:
     // finer per-phase stamps showed the load issue alone taking 0.3 k (oldest wave) to 1.6 k cycles (youngest) at the
     // top of a step.  The six waves that idle during the inverse transforms therefore fetch the NEXT step's words
     // right after barrier 1, into the registers their products have just released; only the three inverse waves
-    // still load at the top of the step (wave_map bit 1 set: every wave loads at the top, the round-1 order, for A/B).
+    // still load at the top of the step (every wave loading there measured 5 % slower,
+    // profiles/r02/wide_kernel_experiments.txt).
     double2 kw[K1][E / 2];
     auto load_keys = [&](int ii) {
         const unsigned so = (unsigned)ii * step_bytes + wave_off;
@@ -679,7 +666,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
 #pragma unroll
             for (int e2 = 0; e2 < E / 2; e2++) kw[c][e2] = kb.load(so + (unsigned)(c * L) * poly_bytes, e2 * 1024);
     };
-    const bool ahead = !(wave_map & 2) && lev != 0;
+    const bool ahead = lev != 0;
     int i = 0, a = 0;
     while (i < n && (a = __builtin_amdgcn_readfirstlane((int)MS[i])) == 0) i++; // a zero rotation adds nothing
     if (i < n && ahead) load_keys(i);
@@ -709,8 +696,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
         STAMP(0) // loads issued, rotation, decomposition
         // the SIMD that hosts three of the nine waves bounds this phase: stepping the issue priority down
         // block by block keeps its waves abreast instead of letting the youngest finish alone
-        ntt_forward_digits<F, LOGN, 1, C::PRIO ? 3 : 0>(x, xb, twf, lane);
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
+        ntt_forward_digits<F, LOGN, 1, 3>(x, xb, twf, lane);
+        __builtin_amdgcn_s_setprio(0);
         STAMP(1) // forward transform
 #pragma unroll
         for (int c = 0; c < K1; c++) {
@@ -745,7 +732,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
         STAMP(4) // inverse side (lev = 0) or nothing
         lds_block_sync(); // accumulator copies published, columns cleared
         STAMP(5) // barrier 2
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         i = inext;
         a = anext;
     }
@@ -791,6 +778,9 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
 //                 stretches from 5.7 k to 9 k cycles (5 % slower than in step); BELOW them (they only have to be done by the
 //                 end of the interval) and the forward waves at one flat priority: 4 % FASTER than in step - the default.
 //                 Same barriers per step, same arithmetic: identical ciphertexts.
+// Issue priorities (profiles/r04/duo_experiments.txt, profiles/r05/ab_duo1024_fpi.jsonl): at N = 512 as just described, in
+// either build; at N = 1024 the forward waves step down 3 -> 2 -> 1 and the inverse waves go first, in either build (flat
+// priorities and none measured 5 % slower there).
 // ------------------------------------------------------------------------------------
 template <typename F_, int LOGN_, int K_, int L_, bool STAG_>
 struct DuoCfg {
@@ -808,6 +798,8 @@ struct DuoCfg {
     static constexpr int TW_ROWS = G::TWB + G::TWC;
     static_assert(L >= 2, "part A needs at least one level");
     static_assert(K1 == 2 || K1 == 3, "wave maps are written for k = 1 and k = 2");
+    static constexpr bool FLAT = LOGN < 10;            // forward waves at one priority (2) instead of stepping 3 -> 2 -> 1
+    static constexpr bool INV_LOW = STAG && LOGN < 10; // inverse waves below the other bootstrap's forward waves
     static constexpr size_t TW_SHARED = COMPACT ? sizeof(double) * TW_ROWS * 64 : 0; // at the workgroup's base, before the bootstraps
     // per bootstrap
     static constexpr size_t X_OFF = 0;                                              // double [NWB][XPAD]
@@ -823,7 +815,7 @@ template <typename C>
 __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
                                                            const uint32_t *__restrict__ raw_in, const uint32_t *__restrict__ tvs,
                                                            const double *__restrict__ bsk, const double *__restrict__ tw_fwd,
-                                                           uint32_t *__restrict__ out_big, int n, int logB, int flags, int count)
+                                                           uint32_t *__restrict__ out_big, int n, int logB, int count)
 {
     constexpr int LOGN = C::LOGN, K = C::K, L = C::L, K1 = C::K1, NB = C::NB, NWB = C::NWB;
     using F = typename C::F;
@@ -888,9 +880,6 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     for (int q = wb; q < C::TW_ROWS; q += NWB) TW[q * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(q, lane)];
     for (int j = tid; j < K1 * N; j += 64 * NWB) COL[j] = 0.0;
     // the forward direction's per-lane twiddles in registers (123 -> 151): 1.5 % (same-box A/B with the wide kernel's)
-#ifndef HELM_DUO_TW_REG
-#define HELM_DUO_TW_REG 1
-#endif
     TwLane<LOGN, false> twf0;
     TwLane<LOGN, true> twi;
     twf0.base = TW + lane;
@@ -898,9 +887,8 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     twf0.fill_uniform(tw_fwd);
     twi.fill_uniform(tw_fwd);
     __syncthreads();
-    typename std::conditional<(HELM_DUO_TW_REG & 1) != 0, TwLaneReg<LOGN, false>, TwLane<LOGN, false>>::type twf;
-    if constexpr ((HELM_DUO_TW_REG & 1) != 0) twf.load(twf0);
-    else twf = twf0;
+    TwLaneReg<LOGN, false> twf;
+    twf.load(twf0);
 
     // accumulator (0, ..., 0, X^{-b~} tv): part B of polynomial r owns it (registers) and publishes the unrolled u32 copy
     uint32_t *acc_r = ACC + (size_t)r * C::ACC3;
@@ -940,8 +928,6 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
     const int neg_B = -(1 << logB);
     const int rep = logB * L;
-    const bool prio = (flags & 1) != 0;
-    const bool flat = (flags & 4) != 0; // forward waves keep one priority (2) instead of stepping 3 -> 2 -> 1
 
     // key words of one level of this wave's row: k+1 polynomials
     double2 kw[K1][E / 2];
@@ -967,10 +953,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
         const int i = tt >> 1;
         if (tt >= 0 && tt < 2 * n && !(tt & 1)) {
             // ---- forward interval of step i --------------------------------------------------------------------------
-            if (prio) {
-                if (flat) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(3);
-            }
+            __builtin_amdgcn_s_setprio(C::FLAT ? 2 : 3);
             const int a = __builtin_amdgcn_readfirstlane((int)MS[i]);
             uint32_t st[E];
             {
@@ -991,7 +974,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
 #pragma unroll
                 for (int e = 0; e < E; e++) x[0][e] = (double)decompose_step(st[e], logB, half_m1, neg_B);
                 ntt_forward_digits<F, LOGN, 1>(x, xb, twf, lane);
-                if (prio && !flat) __builtin_amdgcn_s_setprio(1);
+                if constexpr (!C::FLAT) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int c = 0; c < K1; c++) {
                     double *col = COL + (size_t)c * N + lane;
@@ -1013,7 +996,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
                     for (int e = 0; e < E; e++) x[0][e] = (double)decompose_step(st[e], logB, half_m1, neg_B, lev == 0);
                     if (lev != L - 2) load_keys(i, lev); // (the first level's words came an interval ahead)
                     ntt_forward_digits<F, LOGN, 1>(x, xb, twf, lane);
-                    if (prio && !flat) { // a wave steps its priority down as it advances: whoever is behind goes first (see k_pbs)
+                    if constexpr (!C::FLAT) { // a wave steps its priority down as it advances: whoever is behind goes first (see k_pbs)
                         if (lev) __builtin_amdgcn_s_setprio(2);
                         else __builtin_amdgcn_s_setprio(1);
                     }
@@ -1031,12 +1014,9 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
             STAMP(0) // rotation, digits, forward transforms, products
         } else if (tt >= 0 && tt < 2 * n) {
             // ---- inverse interval of step i: every product of the step is in its column ------------------------------
-            // in step: everybody waits for the inverse waves, they go first.  Staggered: flag 2 puts the inverse chain BELOW the
-            // other bootstrap's forward waves instead (it only has to be done by the end of their interval)
-            if (prio) {
-                if (C::STAG && (flags & 2)) __builtin_amdgcn_s_setprio(0);
-                else __builtin_amdgcn_s_setprio(3);
-            }
+            // in step: everybody waits for the inverse waves, they go first.  INV_LOW puts the inverse chain BELOW the other
+            // bootstrap's forward waves instead (it only has to be done by the end of their interval)
+            __builtin_amdgcn_s_setprio(C::INV_LOW ? 0 : 3);
             if (g == 1) {
                 double mine[E];
                 double *col = COL + (size_t)r * N + lane;
@@ -1086,7 +1066,8 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
 //                                    key rows (k+1 transforms, (k+1)^2 products); idle during the inverse transforms.
 // Wave w serves bootstrap w % 3 in role w / 3: every SIMD carries three waves of about the same instruction count.  Three
 // workgroup barriers per step (digits published | column sums published | column sums consumed).  Ciphertexts identical
-// to every other build (exact integer sums in any order).
+// to every other build (exact integer sums in any order).  Issue priorities step down as a
+// wave advances, as in k_pbs (without them 7 % slower, profiles/r04/trio_experiments.txt).
 // ------------------------------------------------------------------------------------
 template <typename F_, int LOGN_, int K_, int L_>
 struct TrioCfg {
@@ -1109,14 +1090,13 @@ struct TrioCfg {
     static constexpr size_t BYTES = TW_BYTES + BOOT_BYTES * NB;
 };
 
-template <typename C, bool PRIO>
+template <typename C>
 __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
                                                             const uint32_t *__restrict__ raw_in, const uint32_t *__restrict__ tvs,
                                                             const double *__restrict__ bsk, const double *__restrict__ tw_fwd,
                                                             uint32_t *__restrict__ out_big, int n, int logB, int count)
 {
     constexpr int LOGN = C::LOGN, K = C::K, L = C::L, NB = C::NB, K1 = C::K1, HL = C::HL;
-    constexpr bool prio = PRIO; // compile-time: as a run-time flag the branches cost the helper role 98 spilled registers
     using F = typename C::F;
     using G = Geo<LOGN>;
     constexpr int N = G::N, E = G::E;
@@ -1183,7 +1163,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
             STAMP_BEGIN
             lds_block_sync(); // A: the digits of this step are published
             STAMP(1)
-            if (prio) __builtin_amdgcn_s_setprio(2);
+            __builtin_amdgcn_s_setprio(2);
             double s0[E], s1[E];
 #pragma unroll
             for (int q = 0; q < K1; q++) {
@@ -1207,7 +1187,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
 #pragma unroll
                     for (int e2 = 0; e2 < E / 2; e2++) bwl[c][e2] = kb.load(so + (unsigned)(c * L) * poly_bytes, e2 * 1024);
                 __builtin_amdgcn_sched_barrier(0);
-                if (prio && q == K1 - 1) __builtin_amdgcn_s_setprio(0);
+                if (q == K1 - 1) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
                 for (int c = 0; c < K1; c++)
 #pragma unroll
@@ -1231,7 +1211,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
                             }
                         }
                     }
-                if (prio && q == 0) __builtin_amdgcn_s_setprio(1);
+                if (q == 0) __builtin_amdgcn_s_setprio(1);
             }
             lds_wave_sync(); // the last transform's reads of the scratch (= slot 0) are done
             {
@@ -1285,7 +1265,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
     int cd[K1]; // wave-uniform column of each distance
 #pragma unroll
     for (int d = 0; d < K1; d++) cd[d] = p + d >= K1 ? p + d - K1 : p + d;
-    if (prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
 
     for (int i = 0; i < n; i++) {
         STAMP_BEGIN
@@ -1304,7 +1284,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
         STAMP(0)
         lds_block_sync(); // A: digits published (the accumulator copy in this wave's slots has been read)
         STAMP(1)
-        if (prio) __builtin_amdgcn_s_setprio(2);
+        __builtin_amdgcn_s_setprio(2);
         double mine[E], keep[E];
 #pragma unroll
         for (int lev = L - 2; lev >= 0; lev--) {
@@ -1324,7 +1304,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
 #pragma unroll
                 for (int e2 = 0; e2 < E / 2; e2++) bwl[d][e2] = kb.load(so_i + (unsigned)(cd[d] * L + lev) * poly_bytes, e2 * 1024);
             __builtin_amdgcn_sched_barrier(0);
-            if (prio && lev == 0) __builtin_amdgcn_s_setprio(0);
+            if (lev == 0) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int d = 0; d < K1; d++)
 #pragma unroll
@@ -1348,7 +1328,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
                         }
                     }
                 }
-            if (prio && lev == L - 2 && lev != 0) __builtin_amdgcn_s_setprio(1);
+            if (lev == L - 2 && lev != 0) __builtin_amdgcn_s_setprio(1);
         }
         {
             double *dst = xb + C::slot_off(0) + lane;
@@ -1379,7 +1359,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
         for (int e = 0; e < E; e++) mine[e] = reduce<F>(mine[e]);
         lds_block_sync(); // C: every hand-over slot has been read
         STAMP(4)
-        if (prio) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         ntt_inverse<F, LOGN>(mine, xb, twi, lane);
 #pragma unroll
         for (int e = 0; e < E; e++) accr[e] += to_torus32(mine[e]);
@@ -1473,7 +1453,7 @@ __device__ inline int tw_lane_index_half10(int s, int lane, int hh)
     return 0;
 }
 
-template <typename C, bool PRIO>
+template <typename C>
 __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
                                                              const uint32_t *__restrict__ raw_in, const uint32_t *__restrict__ tvs,
                                                              const double *__restrict__ bsk, const double *__restrict__ tw_fwd,
@@ -1583,7 +1563,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
     const int rep = logB * L;
     const uint32_t rnd = 1u << (31 - rep);
 
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
+    // issue priorities stepping down through the step (off: 6.61 against 6.18 ms per 768, profiles/r06/ab_tri10.jsonl)
+    __builtin_amdgcn_s_setprio(3);
     STAMP_DECL
     for (int i = 0; i < n; i++) {
         STAMP_BEGIN
@@ -1632,8 +1613,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
             __builtin_amdgcn_sched_barrier(0);
             ntt_forward<F, 9, 1, decltype(twf), 0, NoHook, 3>(x, xb, twf, lane);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PRIO)
-                if (lev == 0) __builtin_amdgcn_s_setprio(0);
+            if (lev == 0) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int e2 = 0; e2 < EH / 2; e2++) {
                 const double2 wr = kw[0][e2], wo = kw[1][e2];
@@ -1644,10 +1624,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
                 keep[2 * e2] = lev == L - 1 ? u0 : keep[2 * e2] + u0;
                 keep[2 * e2 + 1] = lev == L - 1 ? u1 : keep[2 * e2 + 1] + u1;
             }
-            if constexpr (PRIO) {
-                if (lev == L - 1) __builtin_amdgcn_s_setprio(2);
-                else if (lev == 1) __builtin_amdgcn_s_setprio(1);
-            }
+            if (lev == L - 1) __builtin_amdgcn_s_setprio(2);
+            else if (lev == 1) __builtin_amdgcn_s_setprio(1);
         }
         {
             double *dst = xb + C::HO_OFF + lane;
@@ -1657,7 +1635,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
         STAMP(0) // rotation, digits, forward half transforms, products, hand-over written
         lds_block_sync();
         STAMP(1) // barrier 1
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         {
             const double *src = X + (size_t)(2 * (1 - r) + h) * C::WAVE_DOUBLES + C::HO_OFF + lane;
             if constexpr (!F::LAZY) {
@@ -2114,7 +2092,6 @@ struct helm_hip_ctx {
     uint32_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: the key's four byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0;
-    int wide_map = 1;            // HELM_HIP_WIDE_MAP=0: k_pbs_wide with waves in (polynomial, level) order
     int ks_mfma = 1;             // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
     DevBuf<int8_t> d_dig;
     DevBuf<int32_t> d_dsum;
@@ -2131,11 +2108,7 @@ struct helm_hip_ctx {
                              // bootstraps per workgroup (round 6: 512 bootstraps of helm_cuda 5.11 -> 4.41 ms, profiles/r06/ab_tri10.jsonl);
                              // 1 / 2 k_pbs_duo's compact layout in step / staggered (round 5: 5.50 - 5.55 / 5.75 ms in the 51-bit field, the
                              // two-wave build of rounds 1-4 6.04); 0: a lockstep round
-    int duo1024_flags = 1;   // its issue priorities (HELM_HIP_DUO1024_FLAGS; bits as duo_flags): on, stepping down - flat (5) and off (0) measured 5 % slower
     int trio = 1;            // remainders of two to three bootstraps per CU on k_pbs_trio (HELM_HIP_TRIO=0: a partial lockstep round, round 3's choice)
-    int trio_flags = 1;      // bit 0: issue-priority staging (HELM_HIP_TRIO_FLAGS)
-    int duo_flags = 7;       // k_pbs_duo's issue priorities (HELM_HIP_DUO_FLAGS): bit 0 on at all; bit 1 staggered build: the inverse
-                             // waves BELOW the other bootstrap's forward waves; bit 2 forward waves at one priority instead of stepping down
     // per-call scratch
     DevBuf<PbsJob> d_pbs;
     DevBuf<KsJob> d_ks;
@@ -2378,7 +2351,7 @@ static hipError_t launch_pbs_wide(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires, raw, tvs, ctx->bsk,
-                       ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB, ctx->wide_map);
+                       ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB);
     print_stamps(ctx, C::NW, "wide: prep | fwd | products | bar1 | inverse | bar2");
     return hipGetLastError();
 }
@@ -2404,8 +2377,7 @@ static hipError_t launch_pbs_duo(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t 
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires,
-                       raw, tvs, ctx->bsk, ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB,
-                       C::LOGN >= 10 ? ctx->duo1024_flags : ctx->duo_flags, (int)count);
+                       raw, tvs, ctx->bsk, ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
     print_stamps(ctx, C::NW, "duo: forward | barriers | inverse | - | - | -");
     return hipGetLastError();
 }
@@ -2415,13 +2387,11 @@ static hipError_t launch_pbs_trio(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t
                                   const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = (ctx->trio_flags & 1) ? k_pbs_trio<C, true> : k_pbs_trio<C, false>; // priority staging on / off (A/B)
+    auto kern = k_pbs_trio<C>;
     if (!attr_done[ctx->device & 63]) {
-        for (auto kk : {k_pbs_trio<C, true>, k_pbs_trio<C, false>}) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)C::BYTES);
-            if (e != hipSuccess) return e;
-        }
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::BYTES);
+        if (e != hipSuccess) return e;
         attr_done[ctx->device & 63] = true;
         if (getenv("HELM_HIP_VERBOSE")) {
             hipFuncAttributes fa{};
@@ -2441,13 +2411,11 @@ static hipError_t launch_pbs_tri10(helm_hip_ctx *ctx, const PbsJob *jobs, int64_
                                    const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = (ctx->trio_flags & 1) ? k_pbs_tri10<C, true> : k_pbs_tri10<C, false>; // priority staging on / off (A/B)
+    auto kern = k_pbs_tri10<C>;
     if (!attr_done[ctx->device & 63]) {
-        for (auto kk : {k_pbs_tri10<C, true>, k_pbs_tri10<C, false>}) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)C::BYTES);
-            if (e != hipSuccess) return e;
-        }
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::BYTES);
+        if (e != hipSuccess) return e;
         attr_done[ctx->device & 63] = true;
         if (getenv("HELM_HIP_VERBOSE")) {
             hipFuncAttributes fa{};
@@ -2535,11 +2503,8 @@ static hipError_t launch_pbs_f(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t co
     // Round 4 (N = 512): the lane's block-B / block-C twiddles of the FORWARD direction sit in registers (TW_LANE_FREG: 28 of
     // them, 140 -> 162 registers, still three waves per SIMD) instead of being read from the LDS lane table in every one of the
     // three forward transforms of a step: +1.9 % (profiles/r04/lockstep_twiddle_registers.txt).  N = 1024 (two waves per
-    // bootstrap on one SIMD, 248 registers) reads the table.  -DHELM_LOCK_TW=TW_LANE is round 3's form at N = 512.
-#ifndef HELM_LOCK_TW
-#define HELM_LOCK_TW TW_LANE_FREG
-#endif
-    using Lock = PbsCfg<F, LOGN, K, L, LOGN == 9 ? HELM_LOCK_TW : TW_LANE>;
+    // bootstrap on one SIMD, 248 registers) reads the table.
+    using Lock = PbsCfg<F, LOGN, K, L, LOGN == 9 ? TW_LANE_FREG : TW_LANE>;
     constexpr bool HAS_TRIO = (LOGN == 9 && K == 2) || (LOGN == 10 && K == 1); // k_pbs_trio | k_pbs_tri10
     const int64_t cus = ctx->n_cus;
     int v = ctx->pbs_variant;
@@ -2792,13 +2757,9 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
         }
         if (const char *v = getenv("HELM_HIP_DUO")) ctx->duo_build = atoi(v) >= 0 && atoi(v) <= 2 ? atoi(v) : 2;
         if (const char *v = getenv("HELM_HIP_DUO1024")) ctx->duo1024 = atoi(v) >= 1 && atoi(v) <= 3 ? atoi(v) : 0;
-        if (const char *v = getenv("HELM_HIP_DUO1024_FLAGS")) ctx->duo1024_flags = atoi(v);
-        if (const char *v = getenv("HELM_HIP_DUO_FLAGS")) ctx->duo_flags = atoi(v);
         if (const char *v = getenv("HELM_HIP_TRIO")) ctx->trio = atoi(v) != 0;
-        if (const char *v = getenv("HELM_HIP_TRIO_FLAGS")) ctx->trio_flags = atoi(v);
         if (const char *v = getenv("HELM_HIP_CLOCK_PROBE")) ctx->clock_probe = atoi(v);
         if (const char *v = getenv("HELM_HIP_KS_MFMA")) ctx->ks_mfma = atoi(v);
-        if (const char *v = getenv("HELM_HIP_WIDE_MAP")) ctx->wide_map = atoi(v);
         while ((1 << ctx->logN) < P.N) ctx->logN++;
         HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
         ctx->stream = ctx->own_stream;
@@ -2951,7 +2912,7 @@ int helm_hip_bound_violations(helm_hip_ctx *ctx, uint32_t counts[8], int reset, 
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return HELM_SHORT_ROOT_STAGES != 0 ? 2 : 0; // both fields of this engine (5072^4 + 1, 6432^4 + 1) have short eighth roots
+    return 2; // both fields of this engine (5072^4 + 1, 6432^4 + 1) have short eighth roots
 }
 
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4])

@@ -55,21 +55,17 @@ namespace {
 // file) run without recentring.  Round 4: the pair is 5072^4 + 1 and 5096^4 + 1 (ntt_fp64.h FpG, FpG2; rounds 1-3:
 // Fp<49>, Fp49b with 2^53 / p = 14.2) - their fourth root of unity psi^(N/2) = +-b^2 is 25 bits long, so stage 1 of a
 // forward transform on digits (|d| <= 2^23: the split kernel is only chosen for pbs_logB <= 24) is ONE multiplication,
-// exact and inside (-p/2, p/2), instead of a modular one (HELM_SI_PLAIN_STAGE1; p0 p1 / 2 = 2^97.5 covers more than before).
+// exact and inside (-p/2, p/2), instead of a modular one (p0 p1 / 2 = 2^97.5 covers more than before;
+// profiles/r04/short_roots_field.txt).
 using F0 = FpG;
 using F1 = FpG2;
 // Round 6: the 46-bit pair (ntt_fp64.h FpJ, FpJ2) for k_pbs64k contexts whose LOADED key keeps the exact products below
 // p p' / 2 = 2^90.62 (helm_si_load_bootstrap_key; helm_si_field_bits() says which pair a context computes in)
 using J0 = FpJ;
 using J1 = FpJ2;
-#ifndef HELM_SI_PLAIN_STAGE1
-#define HELM_SI_PLAIN_STAGE1 1
-#endif
-template <typename F>
 __device__ __forceinline__ double stage1_digit_product(double digit, double w1)
 {
-    if constexpr (HELM_SI_PLAIN_STAGE1) return digit * w1; // |digit| <= 2^23, |w1| = b^2 < 2^24.7: exact, < p/2
-    else return mulmod<F>(digit, w1);
+    return digit * w1; // |digit| <= 2^23, |w1| = b^2 < 2^24.7: exact, < p/2
 }
 
 #ifdef HELM_WIDE_STAMPS
@@ -238,7 +234,7 @@ __device__ __forceinline__ void pbs64_body(unsigned char *smem, const double *__
             fetch(0, ka);
             __builtin_amdgcn_sched_barrier(0);
             STAMP(0) // rotation, decomposition, first key chunk issued
-            ntt_forward<F, LOGN, 1, decltype(twf), 0, NoHook, HELM_SI_PLAIN_STAGE1>(x, xb, twf, lane); // (digits: stage 1 plain)
+            ntt_forward<F, LOGN, 1, decltype(twf), 0, NoHook, 1>(x, xb, twf, lane); // (digits: stage 1 plain)
             STAMP(1) // forward transform
             __builtin_amdgcn_sched_barrier(0);
             fetch(1, kb2);
@@ -390,20 +386,13 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64(const Pbs64Job *__restr
 // parameter set the reference binary installs for LUT mode, PARAM_MESSAGE_1_CARRY_1_KS_PBS
 // (reference src/bin/helm.rs:301: k = 3, N = 512 [dimensions recalled]).  2 (k+1) waves:
 // wave w = (polynomial p = w >> 1, field f = w & 1), as k_pbs64; what changes with k + 1 > 2
-// polynomials is the hand-over: a wave's product with key column c belongs to polynomial c, and
-// the k foreign ones are summed into the (cleared) transform scratch of wave (c, f) with ds_add_f64 -
-// exact integers below 2^53, so the sum does not depend on the order the waves arrive in.  Four
-// workgroup barriers per step; 64 KB of LDS and at most 128 registers: TWO ciphertexts per CU.
+// polynomials is the hand-over: every wave publishes the spectrum of its digit polynomial, and wave
+// (p, f) gathers column p's sum from all k + 1 of them (see pbs64k_body).  Five workgroup barriers
+// per step; 64 KB of LDS and at most 128 registers: TWO ciphertexts per CU.  Measured against the
+// forms they replaced (profiles/r03/si_kernel_experiments.txt): the gather form against a ds_add_f64
+// scatter +6.4 %; the accumulator stored as [acc | -acc] (16) and the digits split between the two
+// field waves of a polynomial (17) each kept.
 // ------------------------------------------------------------------------------------
-#ifndef HELM_SI_K_SPLIT_DIGITS
-#define HELM_SI_K_SPLIT_DIGITS 1
-#endif
-#ifndef HELM_SI_K_ACC2
-#define HELM_SI_K_ACC2 1 // k_pbs64k: the accumulator polynomials stored with their negated copies behind them
-#endif
-#ifndef HELM_SI_K_GATHER
-#define HELM_SI_K_GATHER 1 // k_pbs64k: column sums gathered by the owner of the column instead of scattered with ds_add_f64
-#endif
 //
 // N = 1024 (k = 2, the 3-bit set shortint_m2c1): the same six waves and two ciphertexts per CU, but the LDS of the N = 512
 // layout would be 93 KB (scratch 51 KB + twiddles 16 KB + accumulator 24 KB, 48 KB as [acc | -acc]).  So the accumulator
@@ -422,14 +411,13 @@ struct Pbs64kCfg {
     static constexpr int TW_IDX = G::N >> G::BC, TW_FIELD = TW_IDX + G::TWC * 64;
     static constexpr size_t TW_OFF = X_OFF + sizeof(double) * NW * G::XPAD;       // double [2][TW_FIELD]
     static constexpr size_t ACC_OFF = TW_OFF + sizeof(double) * 2 * TW_FIELD;     // u64 [K1][N] (none: ACC_X)
-    // HELM_SI_K_ACC2: every polynomial is stored as [acc | -acc] (2N words): a rotated read X^a acc is then ONE indexed read,
+    // every polynomial is stored as [acc | -acc] (2N words): a rotated read X^a acc is then ONE indexed read,
     // no sign logic (5 vector instructions per coefficient in a kernel that is bound by its instruction stream)
-    static constexpr int ACC_LEN = (HELM_SI_K_ACC2 && !ACC_X) ? 2 * G::N : G::N;
+    static constexpr int ACC_LEN = ACC_X ? G::N : 2 * G::N;
     static constexpr size_t MS_OFF = ACC_OFF + (ACC_X ? 0 : sizeof(uint64_t) * K1 * ACC_LEN); // u16 [n+1]
     static constexpr size_t BYTES = (MS_OFF + sizeof(uint16_t) * (MAX_SMALL_N + 1) + 15) / 16 * 16;
     static_assert(NW <= 16, "a workgroup holds at most 16 waves");
     static_assert(2 * BYTES <= 160 * 1024, "two ciphertexts per CU");
-    static_assert(!ACC_X || (HELM_SI_K_GATHER && HELM_SI_K_SPLIT_DIGITS), "ACC_X is built on the gather form with split digits");
     // ACC_X: coefficient j of polynomial p, in the upper half of the scratch of wave (p, j >= N/2)
     __device__ static __forceinline__ int acc_x(int p, int j)
     {
@@ -446,7 +434,7 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
     // 46-bit pair: both leading forward stages plain on the digits (|d| <= 2^17), no recentring of the column sums - the
     // inverse transform takes them unreduced (ntt_inverse, WIDE)
     constexpr bool WIDE = wide_headroom<F>::value;
-    constexpr int DIG = WIDE ? 2 : HELM_SI_PLAIN_STAGE1;
+    constexpr int DIG = WIDE ? 2 : 1;
     using G = Geo<LOGN>;
     constexpr int N = G::N, E = G::E, H = E / 2;
     double *X = reinterpret_cast<double *>(smem + C::X_OFF);
@@ -464,7 +452,7 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
     const unsigned poly_bytes = (unsigned)(N / 2) * 16u;      // one key polynomial in one field
     const unsigned col_bytes = 2u * poly_bytes;               // both fields
     const unsigned step_bytes = (unsigned)(K1 * K1) * col_bytes;
-    const unsigned row_off = (HELM_SI_K_GATHER ? (unsigned)p : (unsigned)(p * K1)) * col_bytes + (unsigned)f * poly_bytes;
+    const unsigned row_off = (unsigned)p * col_bytes + (unsigned)f * poly_bytes;
     KeyBuf kb;
     kb.init(bsk, (size_t)n * step_bytes, lane);
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
@@ -481,7 +469,6 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
         const int a = __builtin_amdgcn_readfirstlane((int)MS[i]);
         if (a == 0) continue; // uniform over the workgroup
         const unsigned so_i = (unsigned)i * step_bytes + row_off;
-#if HELM_SI_K_GATHER
         // Gather form of the hand-over: wave (p, f) owns OUTPUT column p.  Every wave publishes the spectrum of its digit
         // polynomial in its scratch; after the barrier each wave reads all K1 spectra and multiplies them with the key
         // words of column p (rows 0..k): the column sum stays in registers - no LDS atomics, no clear, no data-dependent
@@ -505,17 +492,12 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
                     if (src >= N) v = 0ull - v;
                     v -= acc_own[eo];
                 } else {
-                    if constexpr (HELM_SI_K_ACC2) v = acc_p[src];
-                    else {
-                        v = acc_p[src & (N - 1)];
-                        if (src >= N) v = 0ull - v;
-                    }
+                    v = acc_p[src];
                     v -= acc_p[j];
                 }
                 const uint32_t st = (uint32_t)((v + (1ull << (63 - logB))) >> (64 - logB));
                 return (double)((int)((st + half_m1) & bmask) - (int)half_m1); // st <= B/2 stays, above it st - B
             };
-#if HELM_SI_K_SPLIT_DIGITS
             // the two field waves of a polynomial need the same digits: each makes half of them and hands them to the other
             // through the other's (free) transform scratch - one more barrier, half the decomposition work
             // (ACC_X: through the lower halves - the upper ones hold the accumulator until the barrier)
@@ -529,10 +511,6 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
             lds_block_sync();
 #pragma unroll
             for (int e = 0; e < H; e++) x[0][(1 - f) * H + e] = xb[(XO * (1 - f) * H + e) * 64 + lane];
-#else
-#pragma unroll
-            for (int e = 0; e < E; e++) x[0][e] = digit(e, 0);
-#endif
             ntt_forward<F, LOGN, 1, decltype(twf), 0, NoHook, DIG>(x, xb, twf, lane); // (digits: stage 1 - 46-bit pair: stages 1 and 2 - plain)
 #pragma unroll
             for (int e = 0; e < E; e++) xb[e * 64 + lane] = x[0][e];
@@ -561,67 +539,6 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
             __builtin_amdgcn_sched_barrier(0);
         }
         lds_block_sync(); // every wave has read: the scratches are free for the inverse transforms
-#else
-        // key words: all K1 columns of the first half of the spectrum slots at the top (the transform covers them), the
-        // second half slot pair by slot pair around the products (at most three quarters of the words live at once:
-        // the kernel must stay within 128 registers for two ciphertexts per CU)
-        double2 kw[H][K1];
-        auto fetch = [&](int u) {
-#pragma unroll
-            for (int c = 0; c < K1; c++) kw[u][c] = kb.load(so_i + (unsigned)c * col_bytes, u * 1024);
-        };
-#pragma unroll
-        for (int u = 0; u < H / 2; u++) fetch(u);
-        // ---- rotate / subtract, one signed digit per coefficient (pbs_l = 1) ------------------
-        double x[1][E];
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int j = G::jA(lane, e);
-            const int src = (j - a) & (2 * N - 1);
-            uint64_t v;
-            if constexpr (HELM_SI_K_ACC2) v = acc_p[src];
-            else {
-                v = acc_p[src & (N - 1)];
-                if (src >= N) v = 0ull - v;
-            }
-            v -= acc_p[j];
-            const uint32_t st = (uint32_t)((v + (1ull << (63 - logB))) >> (64 - logB));
-            x[0][e] = (double)((int)((st + half_m1) & bmask) - (int)half_m1); // st <= B/2 stays, above it st - B
-        }
-        ntt_forward<F, LOGN, 1, decltype(twf), 0, NoHook, DIG>(x, xb, twf, lane); // (digits: stage 1 - 46-bit pair: stages 1 and 2 - plain)
-        // the scratch becomes this wave's column sum: clear it, and wait until every wave is through its transform
-#pragma unroll
-        for (int e = 0; e < E; e++) xb[e * 64 + lane] = 0.0;
-        lds_block_sync();
-        // ---- products: column p stays, the others go to the waves of their polynomials --------
-        double mine[E];
-        auto products = [&](int u) {
-#pragma unroll
-            for (int c = 0; c < K1; c++) {
-                double *sum_c = X + (size_t)(c * 2 + f) * G::XPAD + lane;
-                const double t0 = mulmod<F>(x[0][2 * u], kw[u][c].x), t1 = mulmod<F>(x[0][2 * u + 1], kw[u][c].y);
-                if (c == p) {
-                    mine[2 * u] = t0;
-                    mine[2 * u + 1] = t1;
-                } else { // |t| <= 1.5 p, k of them and the own one: <= 6 p < 2^53, every partial sum exact
-                    lds_add_wg(sum_c + (2 * u) * 64, t0);
-                    lds_add_wg(sum_c + (2 * u + 1) * 64, t1);
-                }
-            }
-        };
-#pragma unroll
-        for (int u = 0; u < H; u++) {
-            if (u + H / 2 < H) {
-                fetch(u + H / 2);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            products(u);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_block_sync(); // every foreign product is in
-#pragma unroll
-        for (int e = 0; e < E; e++) mine[e] = reduce<F>(mine[e] + xb[e * 64 + lane]);
-#endif
         // WIDE: the outputs stay unreduced (<= 21 p): the CRT below reduces the DIFFERENCE of the two residues once instead of
         // both residues (X = r0 + p0 t equals the exact integer for any representative r0 with |r0| + |V| + p0 |t| < p0 p1)
         ntt_inverse<F, LOGN, decltype(twi), 0, !WIDE>(mine, xb, twi, lane);
@@ -642,7 +559,7 @@ __device__ __forceinline__ void pbs64k_body(unsigned char *smem, const double *_
             } else {
                 const uint64_t nv = acc_p[j] + xv;
                 acc_p[j] = nv;
-                if constexpr (HELM_SI_K_ACC2) acc_p[j + N] = 0ull - nv;
+                acc_p[j + N] = 0ull - nv;
             }
         }
         lds_block_sync(); // accumulator complete before the next step's rotated reads; scratch free again
@@ -695,7 +612,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
             if constexpr (C::ACC_X) reinterpret_cast<uint64_t *>(smem + C::X_OFF)[C::acc_x(pp, jj)] = v;
             else {
                 ACC[(size_t)pp * C::ACC_LEN + jj] = v;
-                if constexpr (HELM_SI_K_ACC2) ACC[(size_t)pp * C::ACC_LEN + N + jj] = 0ull - v;
+                ACC[(size_t)pp * C::ACC_LEN + N + jj] = 0ull - v;
             }
         }
     }
@@ -730,10 +647,10 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
 // half 1-h mirrored.  The halves meet once per step, in the last inverse stage.
 // Per step: (1) each of the four waves of a polynomial decomposes a quarter of its coefficients
 // and publishes the digits (int32, LDS); (2) stage 1 + half transform + products with the key
-// words of its half of the spectrum; other-polynomial sum handed over; (3) half inverse, exchange
-// with the other half, last stage; (4) CRT with the other field on half of the wave's
-// coefficients, accumulate.  Seven workgroup barriers per step, no redundant work except the
-// 16 stage-1 products per lane.
+// words of its half of the spectrum; other-polynomial sum handed over; (3) half inverse, then ONE
+// exchange among the four waves of the polynomial, after which each computes the last stage of a
+// quarter of the slots in both fields and lifts them with the CRT (lift_pairs), accumulating.  Five
+// workgroup barriers per step, no redundant work except the 16 stage-1 products per lane.
 // ------------------------------------------------------------------------------------
 // LDS flags between two waves of a workgroup (LDS-only fences, as lds_block_sync: global loads stay in flight).
 // set: everything this wave wrote to or read from LDS before is done when the value shows; wait: nothing this wave does
@@ -749,9 +666,6 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-#ifndef HELM_SI_MB_NESTED
-#define HELM_SI_MB_NESTED 1 // multi-bit: the group's key sum in nested form (2^g - 1 multiplications per position and column)
-#endif
 // the half transforms of k_pbs64s (a one-transpose form of the 1,024-point half - lane-bit stages through row swaps - was
 // bit-identical and measured -0.4 % / +0.7 %: profiles/r03/si_kernel_experiments.txt; removed in round 6)
 template <typename F, int LOGH, typename TW, int PRIO, typename HOOK = NoHook>
@@ -773,34 +687,6 @@ struct Pbs64sCfg {
     using G = Geo<LOGN>;      // decomposition geometry: E coefficients per lane
     using GS = Geo<LOGN - 1>; // half transforms
     static constexpr int MAX_SMALL_N = 1024;
-#ifndef HELM_SI_PRIO
-#define HELM_SI_PRIO 1
-#endif
-#ifndef HELM_SI_FUSED_XCHG
-#define HELM_SI_FUSED_XCHG 1 // one exchange for the last inverse stage and the CRT (two barriers instead of four)
-#endif
-#ifndef HELM_SI_KW1_EARLY
-#define HELM_SI_KW1_EARLY 1 // second key column fetched before the LAST block of the forward half transform
-#endif
-#ifndef HELM_SI_STAGE1_SRC
-#define HELM_SI_STAGE1_SRC 1 // k_pbs64s, one level: stage 1 of the full transform done by the wave that makes the digits
-#endif
-#ifndef HELM_SI_TWC_REGS
-#define HELM_SI_TWC_REGS 1 // classical k_pbs64s, one level: the lane's block-C twiddles of both half transforms in registers
-#endif
-#ifndef HELM_SI_PAIR_LIFT
-#define HELM_SI_PAIR_LIFT 1 // k_pbs64s: a wave lifts both outputs j and j + N/2 of a quarter of the slots (lift_pairs)
-#endif
-#ifndef HELM_SI_MIX_HALVES
-#define HELM_SI_MIX_HALVES 1 // k_pbs64s: one wave of either transform half per SIMD (the halves' last stages differ in cost)
-#endif
-#ifndef HELM_SI_STATIC_P
-#define HELM_SI_STATIC_P 1 // k_pbs64s: one inlined body per polynomial as well (the wave's polynomial is a literal inside)
-#endif
-#ifndef HELM_SI_LAZY_INV
-#define HELM_SI_LAZY_INV 1 // the half inverse leaves its outputs uncentred: the last stage recentres anyway
-#endif
-    static constexpr bool PRIO = HELM_SI_PRIO != 0;
     static constexpr int TW_IDX = GS::N >> GS::BC, TW_PART = TW_IDX + GS::TWC * 64; // per (field, half)
     static constexpr size_t X_OFF = 0;                                              // double [NW][GS::XPAD]
     static constexpr size_t TW_OFF = X_OFF + sizeof(double) * NW * GS::XPAD;        // double [2][2][TW_PART]
@@ -814,7 +700,7 @@ struct Pbs64sCfg {
     static constexpr size_t BYTES = FLAG_OFF + sizeof(uint32_t) * 2 * NW;
 };
 
-// The last inverse stage and the CRT of k_pbs64s, lifted in PAIRS (HELM_SI_PAIR_LIFT): wave (f, h) owns slots
+// The last inverse stage and the CRT of k_pbs64s, lifted in PAIRS: wave (f, h) owns slots
 // [(2 f + h) E/4, + E/4) of BOTH halves of its polynomial - from its own value of the slot and the three others' (other
 // half, other field, other field's other half) it computes the last stage of both outputs j and j + N/2 in both fields and
 // lifts both.  Against "every wave lifts the slots of its own half": 12 LDS reads per wave instead of 24 (and 12 values
@@ -847,7 +733,7 @@ __device__ __forceinline__ void lift_pairs(const double (&mine)[C::GS::E], const
     }
 }
 
-template <typename C, typename F, int h, int P = -1>
+template <typename C, typename F, int h, int P>
 __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *__restrict__ bsk, int n, int logB,
                                             double p0inv_mod_p1, double w1, double w1o, int p, int f, int lane)
 {
@@ -856,8 +742,8 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
     using GS = typename C::GS;
     constexpr int N = G::N, E = G::E, EH = GS::E, Q = E / 4, HC = EH / 2;
     // entry priority of the transforms (stepped down block by block inside them)
-    constexpr int PH = !C::PRIO ? 0 : 3;
-    constexpr bool SRC1 = HELM_SI_STAGE1_SRC && L == 1; // stage 1 where the digits are made
+    constexpr int PH = 3;
+    constexpr bool SRC1 = L == 1; // stage 1 where the digits are made (+1.6 %, profiles/r03/si_kernel_experiments.txt)
     double *X = reinterpret_cast<double *>(smem + C::X_OFF);
     uint64_t *ACC = reinterpret_cast<uint64_t *>(smem + C::ACC_OFF);
     using dig_t = typename C::dig_t;
@@ -872,8 +758,9 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
     dig_t *dig_p = DIG + (size_t)p * L * N; // [level][N]
     const double *twt = reinterpret_cast<const double *>(smem + C::TW_OFF);
     const double *tw_own = twt + (size_t)(f * 2 + h) * C::TW_PART, *tw_oth = twt + (size_t)(f * 2 + (1 - h)) * C::TW_PART;
-    // block-C twiddles of both transforms in registers where the kernel has them to spare (one level, classical: 176 + 60)
-    constexpr bool TWC_REGS = HELM_SI_TWC_REGS && L == 1;
+    // block-C twiddles of both transforms in registers where the kernel has them to spare (one level, classical: 176 + 60;
+    // +1.2 %, profiles/r03/si_kernel_experiments.txt)
+    constexpr bool TWC_REGS = L == 1;
     std::conditional_t<TWC_REGS, TwHybridC<LOGN - 1, false>, TwHybrid<LOGN - 1, false>> twf;
     std::conditional_t<TWC_REGS, TwHybridC<LOGN - 1, true>, TwHybrid<LOGN - 1, true>> twi;
     twf.t = tw_own, twi.t = tw_oth;
@@ -906,7 +793,6 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
             // and field (U + V psi^(N/2) for half 0, U - V psi^(N/2) for half 1), and the four results go straight
             // into the transform scratches of the four waves that transform them - no digit buffer, no conversions and
             // no stage-1 product on the consumers' side (they used to compute all sixteen, each half redundantly)
-            using FO = std::conditional_t<std::is_same<F, F0>::value, F1, F0>;
             double *x_f0 = X + (size_t)wave_of(p, f, 0) * GS::XPAD + lane, *x_f1 = X + (size_t)wave_of(p, f, 1) * GS::XPAD + lane;
             double *x_o0 = X + (size_t)wave_of(p, 1 - f, 0) * GS::XPAD + lane, *x_o1 = X + (size_t)wave_of(p, 1 - f, 1) * GS::XPAD + lane;
             auto digit = [&](int j) {
@@ -921,7 +807,7 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
             for (int u = 0; u < Q / 2; u++) {
                 const int e = quarter * (Q / 2) + u;
                 const double U = digit(G::jA(lane, e)), D1 = digit(G::jA(lane, e + EH));
-                const double Vf = stage1_digit_product<F>(D1, w1), Vo = stage1_digit_product<FO>(D1, w1o);
+                const double Vf = stage1_digit_product(D1, w1), Vo = stage1_digit_product(D1, w1o);
                 x_f0[e * 64] = U + Vf;
                 x_f1[e * 64] = U - Vf;
                 x_o0[e * 64] = U + Vo;
@@ -968,7 +854,7 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
 #pragma unroll
                 for (int u = 0; u < HC; u++) kw[0][u] = key(0 * L + lev, u);
             }
-            if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(PH);
+            __builtin_amdgcn_s_setprio(PH);
             double x[1][EH];
             if constexpr (SRC1) {
 #pragma unroll
@@ -977,29 +863,23 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
                 const dig_t *dg = dig_p + lev * N + lane;
 #pragma unroll
                 for (int e = 0; e < EH; e++) {
-                    const double U = (double)dg[64 * e], V = stage1_digit_product<F>((double)dg[64 * (e + EH)], w1);
+                    const double U = (double)dg[64 * e], V = stage1_digit_product((double)dg[64 * (e + EH)], w1);
                     x[0][e] = h ? U - V : U + V;
                 }
             }
             // the second column is asked for between the transform's second transpose and its last block: behind both
             // LDS round trips (fetching it before the transform was measured 1 % slower,
-            // profiles/r02/si_kernel_experiments.txt), with a block of arithmetic to cover the latency
+            // profiles/r02/si_kernel_experiments.txt, after it 0.6 %, profiles/r03/si_kernel_experiments.txt), with a
+            // block of arithmetic to cover the latency
             auto fetch_kw1 = [&]() {
 #pragma unroll
                 for (int u = 0; u < HC; u++) kw[1][u] = key(1 * L + lev, u);
             };
-#if HELM_SI_KW1_EARLY
             half_forward<F, LOGN - 1, decltype(twf), PH>(x, xb, twf, lane, fetch_kw1);
-#else
-            half_forward<F, LOGN - 1, decltype(twf), PH>(x, xb, twf, lane);
-#endif
-            if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             if (lev == 0) {
                 STAMP(2) // digits read, stage 1, half transform
             }
-#if !HELM_SI_KW1_EARLY
-            fetch_kw1();
-#endif
 #pragma unroll
             for (int c = 0; c < K1; c++) {
 #pragma unroll
@@ -1026,65 +906,22 @@ __device__ __forceinline__ void pbs64s_body(unsigned char *smem, const double *_
         lds_block_sync(); // hand-over read: scratch free again
         STAMP(4) // barrier 2, sum, barrier 3
         // ---- (3) half inverse, meet the other half, last stage -------------------------------
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(PH);
-        half_inverse<F, LOGN - 1, decltype(twi), PH, !(HELM_SI_LAZY_INV && HELM_SI_FUSED_XCHG)>(mine, xb, twi, lane); // a_h[e * 64 + lane], centred
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(PH);
+        // a_h[e * 64 + lane], uncentred: the last stage recentres anyway (centring here measured 1.3 % slower,
+        // profiles/r03/si_kernel_experiments.txt)
+        half_inverse<F, LOGN - 1, decltype(twi), PH, false>(mine, xb, twi, lane);
+        __builtin_amdgcn_s_setprio(0);
         STAMP(5) // half inverse
+        // ---- (3b, 4) one exchange for the last inverse stage and the CRT (two barriers instead of four): every wave
+        //      publishes its half inverse, and lift_pairs computes the last stage of its slots in both fields and lifts them
 #pragma unroll
         for (int e = 0; e < EH; e++)
-            if (!(HELM_SI_PAIR_LIFT && HELM_SI_FUSED_XCHG) || e / (EH / 4) != f * 2 + h) xb[e * 64 + lane] = mine[e]; // own slots stay
+            if (e / (EH / 4) != f * 2 + h) xb[e * 64 + lane] = mine[e]; // own slots stay
         lds_block_sync();
-#if HELM_SI_FUSED_XCHG && HELM_SI_PAIR_LIFT
         lift_pairs<C, F, h, true>(mine, x_half, x_field, X + (size_t)wave_of(p, 1 - f, 1 - h) * GS::XPAD, acc_p, f, w1, w1o,
                                   p0inv_mod_p1, lane);
         lds_block_sync(); // accumulator complete, scratch free again
-#elif HELM_SI_FUSED_XCHG
-        // ---- (3b, 4) one exchange: every wave publishes its half inverse; the wave that lifts a slot computes the
-        //      last inverse stage of that slot in BOTH fields (its own from registers + the other half, the other
-        //      field's from the two waves that hold it) and the CRT.  Same values as the two-exchange form.
-        {
-            using FO = std::conditional_t<std::is_same<F, F0>::value, F1, F0>;
-            const double *x_fh = X + (size_t)wave_of(p, 1 - f, 1 - h) * GS::XPAD; // other field, other half
-            constexpr int HH = EH / 2;
-#pragma unroll
-            for (int e = 0; e < HH; e++) {
-                const int s = f * HH + e;
-                const double a = mine[s], o = x_half[s * 64 + lane];
-                const double own = h ? reduce<F>(mulmod<F>(a - o, w1)) : reduce<F>(a + o);
-                const double a2 = x_field[s * 64 + lane], o2 = x_fh[s * 64 + lane];
-                const double oth = h ? reduce<FO>(mulmod<FO>(a2 - o2, w1o)) : reduce<FO>(a2 + o2);
-                const double r0 = f == 0 ? own : oth, r1 = f == 0 ? oth : own;
-                const double t = mulmod<F1>(r1 - r0, p0inv_mod_p1);
-                const uint64_t xv = (uint64_t)to_int64(r0) + F0::P_U64 * (uint64_t)to_int64(t);
-                acc_p[h * (N / 2) + s * 64 + lane] += xv;
-            }
-        }
-        lds_block_sync(); // accumulator complete, scratch free again
-#else
-#pragma unroll
-        for (int e = 0; e < EH; e++) {
-            const double o = x_half[e * 64 + lane];
-            // y[j] = a0 + a1 ; y[j + N/2] = (a0 - a1) * psi^-(N/2) = (a1 - a0) * psi^(N/2)
-            mine[e] = h ? reduce<F>(mulmod<F>(mine[e] - o, w1)) : reduce<F>(mine[e] + o);
-        }
-        lds_block_sync(); // the other half has read: scratch free again
-        STAMP(6) // half exchange, last stage, barriers 4 and 5
-        // ---- (4) CRT: field-f wave lifts slots [f*EH/2, (f+1)*EH/2) of its half ----------------
-        constexpr int HH = EH / 2;
-#pragma unroll
-        for (int e = 0; e < HH; e++) xb[e * 64 + lane] = mine[(1 - f) * HH + e];
-        lds_block_sync();
-#pragma unroll
-        for (int e = 0; e < HH; e++) {
-            const double own = mine[f * HH + e], oth = x_field[e * 64 + lane];
-            const double r0 = f == 0 ? own : oth, r1 = f == 0 ? oth : own;
-            const double t = mulmod<F1>(r1 - r0, p0inv_mod_p1);
-            const uint64_t xv = (uint64_t)to_int64(r0) + F0::P_U64 * (uint64_t)to_int64(t);
-            acc_p[h * (N / 2) + (f * HH + e) * 64 + lane] += xv;
-        }
-        lds_block_sync(); // accumulator complete
-#endif
-        STAMP(7) // CRT, barriers 6 and 7
+        STAMP(7) // last stage and CRT, barriers 4 and 5
     }
     STAMP_END((p * 2 + f) * 2 + h)
 }
@@ -1104,7 +941,7 @@ __host__ __device__ constexpr int bitrev_c(int v, int bits)
 // point of spectrum position j (probed once per context through the key-conversion kernel) and psi_pow the 2N
 // powers of psi.  Same wave roles, transforms, hand-over and CRT as pbs64s_body; n/g steps instead of n, the
 // accumulator is replaced instead of added to.
-template <typename C, typename F, int h, int P = -1>
+template <typename C, typename F, int h, int P>
 __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double *__restrict__ bsk, int n, int logB,
                                                double p0inv_mod_p1, double w1, double w1o, int p, int f, int lane, int g,
                                                const uint16_t *__restrict__ expo, const double *__restrict__ psi_pow)
@@ -1112,7 +949,7 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
     constexpr int LOGN = C::LOGN, K1 = C::K1;
     using G = typename C::G;
     using GS = typename C::GS;
-    constexpr int PH = !C::PRIO ? 0 : 3;
+    constexpr int PH = 3;
     constexpr int N = G::N, E = G::E, EH = GS::E, Q = E / 4, HC = EH / 2;
     double *X = reinterpret_cast<double *>(smem + C::X_OFF);
     uint64_t *ACC = reinterpret_cast<uint64_t *>(smem + C::ACC_OFF);
@@ -1133,7 +970,6 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
     const int quarter = f * 2 + h;
     const size_t part = (size_t)(GS::N / 2);
     const size_t bsk_step = (size_t)K1 * K1 * 4 * part; // one GGSW
-    [[maybe_unused]] const double2 *bsk_w = reinterpret_cast<const double2 *>(bsk) + ((size_t)p * K1 * 4 + f * 2 + h) * part + lane;
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
     [[maybe_unused]] const uint32_t bmask = (1u << logB) - 1u;
     const int subsets = 1 << g;
@@ -1142,13 +978,11 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
     // omega^k, k < EH (omega = psi^(2N/EH)), held by lane k: read with v_readlane by a uniform index
     const double om_tab = psi_pow[(lane & (EH - 1)) * (2 * N / EH)];
     const int om_lo = __double2loint(om_tab), om_hi = __double2hiint(om_tab);
-#if HELM_SI_MB_NESTED
     // key words through buffer loads: descriptor in scalar registers, scalar byte offset per (group, subset, column)
     const unsigned ggsw_bytes = (unsigned)(bsk_step * 16), col_bytes = (unsigned)(4 * part * 16);
     const unsigned wave_off = (unsigned)(((size_t)p * K1 * 4 + f * 2 + h) * part * 16);
     KeyBuf kbuf;
     kbuf.init(bsk, (size_t)(n / g) * subsets * ggsw_bytes, lane);
-#endif
     for (int t = 0; t < n / g; t++) {
         int am[3];
 #pragma unroll
@@ -1168,19 +1002,18 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
         }
         lds_block_sync(); // digits published
         // ---- (2) stage 1 of the full transform, half transform ----------------------------------
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(PH);
+        __builtin_amdgcn_s_setprio(PH);
         double x[1][EH];
         {
             const dig_t *dg = dig_p + lane;
 #pragma unroll
             for (int e = 0; e < EH; e++) {
-                const double U = (double)dg[64 * e], V = stage1_digit_product<F>((double)dg[64 * (e + EH)], w1);
+                const double U = (double)dg[64 * e], V = stage1_digit_product((double)dg[64 * (e + EH)], w1);
                 x[0][e] = h ? U - V : U + V;
             }
         }
         half_forward<F, LOGN - 1, decltype(twf), PH>(x, xb, twf, lane);
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
-#if HELM_SI_MB_NESTED
+        __builtin_amdgcn_s_setprio(0);
         // ---- the group's key in the transform domain, G[c] = sum_S M(e_S) .* K_S[p][c], in NESTED form, and the products
         //      x .* G[c].  M(e_S) is the product of its members' monomial vectors M_i = M(a~_i), so
         //        G = (K_000 + M_0 K_001) + M_1 (K_010 + M_0 K_011) + M_2 [(K_100 + M_0 K_101) + M_1 (K_110 + M_0 K_111)]:
@@ -1190,6 +1023,7 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
         //      one gathered power per lane and member (bq, fetched at the top of the step) times a wave-uniform power of
         //      omega read out of a lane-held table with v_readlane.  Walked slot pair by slot pair and column by column:
         //      the 2^g key words of one (slot pair, column) are fetched one iteration ahead (buffer loads: scalar offsets).
+        //      (The flat sum, one product per subset, measured 16.6 % slower: profiles/r03/si_kernel_experiments.txt.)
         static_assert(K1 == 2, "two key columns");
         double mine[EH], oth[EH];
         auto key_products = [&](auto g_const) {
@@ -1244,141 +1078,22 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
         else key_products(std::integral_constant<int, 2>());
 #pragma unroll
         for (int e = 0; e < EH; e++) xb[e * 64 + lane] = oth[e];
-#else
-        // ---- the group's key in the transform domain: G[c] = sum_S M(e_S) .* K_S[p][c], then the products
-        //      x .* G[c].  The spectrum positions of a lane are expo(lane, e) = c_lane + (2N/EH) rev(e)
-        //      (verified when the table is probed), so M(e_S)[e] = psi^(c_lane e_S) * omega^(e_S rev(e)) with
-        //      omega = psi^(2N/EH) of order EH: one gathered power per lane and subset, EH wave-uniform ones.
-        // The transformed digits wait in the wave's scratch meanwhile (their registers carry the key
-        // pipeline: the two key polynomials of a subset are fetched one half-step ahead of their use).
-        static_assert(K1 == 2, "two key columns, pipelined alternately");
-#pragma unroll
-        for (int e = 0; e < EH; e++) xb[e * 64 + lane] = x[0][e];
-        double gcol[K1][EH];
-        double2 ka[HC], kb[HC];
-        {
-            const double2 *kp = bsk_w + ((size_t)t * subsets) * bsk_step;
-#pragma unroll
-            for (int u = 0; u < HC; u++) ka[u] = kp[u * 64];
-#pragma unroll
-            for (int u = 0; u < HC; u++) kb[u] = (kp + (size_t)4 * part)[u * 64];
-        }
-        for (int S = 0; S < subsets; S++) {
-            int e_s = 0;
-#pragma unroll
-            for (int q = 0; q < 3; q++)
-                if ((S >> q) & 1) e_s += am[q];
-            e_s &= 2 * N - 1;
-            // the next subset's keys (the last iteration refetches its own: harmless, keeps the loop uniform)
-            const double2 *kn = bsk_w + ((size_t)t * subsets + (S + 1 < subsets ? S + 1 : S)) * bsk_step;
-            double mf[EH];
-            if (S != 0) {
-                // psi^(c_lane e_S) as the product of the members' powers (fetched at the top of the step);
-                // omega^(e_S rev(e)) out of the lane-held table by wave-uniform index: no memory access here
-                double bs = (S & 1) ? bq[0] : ((S & 2) ? bq[1] : bq[2]);
-                if ((S & 1) && (S & 2)) bs = reduce<F>(mulmod<F>(bs, bq[1]));
-                if ((S & 3) && (S & 4)) bs = reduce<F>(mulmod<F>(bs, bq[2]));
-                // |m| <= 0.51 p, every term <= 0.51 p: G <= 4.1 p before the recentring below
-#pragma unroll
-                for (int e = 0; e < EH; e++) {
-                    const int k = (e_s * bitrev_c(e, GS::LOGE)) & (EH - 1);
-                    const double om = __hiloint2double(__builtin_amdgcn_readlane(om_hi, k), __builtin_amdgcn_readlane(om_lo, k));
-                    mf[e] = mulmod<F>(bs, om);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < HC; u++) {
-                gcol[0][2 * u] = S == 0 ? ka[u].x : gcol[0][2 * u] + mulmod<F>(ka[u].x, mf[2 * u]);
-                gcol[0][2 * u + 1] = S == 0 ? ka[u].y : gcol[0][2 * u + 1] + mulmod<F>(ka[u].y, mf[2 * u + 1]);
-            }
-#pragma unroll
-            for (int u = 0; u < HC; u++) ka[u] = kn[u * 64];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < HC; u++) {
-                gcol[1][2 * u] = S == 0 ? kb[u].x : gcol[1][2 * u] + mulmod<F>(kb[u].x, mf[2 * u]);
-                gcol[1][2 * u + 1] = S == 0 ? kb[u].y : gcol[1][2 * u + 1] + mulmod<F>(kb[u].y, mf[2 * u + 1]);
-            }
-#pragma unroll
-            for (int u = 0; u < HC; u++) kb[u] = (kn + (size_t)4 * part)[u * 64];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_wave_sync();
-#pragma unroll
-        for (int e = 0; e < EH; e++) x[0][e] = xb[e * 64 + lane];
-        lds_wave_sync();
-        double col[K1][EH];
-#pragma unroll
-        for (int c = 0; c < K1; c++)
-#pragma unroll
-            for (int e = 0; e < EH; e++) col[c][e] = mulmod<F>(x[0][e], reduce<F>(gcol[c][e])); // <= 1.5 p
-        double mine[EH];
-#pragma unroll
-        for (int e = 0; e < EH; e++) {
-            xb[e * 64 + lane] = p == 0 ? col[1][e] : col[0][e];
-            mine[e] = p == 0 ? col[0][e] : col[1][e];
-        }
-#endif
         lds_block_sync();
 #pragma unroll
         for (int e = 0; e < EH; e++) mine[e] = reduce<F>(mine[e] + x_poly[e * 64 + lane]); // <= 11.4 p before
         lds_block_sync(); // hand-over read: scratch free again
         // ---- (3) half inverse, meet the other half, last stage -----------------------------------
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(PH);
-        half_inverse<F, LOGN - 1, decltype(twi), PH, !(HELM_SI_LAZY_INV && HELM_SI_FUSED_XCHG)>(mine, xb, twi, lane);
-        if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(PH);
+        half_inverse<F, LOGN - 1, decltype(twi), PH, false>(mine, xb, twi, lane); // uncentred, as in pbs64s_body
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int e = 0; e < EH; e++)
-            if (!(HELM_SI_PAIR_LIFT && HELM_SI_FUSED_XCHG) || e / (EH / 4) != f * 2 + h) xb[e * 64 + lane] = mine[e]; // own slots stay
+            if (e / (EH / 4) != f * 2 + h) xb[e * 64 + lane] = mine[e]; // own slots stay
         lds_block_sync();
-#if HELM_SI_FUSED_XCHG
-#if HELM_SI_PAIR_LIFT
+        // the lifted value REPLACES the accumulator
         lift_pairs<C, F, h, false>(mine, x_half, x_field, X + (size_t)wave_of(p, 1 - f, 1 - h) * GS::XPAD, acc_p, f, w1, w1o,
                                    p0inv_mod_p1, lane);
-#else
-        // ---- (3b, 4) one exchange: every wave publishes its half inverse; the wave that lifts a slot computes the
-        //      last inverse stage of that slot in BOTH fields (its own from registers + the other half, the other
-        //      field's from the two waves that hold it) and the CRT.  Same values as the two-exchange form.
-        {
-            using FO = std::conditional_t<std::is_same<F, F0>::value, F1, F0>;
-            const double *x_fh = X + (size_t)wave_of(p, 1 - f, 1 - h) * GS::XPAD; // other field, other half
-            constexpr int HH = EH / 2;
-#pragma unroll
-            for (int e = 0; e < HH; e++) {
-                const int s = f * HH + e;
-                const double a = mine[s], o = x_half[s * 64 + lane];
-                const double own = h ? reduce<F>(mulmod<F>(a - o, w1)) : reduce<F>(a + o);
-                const double a2 = x_field[s * 64 + lane], o2 = x_fh[s * 64 + lane];
-                const double oth = h ? reduce<FO>(mulmod<FO>(a2 - o2, w1o)) : reduce<FO>(a2 + o2);
-                const double r0 = f == 0 ? own : oth, r1 = f == 0 ? oth : own;
-                const double t = mulmod<F1>(r1 - r0, p0inv_mod_p1);
-                const uint64_t xv = (uint64_t)to_int64(r0) + F0::P_U64 * (uint64_t)to_int64(t);
-                acc_p[h * (N / 2) + s * 64 + lane] = xv;
-            }
-        }
-#endif
         lds_block_sync(); // accumulator complete, scratch free again
-#else
-#pragma unroll
-        for (int e = 0; e < EH; e++) {
-            const double o = x_half[e * 64 + lane];
-            mine[e] = h ? reduce<F>(mulmod<F>(mine[e] - o, w1)) : reduce<F>(mine[e] + o);
-        }
-        lds_block_sync();
-        // ---- (4) CRT: the lifted value REPLACES the accumulator ----------------------------------
-        constexpr int HH = EH / 2;
-#pragma unroll
-        for (int e = 0; e < HH; e++) xb[e * 64 + lane] = mine[(1 - f) * HH + e];
-        lds_block_sync();
-#pragma unroll
-        for (int e = 0; e < HH; e++) {
-            const double own = mine[f * HH + e], oth = x_field[e * 64 + lane];
-            const double r0 = f == 0 ? own : oth, r1 = f == 0 ? oth : own;
-            const double tt = mulmod<F1>(r1 - r0, p0inv_mod_p1);
-            acc_p[h * (N / 2) + (f * HH + e) * 64 + lane] = (uint64_t)to_int64(r0) + F0::P_U64 * (uint64_t)to_int64(tt);
-        }
-        lds_block_sync(); // accumulator complete
-#endif
     }
 }
 
@@ -1406,7 +1121,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64s(const Pbs64Job *__rest
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the waves of polynomial 1 take the halves the other way round: each SIMD (wave index mod 4) then holds one wave of
     // either half - the last inverse stage costs the h = 1 waves sixteen modular multiplications more than the h = 0 waves
-    const int p = w >> 2, f = (w >> 1) & 1, h = HELM_SI_MIX_HALVES ? ((w & 1) ^ p) : (w & 1);
+    // (+1.2 %, profiles/r03/si_kernel_experiments.txt)
+    const int p = w >> 2, f = (w >> 1) & 1, h = (w & 1) ^ p;
     const Pbs64Job job = jobs[blockIdx.x];
     const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
     for (int i = tid; i <= n; i += 64 * C::NW) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
@@ -1435,14 +1151,13 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64s(const Pbs64Job *__rest
     __syncthreads();
     // psi^(N/2): entry 1 of the full forward table of this wave's field
     const double w1 = f == 0 ? tw0[1] : tw1[1], w1o = f == 0 ? tw1[1] : tw0[1];
-    // one specialisation per (field, transform half): both are uniform over the wave
-    // (the polynomial as a literal too where HELM_SI_STATIC_P: the bodies are inlined, so `c == p` in the products and the
-    // row offsets fold - 66 v_cndmask per wave-step gone from the classical kernel)
-#define HELM_SI_BODY(FN, FT, HH, FF, ...)                                                      \
-    do {                                                                                       \
-        if (HELM_SI_STATIC_P && p == 0) FN<C, FT, HH, 0>(smem, bsk, n, logB, p0inv_mod_p1, w1, w1o, 0, FF, lane, ##__VA_ARGS__); \
-        else if (HELM_SI_STATIC_P) FN<C, FT, HH, 1>(smem, bsk, n, logB, p0inv_mod_p1, w1, w1o, 1, FF, lane, ##__VA_ARGS__);      \
-        else FN<C, FT, HH>(smem, bsk, n, logB, p0inv_mod_p1, w1, w1o, p, FF, lane, ##__VA_ARGS__);                            \
+    // one specialisation per (field, transform half, polynomial): all three are uniform over the wave
+    // (the polynomial as a literal too: the bodies are inlined, so `c == p` in the products and the row offsets fold - 66
+    // v_cndmask per wave-step gone from the classical kernel, +3.4 %, profiles/r03/si_kernel_experiments.txt)
+#define HELM_SI_BODY(FN, FT, HH, FF, ...)                                                                                    \
+    do {                                                                                                                     \
+        if (p == 0) FN<C, FT, HH, 0>(smem, bsk, n, logB, p0inv_mod_p1, w1, w1o, 0, FF, lane, ##__VA_ARGS__);                 \
+        else FN<C, FT, HH, 1>(smem, bsk, n, logB, p0inv_mod_p1, w1, w1o, 1, FF, lane, ##__VA_ARGS__);                        \
     } while (0)
     if constexpr (MB) {
         if (f == 0) {

@@ -787,14 +787,11 @@ __device__ __forceinline__ void ntt_forward(double (&x)[M][Geo<LOGN>::E], double
     else fwd_block<F, LOGN, M, 0, G::BC - 1, 0, G::TWA + G::TWB>(x, tw, G::jC(lane, 0));
 }
 
-// ntt_forward on decomposition digits (see DIGITS above).  -DHELM_SHORT_ROOT_STAGES=0 keeps the general stages (A/B).
-#ifndef HELM_SHORT_ROOT_STAGES
-#define HELM_SHORT_ROOT_STAGES 1
-#endif
+// ntt_forward on decomposition digits (see DIGITS above).
 template <typename F, int LOGN, int M, int PRIO = 0, typename TW>
 __device__ __forceinline__ void ntt_forward_digits(double (&x)[M][Geo<LOGN>::E], double *xbuf, const TW &tw, int lane)
 {
-    ntt_forward<F, LOGN, M, TW, PRIO, NoHook, HELM_SHORT_ROOT_STAGES != 0 ? 2 : 0>(x, xbuf, tw, lane);
+    ntt_forward<F, LOGN, M, TW, PRIO, NoHook, 2>(x, xbuf, tw, lane);
 }
 
 // Inverse (without the 1/N factor, which is folded into the bootstrapping key).
@@ -815,9 +812,6 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
     // slot class, so the next block's bound is eight times the largest value left unreduced: recentring slots 0-2 at
     // the first transpose (the rest <= 1.27 p) and 0-4 at the second (<= 0.8 p) keeps every sum below 0.75 x 2^53
     // (tests/test_lazy_bounds.py) and saves 8 of the 16 recentrings of the two transposes (24 instructions).
-#ifndef HELM_LEAN_INVERSE
-#define HELM_LEAN_INVERSE 1
-#endif
     // BLK8 (twiddle source TwBlk8Inv): blocks C and B in the 8-point block form, block A with its two short-root stages as
     // mul_broot.  A block-form block ends with the diagonal: slots 1-7 are fresh products (<= 0.94 p from inputs <= p/2),
     // slot 0 the pure sum (<= 4 p).  Recentring slot 0 alone at each transpose keeps every sum below 10.7 p of 2^53 = 13.6 p
@@ -825,7 +819,7 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
     constexpr bool BLK8 = is_blk8<TW>::value;
     static_assert(!BLK8 || (blk8_field<F>::value && F::LAZY && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3),
                   "8-point block form: N = 512, centred output, a field of blk8_field");
-    constexpr bool LEAN = !BLK8 && HELM_LEAN_INVERSE != 0 && F::LAZY && lean_inverse_ok<F>::value && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3;
+    constexpr bool LEAN = !BLK8 && F::LAZY && lean_inverse_ok<F>::value && CENTRE && LOGN == 9 && G::BA == 3 && G::BB == 3 && G::BC == 3;
     // what the slot classes above assume of the layout: eight values per lane, three blocks of three stages, so that a
     // transpose hands a lane eight values of ONE slot of the block before (tests/test_lazy_bounds.py recomputes the bounds)
     static_assert(!LEAN || (G::E == 8 && G::BA + G::BB + G::BC == LOGN), "LEAN inverse: slot-class bounds are derived for Geo<9>");

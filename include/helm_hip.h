@@ -143,7 +143,7 @@ int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4]);
 int helm_hip_field_bits(const helm_hip_ctx *ctx);
 /* Number of leading stages of every forward transform on decomposition digits that run as plain multiplications by short
  * roots of unity (2 in both fields of this engine: one radix-4 butterfly of 10 operations per four values instead of two
- * stages of modular butterflies; 0 when built with -DHELM_SHORT_ROOT_STAGES=0).  For benchmarks that count the operations
+ * stages of modular butterflies).  For benchmarks that count the operations
  * the kernels execute; results do not depend on it. */
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx);
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box, same-process A/B of the builds that serve launches of 257..512 bootstraps at N = 1024 (helm_cuda): the two-wave
-build with all levels in flight (round 1), k_pbs_duo's compact layout in step / staggered under several priority settings.
+build with all levels in flight (round 1), k_pbs_duo's compact layout in step / staggered.
 The engine reads its switches when a context is created, so one context per setting, the launches alternating.
 usage: ab_duo1024.py [B ...]   -> one line per (setting, B): best and median of the rounds, and a digest of the ciphertexts"""
 import hashlib
@@ -15,12 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import helm_amd  # noqa: E402
 
 SETTINGS = [("two-wave (HELM_HIP_DUO1024=0)", {"HELM_HIP_DUO1024": "0"}),
-            ("duo in step, flags 7", {"HELM_HIP_DUO1024": "1", "HELM_HIP_DUO1024_FLAGS": "7"}),
-            ("duo in step, flags 1", {"HELM_HIP_DUO1024": "1", "HELM_HIP_DUO1024_FLAGS": "1"}),
-            ("duo in step, flags 3", {"HELM_HIP_DUO1024": "1", "HELM_HIP_DUO1024_FLAGS": "3"}),
-            ("duo in step, flags 0", {"HELM_HIP_DUO1024": "1", "HELM_HIP_DUO1024_FLAGS": "0"}),
-            ("duo staggered, flags 7", {"HELM_HIP_DUO1024": "2", "HELM_HIP_DUO1024_FLAGS": "7"}),
-            ("duo staggered, flags 1", {"HELM_HIP_DUO1024": "2", "HELM_HIP_DUO1024_FLAGS": "1"})]
+            ("duo in step", {"HELM_HIP_DUO1024": "1"}),
+            ("duo staggered", {"HELM_HIP_DUO1024": "2"})]
 Bs = [int(x) for x in sys.argv[1:]] or [300, 384, 512]
 ck = helm_amd.ClientKey.generate("helm_cuda", seed=1)
 maxB = max(Bs)
@@ -28,8 +24,7 @@ bits = np.random.default_rng(0).integers(0, 2, size=2 * maxB).astype(bool)
 enc = ck.encrypt(bits)
 ctxs = []
 for name, env in SETTINGS:
-    for k in ("HELM_HIP_DUO1024", "HELM_HIP_DUO1024_FLAGS"):
-        os.environ.pop(k, None)
+    os.environ.pop("HELM_HIP_DUO1024", None)
     os.environ.update(env)
     sk = helm_amd.ServerKey(ck)
     w = sk.wires(3 * maxB)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Same-box, same-process A/B of what serves launches of 513..768 bootstraps at N = 1024 (helm_cuda, reference
 src/bin/helm.rs:141-146): a lockstep round with one SIMD in four empty (HELM_HIP_TRIO=0: rounds 1-5) against k_pbs_tri10
-(round 6: three bootstraps per workgroup, twelve (polynomial, transform half) waves) with its issue priorities on / off, in the
-lazy field FpI and in the 51-bit field; a full lockstep round (1,024) and k_pbs_duo (512) beside them for the width table of
+(round 6: three bootstraps per workgroup, twelve (polynomial, transform half) waves), in the lazy field FpI and in the 51-bit
+field; a full lockstep round (1,024) and k_pbs_duo (512) beside them for the width table of
 helm_hip_launch_costs.  The engine reads its switches when a context is created: one context per setting, launches alternating.
 usage: ab_tri10.py [B ...]   -> one JSON line per (setting, B): best and median of the rounds, digest of the ciphertexts"""
 import hashlib
@@ -16,13 +16,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import helm_amd  # noqa: E402
 
-KEYS = ("HELM_HIP_TRIO", "HELM_HIP_TRIO_FLAGS", "HELM_HIP_FIELD", "HELM_HIP_DUO1024")
+KEYS = ("HELM_HIP_TRIO", "HELM_HIP_FIELD", "HELM_HIP_DUO1024")
 SETTINGS = [("FpI: lockstep round (HELM_HIP_TRIO=0)", {"HELM_HIP_TRIO": "0"}),
-            ("FpI: k_pbs_tri10, priorities on", {"HELM_HIP_TRIO": "1", "HELM_HIP_TRIO_FLAGS": "1"}),
-            ("FpI: k_pbs_tri10, priorities off", {"HELM_HIP_TRIO": "1", "HELM_HIP_TRIO_FLAGS": "0"}),
+            ("FpI: k_pbs_tri10", {"HELM_HIP_TRIO": "1"}),
             ("FpI: k_pbs_tri10 three AND two per workgroup (HELM_HIP_DUO1024=3)", {"HELM_HIP_TRIO": "1", "HELM_HIP_DUO1024": "3"}),
             ("FpH: lockstep round (HELM_HIP_TRIO=0)", {"HELM_HIP_TRIO": "0", "HELM_HIP_FIELD": "51"}),
-            ("FpH: k_pbs_tri10, priorities on", {"HELM_HIP_TRIO": "1", "HELM_HIP_TRIO_FLAGS": "1", "HELM_HIP_FIELD": "51"})]
+            ("FpH: k_pbs_tri10", {"HELM_HIP_TRIO": "1", "HELM_HIP_FIELD": "51"})]
 Bs = [int(x) for x in sys.argv[1:]] or [300, 400, 512, 600, 768, 1024]
 ck = helm_amd.ClientKey.generate("helm_cuda", seed=1)
 maxB = max(Bs)
