@@ -169,6 +169,7 @@ HIP_API = {
     "helm_hip_set_stream": (C.c_int, [vp, vp]),
     "helm_hip_sync": (C.c_int, [vp]),
     "helm_hip_launch_quantum": (C.c_int64, [vp]),
+    "helm_hip_kernel_class": (C.c_int, [vp]),
     "helm_hip_launch_costs": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "helm_hip_field_bits": (C.c_int, [vp]),
     "helm_hip_short_root_stages": (C.c_int, [vp]),

@@ -113,7 +113,10 @@ __device__ __forceinline__ uint32_t modswitch(uint32_t x, int log2_2N)
 //   next = (state + B/2 - 1 + sb) >> logB;  digit = state - next * B
 // - five instructions per digit with the conversion (bit-field extract, three-operand add, shift,
 // 24-bit multiply-add, convert) instead of eight.  Needs state + B/2 < 2^32 (logB * L <= 31) and
-// next < 2^23; both follow from the field-size bound checked in helm_hip_ctx_create.
+// next < 2^23 (the 24-bit multiply).  next after the least significant level is at most 2^(logB (L-1)), so the second
+// needs logB (L-1) <= 22: for the five tuned shapes the capacity bound checked in helm_hip_ctx_create caps logB (L-1) at
+// 16 ((512,1,3), logB <= 8).  The generic kernel's domain does not (e.g. L = 5, logB = 6): it uses gen_decompose_step
+// (helm_pbs_generic.inc), the same recurrence with a full 32-bit multiply.
 // `last`: the most significant level.  There the state is at most B = 2^logB (it starts below 2^(L logB) and loses logB
 // bits per level, the rounding carry included), so its tie bit - bit 2 logB - 1 - is zero for logB >= 2, and for logB = 1
 // (s = 2: tie bit set) (s + tie) >> 1 == s >> 1: the bit never changes the digit and is not extracted.
@@ -2001,6 +2004,9 @@ __global__ __launch_bounds__(64) void k_ntt_roundtrip(const uint32_t *__restrict
     for (int e = 0; e < E; e++) dst[(size_t)blockIdx.x * N + G::jA(lane, e)] = to_torus32(x[0][e]);
 }
 
+// k_pbs_generic: k and pbs_l at run time, every admitted shape the tuned builds do not cover (and HELM_HIP_PBS_VARIANT=10)
+#include "helm_pbs_generic.inc"
+
 #endif // HELM_HIP_TU == 0
 
 // ------------------------------------------------------------------------------------
@@ -2109,6 +2115,11 @@ struct helm_hip_ctx {
                              // 1 / 2 k_pbs_duo's compact layout in step / staggered (round 5: 5.50 - 5.55 / 5.75 ms in the 51-bit field, the
                              // two-wave build of rounds 1-4 6.04); 0: a lockstep round
     int trio = 1;            // remainders of two to three bootstraps per CU on k_pbs_trio (HELM_HIP_TRIO=0: a partial lockstep round, round 3's choice)
+    bool generic = false;    // the shape has no tuned build: k_pbs_generic serves it (helm_hip_kernel_class)
+    bool gen_path = false;   // k_pbs_generic runs every launch (generic shape, or HELM_HIP_PBS_VARIANT=10): FpH, its own key layout
+    int gen_d = 1;           // k_pbs_generic: digit polynomials per batch (gen_batch)
+    size_t gen_lds = 0;      // k_pbs_generic: LDS bytes per workgroup (GenLds)
+    int gen_per_cu = 1;      // k_pbs_generic: resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
     // per-call scratch
     DevBuf<PbsJob> d_pbs;
     DevBuf<KsJob> d_ks;
@@ -2554,7 +2565,8 @@ static hipError_t launch_pbs_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t co
     return launch_pbs_f<FpH, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big);
 }
 
-static bool pbs_supported(const helm_hip_params &P)
+// the shapes the tuned builds cover (kernel class 0)
+static bool pbs_tuned(const helm_hip_params &P)
 {
     if (P.N == 512 && P.k == 2 && P.pbs_l == 3) return true;
     if (P.N == 512 && P.k == 1 && P.pbs_l == 3) return true;
@@ -2564,16 +2576,57 @@ static bool pbs_supported(const helm_hip_params &P)
     return false;
 }
 
+// the shapes k_pbs_generic takes (a superset of the tuned ones): its LDS budget is (k+1) N <= 8192 (helm_pbs_generic.inc)
+static bool pbs_admitted(const helm_hip_params &P)
+{
+    return (P.N == 256 || P.N == 512 || P.N == 1024 || P.N == 2048) && P.k >= 1 && (int64_t)(P.k + 1) * P.N <= 8192 &&
+           P.pbs_l >= 1;
+}
+
+template <int LOGN>
+static hipError_t launch_pbs_generic_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                                       const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+{
+    // (the dynamic LDS attribute is set by helm_hip_ctx_create, at the largest layout of this N)
+    static std::atomic<bool> told[64];
+    auto kern = k_pbs_generic<LOGN>;
+    if (!told[ctx->device & 63]) {
+        told[ctx->device & 63] = true;
+        if (getenv("HELM_HIP_VERBOSE")) {
+            hipFuncAttributes fa{};
+            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
+            fprintf(stderr, "[helm_hip] k_pbs_generic N=%d D=%d: LDS %zu B, regs %d, scratch %zu B, max %d workgroups/CU\n", 1 << LOGN, ctx->gen_d,
+                    ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(GEN_THREADS), ctx->gen_lds, ctx->stream, jobs, wires, raw, tvs, ctx->bsk,
+                       ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n, ctx->P.k, ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d);
+    return hipGetLastError();
+}
+
+static hipError_t launch_pbs_generic(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                                     const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+{
+    switch (ctx->P.N) {
+    case 256: return launch_pbs_generic_t<8>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 512: return launch_pbs_generic_t<9>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 1024: return launch_pbs_generic_t<10>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 2048: return launch_pbs_generic_t<11>(ctx, jobs, count, wires, raw, tvs, out_big);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 static hipError_t launch_pbs(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                              const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     const helm_hip_params &P = ctx->P;
+    if (ctx->gen_path) return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 512 && P.k == 2 && P.pbs_l == 3) return launch_pbs_t<9, 2, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 512 && P.k == 1 && P.pbs_l == 3) return launch_pbs_t<9, 1, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 512 && P.k == 1 && P.pbs_l == 2) return launch_pbs_t<9, 1, 2>(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 1024 && P.k == 1 && P.pbs_l == 3) return launch_pbs_t<10, 1, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 1024 && P.k == 1 && P.pbs_l == 2) return launch_pbs_t<10, 1, 2>(ctx, jobs, count, wires, raw, tvs, out_big);
-    return hipErrorInvalidValue;
+    return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
 }
 
 static hipError_t launch_ks(helm_hip_ctx *ctx, const KsJob *jobs, int64_t count, const uint32_t *big, uint32_t *out)
@@ -2720,9 +2773,10 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
     if (P.torus_bits != 32) return fail(HELM_ERR_INVALID, "only torus_bits = 32 is implemented");
     if (P.pbs_order != 0) return fail(HELM_ERR_INVALID, "only pbs_order = 0 (bootstrap then keyswitch)");
     if (P.grouping_factor != 1) return fail(HELM_ERR_INVALID, "multi-bit PBS (grouping_factor > 1) not implemented");
-    if (!pbs_supported(P))
-        return fail(HELM_ERR_INVALID, "unsupported (N,k,pbs_l): built variants are (512,2,3) (512,1,3) (512,1,2) "
-                                      "(1024,1,3) (1024,1,2)");
+    if (!pbs_admitted(P))
+        return fail(HELM_ERR_INVALID, "unsupported (N,k,pbs_l): N must be 256, 512, 1024 or 2048, k >= 1 with (k+1) N <= 8192, "
+                                      "pbs_l >= 1 (tuned builds: (512,2,3) (512,1,3) (512,1,2) (1024,1,3) (1024,1,2); "
+                                      "every other shape runs the generic kernel)");
     if (P.n < 1 || P.n > 1024) return fail(HELM_ERR_INVALID, "n must be in [1,1024]");
     if (P.pbs_logB < 1 || P.pbs_logB * P.pbs_l > 31) return fail(HELM_ERR_INVALID, "bad PBS decomposition");
     if (P.ks_logB < 1 || P.ks_logB > 7 || P.ks_logB * P.ks_l > 32 ||
@@ -2751,9 +2805,9 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
         if (const char *v = getenv("HELM_HIP_PBS_VARIANT")) {
             ctx->pbs_variant = atoi(v);
             const int pv = ctx->pbs_variant;
-            if (!(pv == 0 || pv == 4 || pv == 5 || pv == 6 || pv == 7 || pv == 9 || (pv == 8 && P.N == 1024)))
+            if (!(pv == 0 || pv == 4 || pv == 5 || pv == 6 || pv == 7 || pv == 9 || pv == 10 || (pv == 8 && P.N == 1024)))
                 return fail(HELM_ERR_INVALID, std::string("HELM_HIP_PBS_VARIANT=") + v + ": builds are 4 wide, 5 lockstep, 6 / 7 duo in step / "
-                                              "staggered, 9 trio (1 latency, 2 balanced, 3 throughput, 8 sym were retired in round 6)");
+                                              "staggered, 9 trio, 10 generic (1 latency, 2 balanced, 3 throughput, 8 sym were retired in round 6)");
         }
         if (const char *v = getenv("HELM_HIP_DUO")) ctx->duo_build = atoi(v) >= 0 && atoi(v) <= 2 ? atoi(v) : 2;
         if (const char *v = getenv("HELM_HIP_DUO1024")) ctx->duo1024 = atoi(v) >= 1 && atoi(v) <= 3 ? atoi(v) : 0;
@@ -2772,6 +2826,49 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
         const int N = P.N;
         ctx->field = (N == 512 && bound * 1.002 < FpG::P / 2 && P.pbs_logB <= 12) ? 49 : 51;
         if (const char *v = getenv("HELM_HIP_FIELD")) if (atoi(v) == 51) ctx->field = 51;
+        // the generic class (a shape no tuned build covers, or every launch under HELM_HIP_PBS_VARIANT=10): always FpH, its
+        // own key layout, one workgroup of GEN_THREADS per bootstrap; the quantum follows its occupancy
+        ctx->generic = !pbs_tuned(P);
+        if (ctx->generic && ctx->pbs_variant != 0 && ctx->pbs_variant != 10)
+            return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(ctx->pbs_variant) +
+                                              " names a tuned build, which this shape (N,k,pbs_l) has not: it runs the generic kernel "
+                                              "(variant 10, or leave the variable unset)");
+        ctx->gen_path = ctx->generic || ctx->pbs_variant == 10;
+        if (ctx->gen_path) {
+            ctx->field = 51;
+            const void *kern = ctx->logN == 8    ? reinterpret_cast<const void *>(k_pbs_generic<8>)
+                               : ctx->logN == 9  ? reinterpret_cast<const void *>(k_pbs_generic<9>)
+                               : ctx->logN == 10 ? reinterpret_cast<const void *>(k_pbs_generic<10>)
+                                                 : reinterpret_cast<const void *>(k_pbs_generic<11>);
+            // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a
+            // context created later with a smaller one cannot lower it under an earlier context's launches
+            const int K1max = 8192 / N;
+            const size_t lds_max = GenLds(N, K1max, gen_batch(N, K1max - 1, 31), 1024).bytes;
+            HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            // digit polynomials per batch: the most (<= gen_batch) that cost no resident workgroup against one per batch - a
+            // launch of more bootstraps than fit at once runs a partial second round (boolean_default's shape: D = 4 leaves
+            // 3 workgroups per CU, 2 leave 4, 1 leaves 5 - 51.9 against 44.7 ms for 1,024 bootstraps)
+            auto occupancy = [&](int d, int &nb) -> int {
+                nb = 0;
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, GEN_THREADS, GenLds(N, P.k + 1, d, P.n).bytes));
+                return 0;
+            };
+            int nb1 = 0;
+            if (int rc = occupancy(1, nb1)) return rc;
+            if (nb1 < 1) return fail(HELM_ERR_STATE, "k_pbs_generic: no workgroup of " + std::to_string(GenLds(N, P.k + 1, 1, P.n).bytes) +
+                                                         " B LDS fits a CU");
+            ctx->gen_d = 1;
+            for (int d = gen_batch(N, P.k, P.pbs_l); d > 1; d--) {
+                int nb = 0;
+                if (int rc = occupancy(d, nb)) return rc;
+                if (nb == nb1) {
+                    ctx->gen_d = d;
+                    break;
+                }
+            }
+            ctx->gen_lds = GenLds(N, P.k + 1, ctx->gen_d, P.n).bytes;
+            ctx->gen_per_cu = nb1;
+        }
         if (int rc = setup_field_tables(ctx)) return rc;
         std::vector<uint32_t> tv(N, PT_TRUE);
         HIP_TRY(hipMalloc(&ctx->tv_bool, sizeof(uint32_t) * N));
@@ -2867,7 +2964,14 @@ int helm_hip_sync(helm_hip_ctx *ctx)
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null ctx");
+    if (ctx->gen_path) return (int64_t)ctx->gen_per_cu * ctx->n_cus; // k_pbs_generic: one bootstrap per workgroup, all resident
     return 4 * (int64_t)ctx->n_cus; // PbsCfg::NB bootstraps per workgroup, one workgroup per CU
+}
+
+int helm_hip_kernel_class(const helm_hip_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return ctx->generic ? 1 : 0;
 }
 
 int helm_hip_field_bits(const helm_hip_ctx *ctx)
@@ -2912,12 +3016,23 @@ int helm_hip_bound_violations(helm_hip_ctx *ctx, uint32_t counts[8], int reset, 
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    if (ctx->gen_path) return 0; // k_pbs_generic: plain radix-2 stages throughout
     return 2; // both fields of this engine (5072^4 + 1, 6432^4 + 1) have short eighth roots
 }
 
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4])
 {
     if (!ctx || !cost) return fail(HELM_ERR_INVALID, "null argument");
+    if (ctx->gen_path) {
+        // k_pbs_generic, from its occupancy W (workgroups per CU, one wave of each on every SIMD): a launch of at most q/4 of
+        // the quantum puts w = ceil(q W / 4) workgroups on a CU.  One wave per SIMD leaves the step's latencies (LDS round
+        // trips, key loads, barriers) exposed; from two on, the SIMD's time grows with its waves.  Model: time ~ max(1, w / 2),
+        // relative to the full round - non-decreasing, cost[3] = 1 (not measured; DESIGN.md "The generic kernel class")
+        const int W = ctx->gen_per_cu;
+        const double full = std::max(1.0, W / 2.0);
+        for (int q = 1; q <= 4; q++) cost[q - 1] = std::max(1.0, ((q * W + 3) / 4) / 2.0) / full;
+        return 0;
+    }
     // launch_pbs_f's dispatch, measured (profiles/r04/microbench.jsonl and the other boxes of the round; boolean_default:
     // 3.2 - 3.3 / 5.0 - 5.3 / 6.6 - 6.7 / 7.6 - 8.0 ms for <= 256 / 512 / 768 / 1,024 bootstraps - wide, duo, trio and a full
     // lockstep round, final build of round 4; without k_pbs_duo (A/B switch) a launch of <= 512 is a lockstep round, without
@@ -2949,7 +3064,7 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
     HIP_TRY(hipSetDevice(ctx->device));
-    if (P.N == 1024) {
+    if (P.N == 1024 && !ctx->gen_path) {
         // Round 5: which field serves THIS key.  The exact sum an external product can reach is at most B/2 x the l1-norm of
         // the key coefficients that meet in one output coefficient: the (k+1) l polynomials of one key column of one step (a
         // negacyclic product's output coefficient is a signed sum over ALL coefficients of each factor).  Both groupings of
@@ -2996,7 +3111,17 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
     HIP_TRY(d_std.alloc(n_words));
     if (!ctx->bsk) HIP_TRY(hipMalloc(&ctx->bsk, n_words * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(d_std.p, bsk_std, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (P.N == 512 && ctx->field == 49)
+    if (ctx->gen_path) {
+        // the generic class's layout: [i][r][c][lev][N], bit-reversed transform order (k_bsk_convert_generic)
+#define GEN_CONVERT(LN)                                                                                                     \
+    hipLaunchKernelGGL(k_bsk_convert_generic<LN>, dim3((unsigned)polys), dim3(GEN_THREADS), 0, ctx->stream, d_std.p, ctx->bsk, \
+                       ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l)
+        if (P.N == 256) GEN_CONVERT(8);
+        else if (P.N == 512) GEN_CONVERT(9);
+        else if (P.N == 1024) GEN_CONVERT(10);
+        else GEN_CONVERT(11);
+#undef GEN_CONVERT
+    } else if (P.N == 512 && ctx->field == 49)
         hipLaunchKernelGGL((k_bsk_convert<FpG, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p, ctx->bsk,
                            ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
     else if (P.N == 1024 && ctx->field == 50)
@@ -3796,7 +3921,16 @@ int helm_hip_ntt_roundtrip(helm_hip_ctx *ctx, const uint32_t *poly_in, uint32_t 
     HIP_TRY(d_in.alloc((size_t)count * N));
     HIP_TRY(d_out.alloc((size_t)count * N));
     HIP_TRY(hipMemcpyAsync(d_in.p, poly_in, (size_t)count * N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (N == 512 && ctx->field == 49)
+    if (ctx->gen_path) {
+#define GEN_ROUNDTRIP(LN)                                                                                                     \
+    hipLaunchKernelGGL(k_ntt_roundtrip_generic<LN>, dim3((unsigned)count), dim3(GEN_THREADS), 0, ctx->stream, d_in.p, d_out.p, \
+                       ctx->tw_fwd, ctx->tw_inv, ctx->n_inv)
+        if (N == 256) GEN_ROUNDTRIP(8);
+        else if (N == 512) GEN_ROUNDTRIP(9);
+        else if (N == 1024) GEN_ROUNDTRIP(10);
+        else GEN_ROUNDTRIP(11);
+#undef GEN_ROUNDTRIP
+    } else if (N == 512 && ctx->field == 49)
         hipLaunchKernelGGL((k_ntt_roundtrip<FpG, 9>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p, d_out.p,
                            ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
     else if (N == 1024 && ctx->field == 50)

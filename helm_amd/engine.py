@@ -131,11 +131,20 @@ class ServerKey:
         hip_check(hip.helm_hip_sync(self._h))
 
     def launch_quantum(self):
-        """Bootstraps of one full round of the lockstep build (4 per compute unit)."""
+        """Bootstraps of one full round: 4 per compute unit on the lockstep build, the generic kernel's resident workgroups
+        per compute unit x compute units when that kernel runs the context's launches."""
         q = int(hip.helm_hip_launch_quantum(self._h))
         if q <= 0:
             hip_check(q or -1)
         return q
+
+    def kernel_class(self):
+        """"tuned" when the parameter shape (N, k, pbs_l) has tuned blind-rotate builds, "generic" when the generic kernel
+        (k and pbs_l at run time) serves it (helm_hip_kernel_class; HELM_HIP_PBS_VARIANT=10 does not change it)."""
+        v = int(hip.helm_hip_kernel_class(self._h))
+        if v < 0:
+            hip_check(v)
+        return "generic" if v == 1 else "tuned"
 
     def wires(self, n_wires):
         return DeviceWires(self, n_wires)

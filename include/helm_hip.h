@@ -72,7 +72,7 @@ typedef struct {
     int32_t torus_bits;      /* 32 (64 reserved for LUT / arithmetic mode)   */
     int32_t n;               /* small LWE dimension                          */
     int32_t k;               /* GLWE dimension                               */
-    int32_t N;               /* polynomial size: 512 or 1024                 */
+    int32_t N;               /* polynomial size: 256, 512, 1024 or 2048      */
     int32_t pbs_l;           /* bootstrap decomposition level count          */
     int32_t pbs_logB;        /* bootstrap decomposition base log             */
     int32_t ks_l;            /* keyswitch decomposition level count          */
@@ -120,15 +120,24 @@ int helm_hip_set_stream(helm_hip_ctx *ctx, void *hip_stream);
 int helm_hip_sync(helm_hip_ctx *ctx);
 /* Bootstraps of one full round of the dominant (lockstep) build on this device: 4 per compute unit.
  * A launch of a whole number of rounds leaves no partial round behind; the host's launch packing
- * (helm_host_pack_levels) sizes launches with it.  Negative on error. */
+ * (helm_host_pack_levels) sizes launches with it.  When the generic kernel runs the context's launches (kernel class 1,
+ * or HELM_HIP_PBS_VARIANT=10): its resident workgroups per compute unit (one bootstrap each, from the HIP occupancy
+ * calculator at the context's LDS size) x compute units.  Negative on error. */
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx);
+
+/* Which blind-rotate kernel class the context's shape (N, k, pbs_l) runs on: 0 = the tuned builds (k_pbs, k_pbs_wide,
+ * k_pbs_duo, k_pbs_trio, k_pbs_tri10: (512,2,3) (512,1,3) (512,1,2) (1024,1,3) (1024,1,2)), 1 = the generic kernel
+ * (k_pbs_generic: k and pbs_l at run time, N = 256 ... 2048, (k+1) N <= 8192, always the 51-bit field).  It reflects the
+ * shape only: HELM_HIP_PBS_VARIANT=10, which runs a tuned shape on the generic kernel, does not change it (on a class-1
+ * shape helm_hip_ctx_create refuses the variants that name tuned builds).  Negative on error. */
+int helm_hip_kernel_class(const helm_hip_ctx *ctx);
 
 /* What a launch of at most 1/4, 2/4, 3/4 and 4/4 of helm_hip_launch_quantum() bootstraps costs on this context, relative to
  * a full round (cost[3] = 1): the engine runs a different build of the blind-rotate kernel per width (k_pbs_wide: one
  * bootstrap per CU on four SIMDs, k_pbs_duo: two per CU on two SIMDs each, k_pbs_trio: three per CU on four waves each, full
  * lockstep rounds).  Measured on
  * MI355X (profiles/r04/microbench.jsonl); the host's launch packing (helm_host_pack_levels_costed) sizes launches that are
- * narrower than a round with it. */
+ * narrower than a round with it.  On the generic kernel: a model from its occupancy (non-decreasing, cost[3] = 1). */
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4]);
 
 /* The prime field the blind-rotate kernels of this context compute in, as its size class: 49 = the lazy field p = 5072^4 + 1
@@ -143,7 +152,8 @@ int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4]);
 int helm_hip_field_bits(const helm_hip_ctx *ctx);
 /* Number of leading stages of every forward transform on decomposition digits that run as plain multiplications by short
  * roots of unity (2 in both fields of this engine: one radix-4 butterfly of 10 operations per four values instead of two
- * stages of modular butterflies).  For benchmarks that count the operations
+ * stages of modular butterflies); 0 when the generic kernel runs the context's launches (kernel class 1, or
+ * HELM_HIP_PBS_VARIANT=10: plain radix-2 stages).  For benchmarks that count the operations
  * the kernels execute; results do not depend on it. */
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx);
 

@@ -101,6 +101,7 @@ extern "C" {
     pub fn helm_hip_set_stream(ctx: *mut helm_hip_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn helm_hip_sync(ctx: *mut helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_quantum(ctx: *const helm_hip_ctx) -> i64;
+    pub fn helm_hip_kernel_class(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_costs(ctx: *const helm_hip_ctx, cost: *mut f64) -> c_int;
     pub fn helm_hip_short_root_stages(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_field_bits(ctx: *const helm_hip_ctx) -> c_int;
