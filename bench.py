@@ -6,7 +6,15 @@ input blocks, inputs already encrypted and resident in HBM.  The level schedule 
 (helm_amd/csrc/host/level_pack.cpp): the blocks share no wires, so launches hold whole lockstep rounds and only
 the drain at the end of a pass is partial.
 
-    python3 bench.py --gpus N --steps K --warmup W
+    python3 bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing more: set-up (keys, netlist, packed program, encrypted inputs), W
+warm-up steps, the K timed steps, the decryption check of what they computed (every block == software AES: a wrong result
+ends the run with an error instead of a number), --dump-outputs if asked, the line.  Its kernel times and roofline take no
+run of their own: the engine's events and the power sampler over the timed steps, the committed counter profiles.
+`--full` adds everything that does take runs of its own after the headline: at N = 1 `single_block`, `configs`,
+`cpu_baseline` and `other_modes`; at N > 1 the `solo` run and the two scalings that are not the headline (the --no-*
+options leave parts of it out).
 
 With N > 1 and no RANK in the environment this process is only a launcher: it has not touched the GPU (it imports
 nothing beyond the standard library), starts `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a
@@ -25,8 +33,8 @@ One line, every result named:
   weak                       independent blocks: every GPU evaluates its own `--blocks` blocks, no data-path collective
   rccl_ranks                 what the library's own RCCL communicator reports (ncclCommCount / ncclCommUserRank), the RCCL
                              version, and what carried the control plane (barrier, maximum over the ranks, the unique id)
-`--scaling strong` / `--scaling weak` make one of the other two the headline instead; all three are always in the line
-under their own names (the runs that are not the headline with `--side-steps` timed steps).
+`--scaling strong` / `--scaling weak` make one of the other two the headline instead; with `--full` all three are in the
+line under their own names (the runs that are not the headline with `--side-steps` timed steps).
 
 A worker that fails - an exception, a wrong decryption, a collective that does not come back within
 `--leg-timeout` seconds - ends with a non-zero exit code and its error in the line; nothing is retried.
@@ -71,10 +79,14 @@ def parse_args(argv=None):
                     help="which N > 1 run is the headline `value` (default: the per-level shard at fixed work per GPU)")
     ap.add_argument("--params", default="boolean_default")
     ap.add_argument("--no-pack", action="store_true", help="level-synchronous launches (the round-1 schedule)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-modes", action="store_true", help="skip the LUT-mode / arithmetic-mode side measurements")
-    ap.add_argument("--no-configs", action="store_true", help="skip the per-configuration wall-clock lines (BASELINE.json configs 1-3)")
-    ap.add_argument("--no-side-legs", action="store_true", help="N > 1: only the headline run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: N = 1: single_block, the BASELINE.json "
+                         "configurations, the CPU baseline and the other modes; N > 1: the solo run and the two other scalings "
+                         "(the --no-* options below leave parts of it out).  Without it a run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-modes", action="store_true", help="--full: skip the LUT-mode / arithmetic-mode side measurements")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the per-configuration wall-clock lines (BASELINE.json configs 1-3)")
+    ap.add_argument("--no-side-legs", action="store_true", help="--full, N > 1: only the headline run")
     ap.add_argument("--overlap", action="store_true",
                     help="sharded runs: the library's overlapped exchange (helm_hip_program_run_sharded_comm, overlap = 1): a launch's "
                          "all-gather + scatter on the engine's exchange stream while the launches that do not need its outputs run; "
@@ -86,7 +98,7 @@ def parse_args(argv=None):
     ap.add_argument("--force-comm", action="store_true",
                     help="N = 1: run the headline through the sharded path anyway - a world-size-1 RCCL communicator inside the library, "
                          "every launch stage -> ncclAllGather -> scatter (what the exchange machinery itself costs; rccl_ranks is filled)")
-    ap.add_argument("--side-steps", type=int, default=3, help="N > 1: timed steps of the runs that are not the headline")
+    ap.add_argument("--side-steps", type=int, default=3, help="--full, N > 1: timed steps of the runs that are not the headline")
     ap.add_argument("--wall-budget", type=float, default=450.0,
                     help="N > 1: seconds the whole run should stay under; the planned wall time of every run is printed (stderr, "
                          "and `planned_wall_s` in the line) before it starts, and the runs that are NOT the headline are cut to one "
@@ -837,7 +849,7 @@ def fill_result(bench, result):
 
     # ---- N > 1: which other runs follow, decided the same way on every rank from figures every rank holds ----
     legs, dropped = [], []
-    if world > 1 and not args.no_side_legs:
+    if world > 1 and args.full and not args.no_side_legs:
         used, setup_s = guarded(bench, result, "plan of the remaining runs",
                                 lambda: bench.agree_max([time.time() - bench.t_start, head["setup_s"]]))
         gpu_rate = head["value"] / world / (0.76 if head_kind == "strong" else 1.0)
@@ -1072,7 +1084,7 @@ def fill_result(bench, result):
 
     # ---- wall-clock of ONE AES-128 evaluation (latency; levels are 80-256 gates wide, so the
     #      GPU is far from full: this is the n-step blind-rotation chain, 207 levels deep) ------
-    if world == 1:
+    if world == 1 and args.full:
         prog1, launches1, _, _ = make_program(bench.sk, bench.circuit, bench.wire_names, 1, quantum)
         prog1.run(head["wires"])
         bench.sync_all()
@@ -1118,7 +1130,7 @@ def fill_result(bench, result):
         checkpoint(result)
 
     # ---- every BASELINE.json configuration as a wall-clock line (each one circuit, outside the timed region) ----
-    if world == 1 and not args.no_configs:
+    if world == 1 and args.full and not args.no_configs:
         try:
             result["configs"] = baseline_configs(bench, result)
         except Exception as e:  # the headline line must survive a failure here
@@ -1126,14 +1138,14 @@ def fill_result(bench, result):
         checkpoint(result)
 
     # ---- CPU baseline: the oracle (a port, not tfhe-rs) on this box's host cores --------
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, bench.ck, bench.circuit, bench.wire_names, bench.index, bench.nw,
                                               head["wires"], head["keys_pt"], gpu_value=head["value"],
                                               gpu_single_block=result["single_block"]["gate_bootstraps_per_s"])
         checkpoint(result)
     # ---- the other two modes of the reference, same GPU, outside the timed region: 3-input LUT
     #      gates (BASELINE config 3's primitive) and the chi-squared u32 netlist (config 5) ------
-    if world == 1 and not args.no_other_modes:
+    if world == 1 and args.full and not args.no_other_modes:
         try:
             result["other_modes"] = other_modes(bench.local_rank)
         except Exception as e:  # the headline line must survive a failure here

@@ -66,7 +66,7 @@ def test_hung_worker_group_is_stopped_and_reported():
 def test_rehearsal_two_ranks_on_one_gpu_reports_every_named_result():
     """HELM_BENCH_REHEARSE=1: both ranks on cuda:0, the library's communicator over a host transport - the whole N > 1 path of bench.py, launcher
     included: sharded_weak (the headline: the per-level shard at fixed work per GPU), strong and weak each under its own name, rc 0."""
-    rc, lines, err = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4", "--side-steps", "1"],
+    rc, lines, err = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4", "--side-steps", "1", "--full"],
                                {"HELM_BENCH_REHEARSE": "1"}, timeout=1100)
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
@@ -163,7 +163,8 @@ def test_rehearsal_with_rank_threads_reports_every_named_result():
     """HELM_BENCH_REHEARSE=threads: the ranks are threads of ONE process (the box allows six GPU processes, the scaling run
     has eight ranks - profiles/r05/rehearse_n8.json is this command at --gpus 8): the library's in-process communicator
     (helm_comm_create_in_process) under the real run's programs, sharded passes, three named runs and decryption checks."""
-    rc, lines, err = run_bench(["--gpus", "3", "--steps", "1", "--warmup", "0", "--blocks", "3", "--side-steps", "1", "--scaling", "strong"],
+    rc, lines, err = run_bench(["--gpus", "3", "--steps", "1", "--warmup", "0", "--blocks", "3", "--side-steps", "1", "--scaling", "strong",
+                                "--full"],
                                {"HELM_BENCH_REHEARSE": "threads"}, timeout=900)
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines

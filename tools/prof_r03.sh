@@ -4,8 +4,8 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_r03; mkdir -p $O
-BENCH="--steps 1 --warmup 1 --no-cpu-baseline --no-other-modes"
-SMALL="--steps 1 --warmup 0 --blocks 4 --no-cpu-baseline --no-other-modes"
+BENCH="--full --steps 1 --warmup 1 --no-cpu-baseline --no-other-modes"
+SMALL="--full --steps 1 --warmup 0 --blocks 4 --no-cpu-baseline --no-other-modes"
 echo "== 1 kernel-trace stats, gates mode (bench.py $BENCH)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o bench -- python3 bench.py $BENCH > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 echo "== 2 kernel-trace stats, LUT mode (1,024 three-input LUTs x 3; classical and multi-bit sets; 2,048 two-input LUTs x 3 on the binary's set)"

@@ -4,10 +4,10 @@
 cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out/prof_r04; mkdir -p $O
-BENCH="--steps 1 --warmup 1 --no-cpu-baseline --no-other-modes"
+BENCH="--full --steps 1 --warmup 1 --no-cpu-baseline --no-other-modes"
 SMALL="--steps 1 --warmup 0 --blocks 4 --no-cpu-baseline --no-other-modes"
-echo "== 0 the bench line itself, default arguments (same box as everything below)"
-timeout -k 10 600 python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+echo "== 0 the bench line itself, everything it measures: --full (same box as everything below)"
+timeout -k 10 600 python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
 echo "== 1 kernel-trace stats, gates mode (bench.py $BENCH)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o bench -- python3 bench.py $BENCH > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 echo "== 2 kernel-trace stats of one launch per width: 256 (wide), 512 (duo), 768 (trio), 1,024 (lockstep), 5 launches each"
@@ -27,8 +27,8 @@ timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE 
 timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/pmcTW -o w -- python3 bench.py $B > $O/pmcTW.log 2>&1 &&
 python3 tools/pmc_traffic.py $O/pmcTF $O/pmcTW $O/pmc_traffic.json
 echo "== 5 the exchange machinery on one GPU: bench.py --force-comm (world-size-1 RCCL communicator inside the library)"
-timeout -k 10 400 python3 bench.py --force-comm --no-cpu-baseline --no-other-modes > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fc -o fc -- python3 bench.py --force-comm --steps 1 --warmup 0 --blocks 8 --no-cpu-baseline --no-other-modes > $O/fc.log 2>&1 || tail -5 $O/fc.log
+timeout -k 10 400 python3 bench.py --full --force-comm --no-cpu-baseline --no-other-modes > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fc -o fc -- python3 bench.py --full --force-comm --steps 1 --warmup 0 --blocks 8 --no-cpu-baseline --no-other-modes > $O/fc.log 2>&1 || tail -5 $O/fc.log
 echo "== 6 the 8(d) micro-benchmark table"
 rm -f $O/microbench.jsonl
 timeout -k 10 900 python3 tools/microbench_gates.py --out $O/microbench.jsonl > $O/microbench.log 2>&1 || tail -5 $O/microbench.log

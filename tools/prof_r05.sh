@@ -6,10 +6,10 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out/prof_r05; mkdir -p $O
 STEPS="${*:-0 1 2 3 4 5 6 7}"
 has() { case " $STEPS " in *" $1 "*) return 0;; esac; return 1; }
-BENCH="--steps 1 --warmup 1 --no-cpu-baseline --no-other-modes --no-configs"
+BENCH="--full --steps 1 --warmup 1 --no-cpu-baseline --no-other-modes --no-configs"
 if has 0; then
-echo "== 0 the bench line itself, default arguments (same box as everything below)"
-timeout -k 10 600 python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+echo "== 0 the bench line itself, everything it measures: --full (same box as everything below)"
+timeout -k 10 600 python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
 fi
 if has 1; then
 echo "== 1 kernel-trace stats, gates mode (bench.py $BENCH)"
@@ -45,8 +45,8 @@ python3 tools/pmc_traffic.py $O/pmcTF $O/pmcTW $O/pmc_traffic.json
 fi
 if has 5; then
 echo "== 5 the exchange machinery on one GPU: bench.py --force-comm (world-size-1 RCCL communicator inside the library), in order and overlapped"
-timeout -k 10 400 python3 bench.py --force-comm --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
-timeout -k 10 400 python3 bench.py --force-comm --overlap --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm_overlap.json 2> $O/bench_fco.err || tail -5 $O/bench_fco.err
+timeout -k 10 400 python3 bench.py --full --force-comm --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
+timeout -k 10 400 python3 bench.py --full --force-comm --overlap --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm_overlap.json 2> $O/bench_fco.err || tail -5 $O/bench_fco.err
 fi
 if has 6; then
 echo "== 6 the 8(d) micro-benchmark table"

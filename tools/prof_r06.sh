@@ -6,10 +6,10 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out/prof_r06; mkdir -p $O
 STEPS="${*:-0 1 2 3 4 5}"
 has() { case " $STEPS " in *" $1 "*) return 0;; esac; return 1; }
-BENCH="--steps 1 --warmup 1 --no-cpu-baseline --no-other-modes --no-configs"
+BENCH="--full --steps 1 --warmup 1 --no-cpu-baseline --no-other-modes --no-configs"
 if has 0; then
-echo "== 0 the bench line itself, default arguments (same box as everything below)"
-timeout -k 10 600 python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+echo "== 0 the bench line itself, everything it measures: --full (same box as everything below)"
+timeout -k 10 600 python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
 fi
 if has 1; then
 echo "== 1 kernel-trace stats, gates mode (bench.py $BENCH)"
@@ -27,12 +27,12 @@ cp $(find $O/lut_m1c1_49 -name "*kernel_stats.csv" | head -1) $O/lut_m1c1_field4
 fi
 if has 3; then
 echo "== 3 world 8 as eight rank threads on this one GPU (HELM_BENCH_REHEARSE=threads): the N > 1 record with its plan, the N = 1 job inside the run, every row's baseline"
-HELM_BENCH_REHEARSE=threads timeout -k 10 900 python3 bench.py --gpus 8 --blocks 8 --steps 1 --warmup 1 > $O/rehearse_n8.json 2> $O/rehearse_n8.err || tail -5 $O/rehearse_n8.err
+HELM_BENCH_REHEARSE=threads timeout -k 10 900 python3 bench.py --full --gpus 8 --blocks 8 --steps 1 --warmup 1 > $O/rehearse_n8.json 2> $O/rehearse_n8.err || tail -5 $O/rehearse_n8.err
 grep "^\[bench\]" $O/rehearse_n8.err
 fi
 if has 4; then
 echo "== 4 the exchange machinery on one GPU: bench.py --force-comm (world-size-1 RCCL communicator inside the library)"
-timeout -k 10 400 python3 bench.py --force-comm --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
+timeout -k 10 400 python3 bench.py --full --force-comm --no-cpu-baseline --no-other-modes --no-configs > $O/bench_n1_forcecomm.json 2> $O/bench_fc.err || tail -5 $O/bench_fc.err
 fi
 if has 5; then
 echo "== 5 the driver's arguments"
