@@ -220,6 +220,8 @@ SI_AUDIT_FN = C.CFUNCTYPE(C.c_int, vp, C.POINTER(SiAuditRecord))  # helm_si_audi
 # every symbol include/helm_shortint.h declares
 SI_API = {
     "helm_si_ctx_create": (C.c_int, [C.c_int, C.POINTER(SiParams), C.POINTER(vp)]),
+    "helm_si_ctx_create_ex": (C.c_int, [C.c_int, C.POINTER(SiParams), C.c_int, C.POINTER(vp)]),
+    "helm_si_kernel_class": (C.c_int, [vp]),
     "helm_si_ctx_destroy": (C.c_int, [vp]),
     "helm_si_ctx_fork": (C.c_int, [vp, C.POINTER(vp)]),
     "helm_si_get_params": (C.c_int, [vp, C.POINTER(SiParams)]),

@@ -1551,6 +1551,14 @@ struct helm_si_ctx {
     uint16_t *expo = nullptr;    // multi-bit: exponent of the evaluation point per spectrum position [2 halves][N/2]
     double *psi_pow = nullptr;   // multi-bit: psi^t, t < 2N, per field
     bool use_split = false;
+    // helm_si_ctx_create_ex: k_pbs64_generic runs every bootstrap launch (a shape no tuned build covers, admitted under
+    // HELM_SI_CREATE_ALLOW_GENERIC, or any shape under HELM_SI_CREATE_FORCE_GENERIC): always the 49-bit pair, its own key
+    // layout (k_bsk_convert64_generic), no split key
+    bool gen = false;
+    int gen_d = 1;                        // digit polynomials per batch (gen64_batch)
+    size_t gen_lds = 0;                   // LDS bytes per workgroup (Gen64Lds)
+    int gen_per_cu = 1;                   // resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+    double *twi[2] = {nullptr, nullptr};  // bit-reversed powers of psi^-1 per field (the generic kernel's inverse transforms)
     uint64_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: eight byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0, ks_mfma = 1; // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
@@ -1647,6 +1655,15 @@ bool si_supported(const helm_si_params &P)
     if (P.k != 1) return false;
     if (!(P.N == 512 || P.N == 1024 || P.N == 2048)) return false;
     return P.pbs_l == 1 || P.pbs_l == 2;
+}
+
+// the shapes k_pbs64_generic takes (helm_si_ctx_create_ex with a HELM_SI_CREATE_* flag): N stops at 2048 because FpG2 has
+// 2-adicity 2^12 (no 2N-th root of unity beyond), (k+1) N <= 4096 is its LDS budget (helm_pbs64_generic.inc), and it has no
+// multi-bit form
+bool si_generic_domain(const helm_si_params &P)
+{
+    return (P.N == 256 || P.N == 512 || P.N == 1024 || P.N == 2048) && P.k >= 1 && (int64_t)(P.k + 1) * P.N <= 4096 &&
+           P.pbs_l >= 1 && P.grouping_factor <= 1;
 }
 
 template <typename C>
@@ -1769,9 +1786,49 @@ hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_
 #if HELM_SI_TU == 0 // ==== everything below: the main unit only ===============================================
 namespace {
 
+// k_pbs64_generic: k, pbs_l and pbs_logB at run time (helm_si_ctx_create_ex)
+#include "helm_pbs64_generic.inc"
+
+template <int LOGN>
+hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                                  const uint64_t *luts, uint64_t *out, int *per_cu)
+{
+    // (the dynamic LDS attribute is set by helm_si_ctx_create_ex, at the largest layout of this N)
+    if (per_cu) {
+        *per_cu = ctx->gen_per_cu;
+        return hipSuccess;
+    }
+    const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx; // a lane reads the key and tables through its primary
+    hipLaunchKernelGGL(k_pbs64_generic<LOGN>, dim3((unsigned)count), dim3(G64_THREADS), ctx->gen_lds, ctx->stream, jobs, small,
+                       luts, root->bsk, root->tw[0], root->tw[1], root->twi[0], root->twi[1], out, ctx->P.n, ctx->P.k,
+                       ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d, root->p0inv_mod_p1);
+    return hipGetLastError();
+}
+
+hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                                const uint64_t *luts, uint64_t *out, int *per_cu)
+{
+    switch (ctx->logN) {
+    case 8: return launch_pbs64_generic_t<8>(ctx, jobs, count, small, luts, out, per_cu);
+    case 9: return launch_pbs64_generic_t<9>(ctx, jobs, count, small, luts, out, per_cu);
+    case 10: return launch_pbs64_generic_t<10>(ctx, jobs, count, small, luts, out, per_cu);
+    case 11: return launch_pbs64_generic_t<11>(ctx, jobs, count, small, luts, out, per_cu);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+const void *pbs64_generic_kernel(int logN)
+{
+    return logN == 8    ? reinterpret_cast<const void *>(k_pbs64_generic<8>)
+           : logN == 9  ? reinterpret_cast<const void *>(k_pbs64_generic<9>)
+           : logN == 10 ? reinterpret_cast<const void *>(k_pbs64_generic<10>)
+                        : reinterpret_cast<const void *>(k_pbs64_generic<11>);
+}
+
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                         const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
+    if (ctx->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
     const helm_si_params &P = ctx->P;
 #if HELM_SI_SPLIT_TU
     if (P.k == 3 || P.k == 2 || (ctx->use_split && ctx->group > 1))
@@ -2159,6 +2216,70 @@ int setup_pair_tables(helm_si_ctx *ctx, int pair)
     return 0;
 }
 
+// A context whose launches run k_pbs64_generic: the inverse twiddle tables of the 49-bit pair, the kernel's LDS attribute and
+// occupancy, and the digit batch D.  Refuses the shape cleanly if no workgroup of it fits a CU.
+int setup_generic(helm_si_ctx *ctx)
+{
+#ifdef HELM_CHECK_BOUNDS
+    // The -O0 counting build of k_pbs64_generic faulted on its first launch (a memory-aperture violation; the -O3 build of the
+    // same source is bit-exact against the oracle on every shape tested), and the cause is not found yet:
+    // until it is, this build refuses the generic class before anything is launched.
+    (void)ctx;
+    return fail(HELM_ERR_STATE, "the generic kernel is not available in the bound-checking build (libhelm_hip_check.so): "
+                                "use the regular library for generic contexts");
+#endif
+    const helm_si_params &P = ctx->P;
+    const int N = P.N, logN = ctx->logN;
+    const uint64_t pm[2] = {F0::P_U64, F1::P_U64}, gen[2] = {F0::GEN, F1::GEN};
+    for (int f = 0; f < 2; f++) { // psi as setup_pair_tables chooses it for pair 0
+        const uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
+        const uint64_t psi_inv = powmod_u64(psi, pm[f] - 2, pm[f]);
+        std::vector<double> ti(N);
+        uint64_t b = 1;
+        for (int i = 0; i < N; i++) {
+            ti[bitrev(i, logN)] = centred(b, pm[f]);
+            b = mulmod_u64(b, psi_inv, pm[f]);
+        }
+        if (!ctx->twi[f]) HIP_TRY(hipMalloc(&ctx->twi[f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(ctx->twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    const void *kern = pbs64_generic_kernel(logN);
+    // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a context
+    // created later with a smaller one cannot lower it under an earlier context's launches
+    const int K1max = 4096 / N;
+    const size_t lds_max = Gen64Lds(N, K1max, gen64_batch(N, K1max - 1, 31), 1024).bytes;
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    auto occupancy = [&](int d, int &nb) -> int {
+        nb = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, G64_THREADS, Gen64Lds(N, P.k + 1, d, P.n).bytes));
+        return 0;
+    };
+    int nb1 = 0;
+    if (int rc = occupancy(1, nb1)) return rc;
+    if (nb1 < 1)
+        return fail(HELM_ERR_INVALID, "k_pbs64_generic: no workgroup of " + std::to_string(Gen64Lds(N, P.k + 1, 1, P.n).bytes) +
+                                          " B LDS fits a CU for this shape");
+    // digit polynomials per batch: the most (<= gen64_batch) that cost no resident workgroup against one per batch
+    ctx->gen_d = 1;
+    for (int d = gen64_batch(N, P.k, P.pbs_l); d > 1; d--) {
+        int nb = 0;
+        if (int rc = occupancy(d, nb)) return rc;
+        if (nb == nb1) {
+            ctx->gen_d = d;
+            break;
+        }
+    }
+    ctx->gen_lds = Gen64Lds(N, P.k + 1, ctx->gen_d, P.n).bytes;
+    ctx->gen_per_cu = nb1;
+    ctx->gen = true;
+    if (getenv("HELM_HIP_VERBOSE")) {
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, kern);
+        fprintf(stderr, "[helm_si] k_pbs64_generic N=%d k=%d l=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N,
+                P.k, P.pbs_l, ctx->gen_d, ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
+    }
+    return 0;
+}
 
 } // namespace
 
@@ -2166,11 +2287,30 @@ extern "C" {
 
 int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx **out)
 {
+    return helm_si_ctx_create_ex(device_id, params, 0, out);
+}
+
+int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out)
+{
     if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
     const helm_si_params &P = *params;
-    if (!si_supported(P))
+    if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC))
+        return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
+                                          " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2)");
+    const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
+    if (force && P.grouping_factor > 1)
+        return fail(HELM_ERR_INVALID, "HELM_SI_CREATE_FORCE_GENERIC: the generic kernel has no multi-bit form (grouping_factor > 1)");
+    const bool tuned = si_supported(P);
+    if (!tuned && flags == 0)
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1; k = 2, N = 1024, pbs_l = 1");
+    if (!tuned && P.grouping_factor > 1)
+        return fail(HELM_ERR_INVALID, "multi-bit blind rotation (grouping_factor > 1) runs on the tuned builds only: this shape "
+                                      "(k,N,pbs_l) has none, and the generic kernel has no multi-bit form");
+    if (!tuned && !si_generic_domain(P))
+        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the generic kernel: its domain is N in {256,512,1024,2048}, "
+                                      "k >= 1 with (k+1) N <= 4096, pbs_l >= 1, grouping_factor <= 1");
+    const bool run_generic = force || !tuned;
     if (P.n < 1 || P.n > 1024) return fail(HELM_ERR_INVALID, "n must be in [1,1024]");
     // (pbs_logB <= 24: the kernels multiply digits by the field's fourth root of unity, 25 bits, without a reduction)
     if (P.pbs_logB < 2 || P.pbs_logB > 24 || P.pbs_logB * P.pbs_l > 31)
@@ -2218,6 +2358,12 @@ int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx 
         (void)helm_si_ctx_destroy(ctx);
         return rc;
     }
+    if (run_generic) {
+        if (int rc = setup_generic(ctx)) {
+            (void)helm_si_ctx_destroy(ctx);
+            return rc;
+        }
+    }
     ctx->group = group;
     if (group > 1) { // the 2N powers of psi per field: monomial products in the transform domain
         std::vector<double> pw((size_t)4 * N);
@@ -2237,6 +2383,7 @@ int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx 
     ctx->use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
     if (const char *v = getenv("HELM_HIP_KS_MFMA")) ctx->ks_mfma = atoi(v);
     if (const char *v = getenv("HELM_SI_SPLIT")) ctx->use_split = (ctx->use_split && atoi(v) != 0) || group > 1;
+    if (ctx->gen) ctx->use_split = false; // (group is 1 here: a generic context has no multi-bit form)
     if (ctx->use_split) {
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
@@ -2280,6 +2427,12 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
     ctx->expo = primary->expo;
     ctx->psi_pow = primary->psi_pow;
     ctx->use_split = primary->use_split;
+    ctx->gen = primary->gen;
+    ctx->gen_d = primary->gen_d;
+    ctx->gen_lds = primary->gen_lds;
+    ctx->gen_per_cu = primary->gen_per_cu;
+    ctx->twi[0] = primary->twi[0];
+    ctx->twi[1] = primary->twi[1];
     ctx->ksk = primary->ksk;
     ctx->ksk_planes = primary->ksk_planes;
     ctx->ks_kchunks = primary->ks_kchunks;
@@ -2318,6 +2471,8 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx)
     if (!ctx->lane_of) { // a lane borrows its keys and tables
         (void)hipFree(ctx->tw[0]);
         (void)hipFree(ctx->tw[1]);
+        (void)hipFree(ctx->twi[0]);
+        (void)hipFree(ctx->twi[1]);
         (void)hipFree(ctx->bsk);
         (void)hipFree(ctx->bsk_split);
         (void)hipFree(ctx->tw_sub);
@@ -2360,6 +2515,12 @@ int helm_si_field_bits(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
     return (ctx->lane_of ? ctx->lane_of : ctx)->pair ? 46 : 49;
+}
+
+int helm_si_kernel_class(const helm_si_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return ctx->gen ? 1 : 0;
 }
 
 int helm_si_set_stream(helm_si_ctx *ctx, void *hip_stream)
@@ -2416,7 +2577,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     HIP_TRY(hipMalloc(&t_std.p, n_words * sizeof(uint64_t)));
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
     if (!ctx->bsk && ctx->group == 1) HIP_TRY(hipMalloc(&ctx->bsk, n_words * 2 * sizeof(double)));
-    if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && ctx->group == 1 && !ctx->lane_of) {
+    if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && ctx->group == 1 && !ctx->lane_of && !ctx->gen) {
         // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
         // every k = 1 set's): the CRT pair follows the key at hand.  An exact product of a blind-rotation step is at most
         // B/2 x the largest l1-norm over the key polynomials that meet in one output column (or, transposed, in one row) - an
@@ -2457,14 +2618,26 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->pair) { // (N = 512 only)
+    if (ctx->gen) {
+        // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
+        const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx;
+#define GEN64_CONVERT(LN)                                                                                                 \
+    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(G64_THREADS), 0, ctx->stream, d_std, ctx->bsk, \
+                       root->tw[0], root->tw[1], root->n_inv[0], root->n_inv[1], root->two32[0], root->two32[1], (int)K1,      \
+                       P.pbs_l)
+        if (ctx->logN == 8) GEN64_CONVERT(8);
+        else if (ctx->logN == 9) GEN64_CONVERT(9);
+        else if (ctx->logN == 10) GEN64_CONVERT(10);
+        else GEN64_CONVERT(11);
+#undef GEN64_CONVERT
+    } else if (ctx->pair) { // (N = 512 only)
         hipLaunchKernelGGL((k_bsk_convert64<J0, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk,
                            ctx->tw[0], ctx->n_inv[0], ctx->two32[0], (int)K1, P.pbs_l, 0);
         hipLaunchKernelGGL((k_bsk_convert64<J1, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk,
                            ctx->tw[1], ctx->n_inv[1], ctx->two32[1], (int)K1, P.pbs_l, 1);
     }
 #define CONV(LN)                                                                                                     \
-    if (ctx->logN == LN && ctx->group == 1 && !ctx->pair) {                                                                                           \
+    if (ctx->logN == LN && ctx->group == 1 && !ctx->pair && !ctx->gen) {                                                                                         \
         hipLaunchKernelGGL((k_bsk_convert64<F0, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk, \
                            ctx->tw[0], ctx->n_inv[0], ctx->two32[0], (int)K1, P.pbs_l, 0);                           \
         hipLaunchKernelGGL((k_bsk_convert64<F1, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk, \

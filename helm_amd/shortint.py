@@ -107,13 +107,25 @@ class SiClientKey:
         return out
 
 
-class SiServerKey:
-    """GPU engine context (64-bit torus) with both keys resident in HBM."""
+SI_CREATE_ALLOW_GENERIC = 1  # include/helm_shortint.h HELM_SI_CREATE_*
+SI_CREATE_FORCE_GENERIC = 2
+_GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC}
 
-    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0):
+
+class SiServerKey:
+    """GPU engine context (64-bit torus) with both keys resident in HBM.
+
+    generic: None admits the shapes of the tuned bootstrap builds only (helm_si_ctx_create); "allow" also admits the
+    shapes no tuned build covers, which then run on the generic kernel (HELM_SI_CREATE_ALLOW_GENERIC); "force" runs every
+    bootstrap on the generic kernel, tuned shapes too (HELM_SI_CREATE_FORCE_GENERIC)."""
+
+    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, generic=None):
+        if generic not in _GENERIC_FLAGS:
+            raise ValueError(f"generic must be None, 'allow' or 'force', not {generic!r}")
         self.params = client_key.params if client_key is not None else params
+        self.generic = generic
         h = nv.vp()
-        hip_check(hip.helm_si_ctx_create(device, C.byref(self.params), C.byref(h)))
+        hip_check(hip.helm_si_ctx_create_ex(device, C.byref(self.params), _GENERIC_FLAGS[generic], C.byref(h)))
         self._h = h
         self.dim = self.params.k * self.params.N
         if client_key is not None:
@@ -128,7 +140,7 @@ class SiServerKey:
     def fork(self):
         """A lane (helm_si_ctx_fork): shares this key's device-resident keys and wire tables, own stream and scratch."""
         lane = SiServerKey.__new__(SiServerKey)
-        lane.params, lane.dim = self.params, self.dim
+        lane.params, lane.dim, lane.generic = self.params, self.dim, self.generic
         h = nv.vp()
         hip_check(hip.helm_si_ctx_fork(self._h, C.byref(h)))
         lane._h = h
@@ -161,6 +173,14 @@ class SiServerKey:
         """49 or 46: the CRT pair of prime fields this context's bootstrap kernels compute in (helm_si_field_bits: it follows
         the loaded key for k > 1 contexts)."""
         return int(hip.helm_si_field_bits(self._h))
+
+    def kernel_class(self):
+        """"tuned" when a tuned bootstrap build runs this context's launches, "generic" when the generic kernel does (a shape
+        no tuned build covers under generic="allow", or any shape under generic="force"; helm_si_kernel_class)."""
+        v = int(hip.helm_si_kernel_class(self._h))
+        if v < 0:
+            hip_check(v)
+        return "generic" if v == 1 else "tuned"
 
     def set_stream(self, stream_ptr):
         nv.require_one_hip_runtime(type(self).__name__ + ".set_stream")  # the handle is another framework's

@@ -129,7 +129,9 @@ int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx);
  * k_pbs_duo, k_pbs_trio, k_pbs_tri10: (512,2,3) (512,1,3) (512,1,2) (1024,1,3) (1024,1,2)), 1 = the generic kernel
  * (k_pbs_generic: k and pbs_l at run time, N = 256 ... 2048, (k+1) N <= 8192, always the 51-bit field).  It reflects the
  * shape only: HELM_HIP_PBS_VARIANT=10, which runs a tuned shape on the generic kernel, does not change it (on a class-1
- * shape helm_hip_ctx_create refuses the variants that name tuned builds).  Negative on error. */
+ * shape helm_hip_ctx_create refuses the variants that name tuned builds) - that variable is a debug switch.  The 64-bit
+ * engine's helm_si_kernel_class (helm_shortint.h) differs: its forcing is an API flag, so it reports the kernel the launches
+ * run on.  Negative on error. */
 int helm_hip_kernel_class(const helm_hip_ctx *ctx);
 
 /* What a launch of at most 1/4, 2/4, 3/4 and 4/4 of helm_hip_launch_quantum() bootstraps costs on this context, relative to

@@ -71,8 +71,33 @@ typedef struct {
     int32_t grouping_factor;
 } helm_si_params;
 
-/* Replaces shortint ServerKey construction (helm.rs:301: gen_keys(PARAM_...)). */
+/* Replaces shortint ServerKey construction (helm.rs:301: gen_keys(PARAM_...)).  Admits the shapes the tuned bootstrap
+ * builds cover: k = 1 at N in {512, 1024, 2048} with pbs_l in {1, 2}; k in {2, 3} at N = 512 and k = 2 at N = 1024, with
+ * pbs_l = 1.  Equal to helm_si_ctx_create_ex(device_id, params, 0, out). */
 int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx **out);
+
+/* Flags of helm_si_ctx_create_ex. */
+enum {
+    HELM_SI_CREATE_ALLOW_GENERIC = 1, /* admit shapes no tuned build covers: they run on the generic kernel */
+    HELM_SI_CREATE_FORCE_GENERIC = 2  /* run every launch on the generic kernel, tuned shapes too (implies 1) */
+};
+/* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
+ * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
+ * 1024, 2048} (FpG2 has 2-adicity 2^12: no 2N-th root of unity beyond N = 2048), k >= 1 with (k+1) N <= 4096 (the kernel's
+ * LDS budget), pbs_l >= 1, grouping_factor <= 1 - and passes every other check of helm_si_ctx_create (n, the decompositions,
+ * message_modulus * carry_modulus, the two-prime capacity bound).  Its bootstraps then run on k_pbs64_generic (k, pbs_l and
+ * pbs_logB at run time, one workgroup per bootstrap, the 49-bit pair: helm_si_field_bits() returns 49).  Multi-bit shapes
+ * without a tuned build are refused, and so is HELM_SI_CREATE_FORCE_GENERIC with grouping_factor > 1.  Everything above
+ * the bootstrap kernel (keyswitch, lincomb, look-up levels, lanes, audit, sharding, round capacity) works unchanged; the
+ * WoP-PBS path (helm_wop_ctx_create) refuses a PBS-side context whose launches run generic.  An importer that meets a key
+ * of an unfamiliar shape passes HELM_SI_CREATE_ALLOW_GENERIC on purpose: the generic kernel is slower than a tuned build.
+ * Unknown flag bits: HELM_ERR_INVALID. */
+int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
+/* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic).  Unlike
+ * helm_hip_kernel_class of the boolean engine, which reports the parameter shape only (its forcing is a debug variable),
+ * this reports the kernel the launches actually run on: HELM_SI_CREATE_FORCE_GENERIC is part of this API, so a forced
+ * tuned shape reports 1.  A lane reports its primary's class.  Negative on error. */
+int helm_si_kernel_class(const helm_si_ctx *ctx);
 int helm_si_ctx_destroy(helm_si_ctx *ctx);
 /* A lane: a second context on the same device that shares `primary`'s keys and may work on its wire tables, with
  * its own stream and scratch - independent parts of a circuit can then be evaluated concurrently (one host thread
@@ -200,7 +225,7 @@ int helm_si_set_audit(helm_si_ctx *ctx, helm_si_audit_fn fn, void *user);
 int helm_si_bound_violations(helm_si_ctx *ctx, uint32_t counts[8], int reset);
 
 /* Programmable bootstraps the device holds at once under this parameter set: CUs x workgroups of the set's bootstrap kernel
- * per CU (1 at N = 2048, 2 for k_pbs64k).  A batch of at most this many ciphertexts takes one bootstrap's time whatever its
+ * per CU (1 at N = 2048, 2 for k_pbs64k; on the generic kernel, its resident workgroups per CU at the context's LDS size).  A batch of at most this many ciphertexts takes one bootstrap's time whatever its
  * size; the host library merges the look-up rounds of concurrent operators into launches of at most this size. */
 int64_t helm_si_round_capacity(helm_si_ctx *ctx);
 

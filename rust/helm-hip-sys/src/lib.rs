@@ -60,6 +60,10 @@ pub const HELM_GATE_BUF: i32 = 10;
 pub const HELM_GATE_CONST_ONE: i32 = 11;
 pub const HELM_GATE_CONST_ZERO: i32 = 12;
 
+// include/helm_shortint.h: flags of helm_si_ctx_create_ex (an importer that meets an untuned key shape passes ALLOW_GENERIC)
+pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
+pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
+
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
 pub const HELM_RADIX_ADD: i32 = 1;
@@ -197,6 +201,8 @@ extern "C" {
 
     // ---- include/helm_shortint.h (LUT / arithmetic modes) -------------------------------------
     pub fn helm_si_ctx_create(device_id: c_int, params: *const helm_si_params, out: *mut *mut helm_si_ctx) -> c_int;
+    pub fn helm_si_ctx_create_ex(device_id: c_int, params: *const helm_si_params, flags: c_int, out: *mut *mut helm_si_ctx) -> c_int;
+    pub fn helm_si_kernel_class(ctx: *const helm_si_ctx) -> c_int;
     pub fn helm_si_ctx_destroy(ctx: *mut helm_si_ctx) -> c_int;
     pub fn helm_si_ctx_fork(primary: *mut helm_si_ctx, lane_out: *mut *mut helm_si_ctx) -> c_int;
     pub fn helm_si_load_bootstrap_key(ctx: *mut helm_si_ctx, bsk_std: *const u64, n_words: usize) -> c_int;
