@@ -221,3 +221,25 @@ def test_46_bit_pair_of_the_binarys_lut_set_stays_exact_without_recentring():
     typical = 4 * 1 * 512 * 2.0 ** 62 * 2.0 ** 17
     worst = 4 * 1 * 512 * 2.0 ** 63 * 2.0 ** 17
     assert typical * 1.3 < pp_half < worst and abs(math.log2(pp_half) - 90.62) < 0.01
+
+
+@pytest.mark.parametrize("kernel,primes,sum_max,prod_max,batch_max", [
+    ("k_pbs_generic", (6432 ** 4 + 1,), 1.14, 0.64, 3.07),
+    ("k_pbs64_generic", (5072 ** 4 + 1, 5096 ** 4 + 1), 1.1, 0.56, 2.8),
+])
+def test_generic_kernels_batch_sums_stay_exact(kernel, primes, sum_max, prod_max, batch_max):
+    """The generic kernels (helm_pbs_generic.inc, helm_pbs64_generic.inc) store every transform stage
+    recentred, |x| <= p/2 + 1: a butterfly's sum or difference and its mulmod, the product of a recentred transform output
+    with a key word, and a column sum that enters a batch recentred and takes at most four products - the figures the
+    kernels' heads and DESIGN quote, for any (k+1) l since the sum is recentred after every batch."""
+    for p in primes:
+        half = p / 2 + 1
+        prod = mulmod_bound(half, p)                    # recentred value x twiddle or key word, |w| <= p/2
+        butterfly = half + prod                         # u + mulmod(v, w): the sum a stage forms before it is recentred
+        assert butterfly < LIMIT and mulmod_bound(2 * half, p) < LIMIT   # (u - v) w of a Gentleman-Sande butterfly
+        batch = half + 4 * prod                         # D <= 4 digit polynomials per batch
+        assert batch < LIMIT and mulmod_bound(batch, p) < LIMIT           # reduce() takes it
+        # the documents quote these to two decimals
+        assert round(butterfly / p, 2) <= sum_max and round(prod / p, 2) <= prod_max and round(batch / p, 2) <= batch_max
+        print(f"\n{kernel} [p = {p}]: butterfly <= {butterfly / p:.4f} p, product <= {prod / p:.4f} p, "
+              f"batch of four <= {batch / p:.4f} p of 2^53 = {LIMIT / p:.2f} p")
