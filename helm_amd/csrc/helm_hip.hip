@@ -133,8 +133,24 @@ template <int L>
 __device__ __forceinline__ void decompose(uint32_t x, int logB, int (&dig)[L])
 {
     const int rep = logB * L;
-    uint32_t state = (x + (1u << (31 - rep))) >> (32 - rep);
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
+    if (L >= 2 && rep == 32) {
+        // every bit is representable (the keyswitch admits ks_l * ks_logB == 32; uniform branch): the word as it is, no
+        // rounding term (a shift by 31 - rep = -1 would be undefined; the hardware masks it to 31 and adds 2^31).  The
+        // state then fills the word: the addition of the least significant level can carry out of it (the carry is bit
+        // 32 - logB of `next`), and `next` outgrows decompose_step's 24-bit multiply - shifts and a subtraction instead.
+        uint32_t state = x;
+#pragma unroll
+        for (int lev = L - 1; lev >= 0; lev--) {
+            const uint32_t sum = state + half_m1 + __builtin_amdgcn_ubfe(state, 2 * logB - 1, 1);
+            uint32_t next = sum >> logB;
+            if (lev == L - 1) next |= (uint32_t)(sum < state) << (32 - logB);
+            dig[lev] = (int)(state - (next << logB));
+            state = next;
+        }
+        return;
+    }
+    uint32_t state = (x + (1u << (31 - rep))) >> (32 - rep);
     const int neg_B = -(1 << logB);
 #pragma unroll
     for (int lev = L - 1; lev >= 0; lev--) dig[lev] = decompose_step(state, logB, half_m1, neg_B, lev == 0);

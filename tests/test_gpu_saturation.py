@@ -14,8 +14,8 @@ Keys that follow the loaded key (N = 1024 boolean: the lazy field FpI; k_pbs64k 
 placed just under and just over the loaders' thresholds.  One child process repeats every case the bound-counting build
 (libhelm_hip_check.so) admits and requires all of its counters at zero.
 
-Out of scope: the multi-bit sets (si_toy_1024_mb2, si_toy_2048_mb3) - their nested key sums need another construction -
-and the keyswitch (integer arithmetic mod 2^w with exact accumulators, tested at all-zero / all-one rows elsewhere)."""
+Out of scope, still: the multi-bit sets (si_toy_1024_mb2, si_toy_2048_mb3), whose nested key sums need another
+construction.  The keyswitch has its own edge construction: tests/ks_edges.py, tests/test_gpu_keyswitch_edges.py."""
 import contextlib
 import json
 import os
