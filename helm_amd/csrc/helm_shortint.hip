@@ -1658,12 +1658,18 @@ bool si_supported(const helm_si_params &P)
 }
 
 // the shapes k_pbs64_generic takes (helm_si_ctx_create_ex with a HELM_SI_CREATE_* flag): N stops at 2048 because FpG2 has
-// 2-adicity 2^12 (no 2N-th root of unity beyond), (k+1) N <= 4096 is its LDS budget (helm_pbs64_generic.inc), and it has no
-// multi-bit form
-bool si_generic_domain(const helm_si_params &P)
+// 2-adicity 2^12 (no 2N-th root of unity beyond), (k+1) N <= 4096 is its LDS budget (helm_pbs64_generic.inc); its multi-bit
+// form (grouping_factor 2 or 3, which must divide n) is on request only: HELM_SI_CREATE_GENERIC_MULTIBIT
+bool si_generic_domain(const helm_si_params &P, bool multibit)
 {
     return (P.N == 256 || P.N == 512 || P.N == 1024 || P.N == 2048) && P.k >= 1 && (int64_t)(P.k + 1) * P.N <= 4096 &&
-           P.pbs_l >= 1 && P.grouping_factor <= 1;
+           P.pbs_l >= 1 && P.grouping_factor <= (multibit ? 3 : 1);
+}
+
+// the shapes the tuned multi-bit build (k_pbs64s) serves
+bool si_tuned_multibit(const helm_si_params &P)
+{
+    return P.k == 1 && P.pbs_l == 1 && (P.N == 1024 || P.N == 2048);
 }
 
 template <typename C>
@@ -1789,6 +1795,17 @@ namespace {
 // k_pbs64_generic: k, pbs_l and pbs_logB at run time (helm_si_ctx_create_ex)
 #include "helm_pbs64_generic.inc"
 
+template <int LOGN, int GG>
+hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                                  const uint64_t *luts, uint64_t *out)
+{
+    const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx; // a lane reads the key and tables through its primary
+    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(G64_THREADS), ctx->gen_lds, ctx->stream, jobs,
+                       small, luts, root->bsk, root->tw[0], root->tw[1], root->twi[0], root->twi[1], root->psi_pow, out,
+                       ctx->P.n, ctx->P.k, ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d, root->p0inv_mod_p1);
+    return hipGetLastError();
+}
+
 template <int LOGN>
 hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                                   const uint64_t *luts, uint64_t *out, int *per_cu)
@@ -1798,11 +1815,9 @@ hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_
         *per_cu = ctx->gen_per_cu;
         return hipSuccess;
     }
-    const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx; // a lane reads the key and tables through its primary
-    hipLaunchKernelGGL(k_pbs64_generic<LOGN>, dim3((unsigned)count), dim3(G64_THREADS), ctx->gen_lds, ctx->stream, jobs, small,
-                       luts, root->bsk, root->tw[0], root->tw[1], root->twi[0], root->twi[1], out, ctx->P.n, ctx->P.k,
-                       ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d, root->p0inv_mod_p1);
-    return hipGetLastError();
+    if (ctx->group == 3) return launch_pbs64_generic_g<LOGN, 3>(ctx, jobs, count, small, luts, out);
+    if (ctx->group == 2) return launch_pbs64_generic_g<LOGN, 2>(ctx, jobs, count, small, luts, out);
+    return launch_pbs64_generic_g<LOGN, 0>(ctx, jobs, count, small, luts, out);
 }
 
 hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
@@ -1817,12 +1832,19 @@ hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t 
     }
 }
 
-const void *pbs64_generic_kernel(int logN)
+template <int GG>
+const void *pbs64_generic_kernel_g(int logN)
 {
-    return logN == 8    ? reinterpret_cast<const void *>(k_pbs64_generic<8>)
-           : logN == 9  ? reinterpret_cast<const void *>(k_pbs64_generic<9>)
-           : logN == 10 ? reinterpret_cast<const void *>(k_pbs64_generic<10>)
-                        : reinterpret_cast<const void *>(k_pbs64_generic<11>);
+    return logN == 8    ? reinterpret_cast<const void *>(k_pbs64_generic<8, GG>)
+           : logN == 9  ? reinterpret_cast<const void *>(k_pbs64_generic<9, GG>)
+           : logN == 10 ? reinterpret_cast<const void *>(k_pbs64_generic<10, GG>)
+                        : reinterpret_cast<const void *>(k_pbs64_generic<11, GG>);
+}
+
+// group: the multi-bit grouping factor (2 or 3), anything else: the classical form
+const void *pbs64_generic_kernel(int logN, int group)
+{
+    return group == 3 ? pbs64_generic_kernel_g<3>(logN) : group == 2 ? pbs64_generic_kernel_g<2>(logN) : pbs64_generic_kernel_g<0>(logN);
 }
 
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
@@ -2243,7 +2265,8 @@ int setup_generic(helm_si_ctx *ctx)
         if (!ctx->twi[f]) HIP_TRY(hipMalloc(&ctx->twi[f], sizeof(double) * N));
         HIP_TRY(hipMemcpy(ctx->twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     }
-    const void *kern = pbs64_generic_kernel(logN);
+    const int group = P.grouping_factor > 1 ? P.grouping_factor : 1;
+    const void *kern = pbs64_generic_kernel(logN, group);
     // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a context
     // created later with a smaller one cannot lower it under an earlier context's launches
     const int K1max = 4096 / N;
@@ -2275,8 +2298,8 @@ int setup_generic(helm_si_ctx *ctx)
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_si] k_pbs64_generic N=%d k=%d l=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N,
-                P.k, P.pbs_l, ctx->gen_d, ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
+        fprintf(stderr, "[helm_si] k_pbs64_generic N=%d k=%d l=%d g=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n",
+                N, P.k, P.pbs_l, group, ctx->gen_d, ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
     }
     return 0;
 }
@@ -2295,22 +2318,32 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
     const helm_si_params &P = *params;
-    if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC))
+    if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
-                                          " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2)");
+                                          " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2, "
+                                          "HELM_SI_CREATE_GENERIC_MULTIBIT = 16; 4 and 8 are reserved)");
     const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
-    if (force && P.grouping_factor > 1)
+    const bool multibit = (flags & HELM_SI_CREATE_GENERIC_MULTIBIT) != 0;
+    if (multibit && !(flags & (HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC)))
+        return fail(HELM_ERR_INVALID, "flags " + std::to_string(flags) + ": HELM_SI_CREATE_GENERIC_MULTIBIT goes with "
+                                          "HELM_SI_CREATE_ALLOW_GENERIC or HELM_SI_CREATE_FORCE_GENERIC");
+    if (force && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "HELM_SI_CREATE_FORCE_GENERIC: the generic kernel has no multi-bit form (grouping_factor > 1)");
-    const bool tuned = si_supported(P);
+    // with HELM_SI_CREATE_GENERIC_MULTIBIT a multi-bit shape is tuned only where the tuned multi-bit build serves it
+    const bool tuned = si_supported(P) && !(multibit && P.grouping_factor > 1 && !si_tuned_multibit(P));
     if (!tuned && flags == 0)
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1; k = 2, N = 1024, pbs_l = 1");
-    if (!tuned && P.grouping_factor > 1)
+    if (!tuned && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation (grouping_factor > 1) runs on the tuned builds only: this shape "
                                       "(k,N,pbs_l) has none, and the generic kernel has no multi-bit form");
-    if (!tuned && !si_generic_domain(P))
-        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the generic kernel: its domain is N in {256,512,1024,2048}, "
-                                      "k >= 1 with (k+1) N <= 4096, pbs_l >= 1, grouping_factor <= 1");
     const bool run_generic = force || !tuned;
+    const bool gen_mb = run_generic && multibit && P.grouping_factor > 1; // the generic kernel's multi-bit form
+    if (gen_mb && (P.grouping_factor > 3 || P.n % P.grouping_factor))
+        return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
+    if ((!tuned || gen_mb) && !si_generic_domain(P, gen_mb))
+        return fail(HELM_ERR_INVALID, std::string("unsupported (k,N,pbs_l) for the generic kernel: its domain is N in {256,512,1024,2048}, "
+                                      "k >= 1 with (k+1) N <= 4096, pbs_l >= 1, ") +
+                                          (gen_mb ? "grouping_factor <= 3 under HELM_SI_CREATE_GENERIC_MULTIBIT" : "grouping_factor <= 1"));
     if (P.n < 1 || P.n > 1024) return fail(HELM_ERR_INVALID, "n must be in [1,1024]");
     // (pbs_logB <= 24: the kernels multiply digits by the field's fourth root of unity, 25 bits, without a reduction)
     if (P.pbs_logB < 2 || P.pbs_logB > 24 || P.pbs_logB * P.pbs_l > 31)
@@ -2323,7 +2356,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     const int group = P.grouping_factor > 1 ? P.grouping_factor : 1;
     if (P.grouping_factor < 0 || group > 3 || P.n % group)
         return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
-    if (group > 1 && !(P.pbs_l == 1 && P.N >= 1024))
+    if (group > 1 && !gen_mb && !(P.pbs_l == 1 && P.N >= 1024))
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation is built for pbs_l = 1, N >= 1024 (every tfhe multi-bit set)");
     // exactness: |sum| <= (k+1) * l * N * (B/2) * 2^63 must stay below p0 * p1 / 2
     {
@@ -2383,7 +2416,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     ctx->use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
     if (const char *v = getenv("HELM_HIP_KS_MFMA")) ctx->ks_mfma = atoi(v);
     if (const char *v = getenv("HELM_SI_SPLIT")) ctx->use_split = (ctx->use_split && atoi(v) != 0) || group > 1;
-    if (ctx->gen) ctx->use_split = false; // (group is 1 here: a generic context has no multi-bit form)
+    if (ctx->gen) ctx->use_split = false; // (a generic context reads one key layout, multi-bit too)
     if (ctx->use_split) {
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
@@ -2570,13 +2603,50 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
     HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->gen && ctx->group > 1) {
+        // The generic kernel's multi-bit form sums the 2^g subsets' products of a group before the CRT lift, so the exact
+        // integer coefficient of a group step is at most B/2 x the largest l1-norm over the key polynomials (taken as centred
+        // 64-bit words) of all subsets and levels that meet in one output column - or, transposed, in one row, as for the
+        // 46-bit pair below.  The creation-time capacity check does not carry the factor 2^g (a worst case no honest key
+        // comes near: a uniformly random key of k = 1, N = 2048, logB = 21, g = 3 stays at 0.71 of the limit); this one is
+        // sufficient for the key at hand and every input.  A key beyond it is refused and the context keeps its state.
+        const size_t per_ggsw = (size_t)P.pbs_l * K1 * K1, subsets = (size_t)1 << ctx->group; // src is [t][S][lev][r][c][N]
+        std::vector<long double> l1(subsets * per_ggsw);
+        long double worst = 0;
+        for (size_t t = 0; t < n_ggsw / subsets; t++) {
+            for (size_t q = 0; q < l1.size(); q++) {
+                const uint64_t *poly = bsk_std + (t * l1.size() + q) * P.N;
+                long double sum = 0;
+                for (int j = 0; j < P.N; j++) {
+                    const int64_t v = (int64_t)poly[j];
+                    sum += v < 0 ? -(long double)v : (long double)v;
+                }
+                l1[q] = sum;
+            }
+            for (size_t c = 0; c < K1; c++) {
+                long double by_col = 0, by_row = 0;
+                for (size_t q = 0; q < l1.size(); q++) {
+                    if (q % K1 == c) by_col += l1[q];
+                    if ((q / K1) % K1 == c) by_row += l1[q];
+                }
+                worst = std::max(worst, std::max(by_col, by_row));
+            }
+        }
+        const long double key_bound = worst * (long double)(1ull << (P.pbs_logB - 1));
+        if (key_bound * 1.001L >= (long double)F0::P * (long double)F1::P / 2) {
+            char ratio[32];
+            snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / ((long double)F0::P * (long double)F1::P / 2));
+            return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the generic multi-bit "
+                                                      "kernel: its largest group sum is ") + ratio + " of p0 p1 / 2");
+        }
+    }
     struct Tmp {
         void *p = nullptr;
         ~Tmp() { if (p) (void)hipFree(p); }
     } t_std; // freed on every return path
     HIP_TRY(hipMalloc(&t_std.p, n_words * sizeof(uint64_t)));
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
-    if (!ctx->bsk && ctx->group == 1) HIP_TRY(hipMalloc(&ctx->bsk, n_words * 2 * sizeof(double)));
+    if (!ctx->bsk && (ctx->group == 1 || ctx->gen)) HIP_TRY(hipMalloc(&ctx->bsk, n_words * 2 * sizeof(double)));
     if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && ctx->group == 1 && !ctx->lane_of && !ctx->gen) {
         // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
         // every k = 1 set's): the CRT pair follows the key at hand.  An exact product of a blind-rotation step is at most
@@ -2660,7 +2730,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->group > 1 && !ctx->expo) {
+    if (ctx->group > 1 && !ctx->gen && !ctx->expo) { // (the generic kernel derives its spectrum positions: helm_pbs64_generic.inc)
         if (int rc = probe_spectrum_positions(ctx)) return rc;
     }
     ctx->have_bsk = true;

@@ -109,7 +109,10 @@ class SiClientKey:
 
 SI_CREATE_ALLOW_GENERIC = 1  # include/helm_shortint.h HELM_SI_CREATE_*
 SI_CREATE_FORCE_GENERIC = 2
-_GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC}
+SI_CREATE_GENERIC_MULTIBIT = 16
+_GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC,
+                  "allow+multibit": SI_CREATE_ALLOW_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
+                  "force+multibit": SI_CREATE_FORCE_GENERIC | SI_CREATE_GENERIC_MULTIBIT}
 
 
 class SiServerKey:
@@ -117,11 +120,14 @@ class SiServerKey:
 
     generic: None admits the shapes of the tuned bootstrap builds only (helm_si_ctx_create); "allow" also admits the
     shapes no tuned build covers, which then run on the generic kernel (HELM_SI_CREATE_ALLOW_GENERIC); "force" runs every
-    bootstrap on the generic kernel, tuned shapes too (HELM_SI_CREATE_FORCE_GENERIC)."""
+    bootstrap on the generic kernel, tuned shapes too (HELM_SI_CREATE_FORCE_GENERIC).  "allow+multibit" and
+    "force+multibit" add HELM_SI_CREATE_GENERIC_MULTIBIT: multi-bit shapes (grouping_factor 2 or 3) the tuned multi-bit
+    build does not serve run on the generic kernel's multi-bit form, under "force+multibit" every multi-bit shape does; the
+    bootstrapping key must then pass the load-time capacity check (include/helm_shortint.h)."""
 
     def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, generic=None):
         if generic not in _GENERIC_FLAGS:
-            raise ValueError(f"generic must be None, 'allow' or 'force', not {generic!r}")
+            raise ValueError(f"generic must be None, 'allow', 'force', 'allow+multibit' or 'force+multibit', not {generic!r}")
         self.params = client_key.params if client_key is not None else params
         self.generic = generic
         h = nv.vp()

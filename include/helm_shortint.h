@@ -79,7 +79,9 @@ int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx 
 /* Flags of helm_si_ctx_create_ex. */
 enum {
     HELM_SI_CREATE_ALLOW_GENERIC = 1, /* admit shapes no tuned build covers: they run on the generic kernel */
-    HELM_SI_CREATE_FORCE_GENERIC = 2  /* run every launch on the generic kernel, tuned shapes too (implies 1) */
+    HELM_SI_CREATE_FORCE_GENERIC = 2, /* run every launch on the generic kernel, tuned shapes too (implies 1) */
+    /* 4 and 8 are reserved: refused as unknown bits */
+    HELM_SI_CREATE_GENERIC_MULTIBIT = 16 /* with 1 or 2: multi-bit shapes may run on the generic kernel's multi-bit form */
 };
 /* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
  * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
@@ -87,11 +89,25 @@ enum {
  * LDS budget), pbs_l >= 1, grouping_factor <= 1 - and passes every other check of helm_si_ctx_create (n, the decompositions,
  * message_modulus * carry_modulus, the two-prime capacity bound).  Its bootstraps then run on k_pbs64_generic (k, pbs_l and
  * pbs_logB at run time, one workgroup per bootstrap, the 49-bit pair: helm_si_field_bits() returns 49).  Multi-bit shapes
- * without a tuned build are refused, and so is HELM_SI_CREATE_FORCE_GENERIC with grouping_factor > 1.  Everything above
+ * without a tuned build are refused, and so is HELM_SI_CREATE_FORCE_GENERIC with grouping_factor > 1, unless
+ * HELM_SI_CREATE_GENERIC_MULTIBIT is given (below).  Everything above
  * the bootstrap kernel (keyswitch, lincomb, look-up levels, lanes, audit, sharding, round capacity) works unchanged; the
  * WoP-PBS path (helm_wop_ctx_create) refuses a PBS-side context whose launches run generic.  An importer that meets a key
  * of an unfamiliar shape passes HELM_SI_CREATE_ALLOW_GENERIC on purpose: the generic kernel is slower than a tuned build.
- * Unknown flag bits: HELM_ERR_INVALID. */
+ * HELM_SI_CREATE_GENERIC_MULTIBIT (only together with one of the two flags above; alone it is HELM_ERR_INVALID) opens the
+ * generic kernel's multi-bit form: the domain becomes the same N, k and pbs_l limits with grouping_factor <= 3 dividing n,
+ * without the tuned multi-bit build's restriction to pbs_l = 1, N >= 1024.  With ALLOW, a multi-bit shape that the tuned
+ * multi-bit build serves (k = 1, pbs_l = 1, N in {1024, 2048}) still runs tuned and every other multi-bit shape of the
+ * domain runs generic - also a tuned classical shape whose multi-bit form does not exist (k = 1, N = 512; pbs_l = 2); with
+ * FORCE every launch runs generic, the tuned multi-bit sets included.  Shapes with grouping_factor <= 1 behave exactly as
+ * without the bit, and without the bit every multi-bit refusal above stands.  The creation-time capacity bound is only a
+ * necessary condition for a generic multi-bit context: a group step sums 2^grouping_factor subsets' products, so
+ * helm_si_load_bootstrap_key checks the key at hand - B/2 x the largest l1-norm (key words as centred 64-bit integers) over
+ * the polynomials of a group, all subsets and levels, that meet in one column or one row must stay below
+ * p0 p1 / 2 / 1.001 - and otherwise returns HELM_ERR_INVALID ("... capacity ...") and leaves the context as it was, usable
+ * for another key.  Keys with the noise and size of a tfhe parameter set stay well below it (about 0.71 of the limit for a
+ * uniformly random key at k = 1, N = 2048, pbs_logB = 21, grouping_factor = 3).
+ * Unknown flag bits (4 and 8 are reserved): HELM_ERR_INVALID. */
 int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
 /* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic).  Unlike
  * helm_hip_kernel_class of the boolean engine, which reports the parameter shape only (its forcing is a debug variable),

@@ -63,6 +63,7 @@ pub const HELM_GATE_CONST_ZERO: i32 = 12;
 // include/helm_shortint.h: flags of helm_si_ctx_create_ex (an importer that meets an untuned key shape passes ALLOW_GENERIC)
 pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
 pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
+pub const HELM_SI_CREATE_GENERIC_MULTIBIT: i32 = 16; // with one of the two above: the generic kernel's multi-bit form
 
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
