@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -1532,13 +1533,10 @@ struct helm_si_wires {
     int64_t n_rows;
 };
 
-struct helm_si_ctx {
-    int device = 0;
-    helm_si_ctx *lane_of = nullptr; // helm_si_ctx_fork(): the context whose keys and tables this one shares
-    helm_si_params P{};
-    int logN = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    bool high_priority = false; // own_stream was created at the device's highest priority (helm_si_set_priority)
+// What a key load decides: the tables of the CRT pair, the keys in their device layouts and the settings that go with them.
+// A primary context owns one (helm_si_ctx::own_keys); a lane holds its primary's, so a key loaded into the primary - which
+// may move the pair and rewrite every table - is what each lane launches with from then on.
+struct SiKeyState {
     double *tw[2] = {nullptr, nullptr};
     double n_inv[2] = {0, 0}, two32[2] = {0, 0};
     double p0inv_mod_p1 = 0;
@@ -1562,10 +1560,31 @@ struct helm_si_ctx {
     uint64_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: eight byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0, ks_mfma = 1; // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
+    bool have_bsk = false, have_ksk = false;
+    SiKeyState() = default;
+    SiKeyState(const SiKeyState &) = delete;
+    SiKeyState &operator=(const SiKeyState &) = delete;
+    ~SiKeyState() // (the owner's device is current: helm_si_ctx_destroy)
+    {
+        for (void *p : {(void *)tw[0], (void *)tw[1], (void *)twi[0], (void *)twi[1], (void *)tw_sub, (void *)bsk,
+                        (void *)bsk_split, (void *)expo, (void *)psi_pow, (void *)ksk, (void *)ksk_planes})
+            (void)hipFree(p);
+    }
+};
+
+struct helm_si_ctx {
+    int device = 0;
+    helm_si_ctx *lane_of = nullptr;     // helm_si_ctx_fork(): the primary this lane was forked from
+    std::vector<helm_si_ctx *> lanes;   // of a primary: its lanes (a key load waits for the stream of each)
+    std::unique_ptr<SiKeyState> own_keys; // of a primary
+    SiKeyState *keys = nullptr;         // own_keys, or the primary's: the one place shared state is read from
+    helm_si_params P{};
+    int logN = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    bool high_priority = false; // own_stream was created at the device's highest priority (helm_si_set_priority)
     DevBuf<int8_t> d_ksdig;
     DevBuf<int32_t> d_ksdsum;
     DevBuf<uint64_t> d_ksbody;
-    bool have_bsk = false, have_ksk = false;
     uint64_t delta = 0;
     int n_cus = 256;
     int64_t round_capacity = 0; // bootstraps resident at once (CUs x workgroups per CU of the set's kernel), probed on first need
@@ -1672,32 +1691,38 @@ bool si_tuned_multibit(const helm_si_params &P)
     return P.k == 1 && P.pbs_l == 1 && (P.N == 1024 || P.N == 2048);
 }
 
+// The dynamic-LDS limit of a launcher's kernels, set once per device (the attribute belongs to the device's code object).
+// `done` is the launcher's own flag set, one per kernel build; atomic because rank threads of one process launch concurrently.
+hipError_t lds_attr_once(std::atomic<bool> (&done)[64], int device, std::initializer_list<const void *> kernels, size_t bytes)
+{
+    if (done[device & 63]) return hipSuccess;
+    for (const void *k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    done[device & 63] = true;
+    return hipSuccess;
+}
+
 template <typename C>
 hipError_t launch_pbs64k_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                            const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    // the CRT pair follows the key loaded into the PRIMARY context (a lane shares its key and tables: helm_si_ctx_fork; a key
-    // loaded after the fork may have moved the pair)
-    const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx;
+    static std::atomic<bool> attr_done[64];
+    const SiKeyState &K = *ctx->keys; // (the CRT pair follows the key loaded last, on a lane too)
     // (the 46-bit pair is built for N = 512 only: helm_si_load_bootstrap_key never chooses it at another N)
     auto kern_j = [] {
         if constexpr (C::LOGN == 9) return k_pbs64k<C, J0, J1>;
         else return k_pbs64k<C, F0, F1>;
     }();
-    if (root->pair && C::LOGN != 9) return hipErrorInvalidValue;
-    auto kern = root->pair ? kern_j : k_pbs64k<C, F0, F1>;
-    if (!attr_done[ctx->device & 63]) {
-        for (auto kk : {k_pbs64k<C, F0, F1>, kern_j}) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)C::BYTES);
-            if (e != hipSuccess) return e;
-        }
-        attr_done[ctx->device & 63] = true;
-    }
+    if (K.pair && C::LOGN != 9) return hipErrorInvalidValue;
+    auto kern = K.pair ? kern_j : k_pbs64k<C, F0, F1>;
+    if (hipError_t e = lds_attr_once(attr_done, ctx->device, {reinterpret_cast<const void *>(k_pbs64k<C, F0, F1>),
+                                                              reinterpret_cast<const void *>(kern_j)}, C::BYTES))
+        return e;
     if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 64 * C::NW, C::BYTES);
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, small, luts, root->bsk,
-                       root->tw[0], root->tw[1], out, ctx->P.n, ctx->P.pbs_logB, root->p0inv_mod_p1);
+    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, small, luts, K.bsk,
+                       K.tw[0], K.tw[1], out, ctx->P.n, ctx->P.pbs_logB, K.p0inv_mod_p1);
     return hipGetLastError();
 }
 
@@ -1706,18 +1731,14 @@ hipError_t launch_pbs64_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count,
                           const uint64_t *luts, uint64_t *out, const double *key = nullptr, int n_steps = -1,
                           int logB = 0, size_t key_stride = 0, int key_first = 0, int *per_cu = nullptr)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
+    static std::atomic<bool> attr_done[64];
+    const SiKeyState &K = *ctx->keys;
     auto kern = k_pbs64<C, MODE>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-    }
+    if (hipError_t e = lds_attr_once(attr_done, ctx->device, {reinterpret_cast<const void *>(kern)}, C::BYTES)) return e;
     if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 64 * C::NW, C::BYTES);
     hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, small, luts,
-                       key ? key : ctx->bsk, ctx->tw[0], ctx->tw[1], out, n_steps >= 0 ? n_steps : ctx->P.n,
-                       logB ? logB : ctx->P.pbs_logB, ctx->p0inv_mod_p1, key_stride, key_first);
+                       key ? key : K.bsk, K.tw[0], K.tw[1], out, n_steps >= 0 ? n_steps : ctx->P.n,
+                       logB ? logB : ctx->P.pbs_logB, K.p0inv_mod_p1, key_stride, key_first);
 #ifdef HELM_WIDE_STAMPS
     {
         unsigned long long v[8 * 8];
@@ -1736,18 +1757,14 @@ template <typename C, bool MB>
 hipError_t launch_pbs64s_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                            const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
+    static std::atomic<bool> attr_done[64];
+    const SiKeyState &K = *ctx->keys;
     auto kern = k_pbs64s<C, MB>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-    }
+    if (hipError_t e = lds_attr_once(attr_done, ctx->device, {reinterpret_cast<const void *>(kern)}, C::BYTES)) return e;
     if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 64 * C::NW, C::BYTES);
     hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, small, luts,
-                       ctx->bsk_split, ctx->tw_sub, ctx->tw[0], ctx->tw[1], out, ctx->P.n, ctx->P.pbs_logB,
-                       ctx->p0inv_mod_p1, ctx->group, ctx->expo, ctx->psi_pow);
+                       K.bsk_split, K.tw_sub, K.tw[0], K.tw[1], out, ctx->P.n, ctx->P.pbs_logB, K.p0inv_mod_p1, K.group,
+                       K.expo, K.psi_pow);
 #ifdef HELM_WIDE_STAMPS
     {
         unsigned long long v[8 * 8];
@@ -1768,12 +1785,19 @@ hipError_t launch_pbs64s_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count
 // multi-bit k_pbs64s, and costs the classical k_pbs64s 0.8 % and its two-level build 1.8 % (same box, alternating,
 // identical ciphertexts: profiles/r03/si_kernel_experiments.txt (15)).  So the launchers of the first two are compiled a
 // second time with -DHELM_SI_TU=1 under that strategy - nothing else of the file is - and the main unit
-// (-DHELM_SI_SPLIT_TU=1) calls them through this one function.  Without the two macros the file is a single unit as before.
+// (-DHELM_SI_SPLIT_TU=1), which instantiates none of their kernels, calls them through this one function.  Without the two
+// macros the file is a single unit that holds the function itself.
+
+// does a (tuned) context launch one of the max-ILP unit's kernels?  The shapes helm_si_tu1_launch_pbs64 lists.
+bool si_ilp_shape(const helm_si_ctx *ctx)
+{
+    return ctx->P.k == 3 || ctx->P.k == 2 || (ctx->keys->use_split && ctx->keys->group > 1);
+}
 } // namespace
 __attribute__((visibility("hidden"))) hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs, int64_t count,
                                                                         const uint64_t *small, const uint64_t *luts,
                                                                         uint64_t *out, int *per_cu);
-#if HELM_SI_TU == 1
+#if !HELM_SI_SPLIT_TU
 hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_t count, const uint64_t *small,
                                     const uint64_t *luts, uint64_t *out, int *per_cu)
 {
@@ -1782,7 +1806,7 @@ hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_
     if (P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
     if (P.k == 2 && ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
     if (P.k == 2) return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->use_split && ctx->group > 1) {
+    if (ctx->keys->use_split && ctx->keys->group > 1) {
         if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, true>(ctx, jobs, count, small, luts, out, per_cu);
         if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11>, true>(ctx, jobs, count, small, luts, out, per_cu);
     }
@@ -1799,10 +1823,10 @@ template <int LOGN, int GG>
 hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                                   const uint64_t *luts, uint64_t *out)
 {
-    const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx; // a lane reads the key and tables through its primary
-    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(G64_THREADS), ctx->gen_lds, ctx->stream, jobs,
-                       small, luts, root->bsk, root->tw[0], root->tw[1], root->twi[0], root->twi[1], root->psi_pow, out,
-                       ctx->P.n, ctx->P.k, ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d, root->p0inv_mod_p1);
+    const SiKeyState &K = *ctx->keys;
+    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(G64_THREADS), K.gen_lds, ctx->stream, jobs,
+                       small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.k,
+                       ctx->P.pbs_l, ctx->P.pbs_logB, K.gen_d, K.p0inv_mod_p1);
     return hipGetLastError();
 }
 
@@ -1812,11 +1836,11 @@ hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_
 {
     // (the dynamic LDS attribute is set by helm_si_ctx_create_ex, at the largest layout of this N)
     if (per_cu) {
-        *per_cu = ctx->gen_per_cu;
+        *per_cu = ctx->keys->gen_per_cu;
         return hipSuccess;
     }
-    if (ctx->group == 3) return launch_pbs64_generic_g<LOGN, 3>(ctx, jobs, count, small, luts, out);
-    if (ctx->group == 2) return launch_pbs64_generic_g<LOGN, 2>(ctx, jobs, count, small, luts, out);
+    if (ctx->keys->group == 3) return launch_pbs64_generic_g<LOGN, 3>(ctx, jobs, count, small, luts, out);
+    if (ctx->keys->group == 2) return launch_pbs64_generic_g<LOGN, 2>(ctx, jobs, count, small, luts, out);
     return launch_pbs64_generic_g<LOGN, 0>(ctx, jobs, count, small, luts, out);
 }
 
@@ -1850,20 +1874,10 @@ const void *pbs64_generic_kernel(int logN, int group)
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                         const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
-    if (ctx->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
+    if (ctx->keys->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
     const helm_si_params &P = ctx->P;
-#if HELM_SI_SPLIT_TU
-    if (P.k == 3 || P.k == 2 || (ctx->use_split && ctx->group > 1))
-        return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu);
-#endif
-    if (P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (P.k == 2 && ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (P.k == 2) return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->use_split) {
-        if (ctx->group > 1) {
-            if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, true>(ctx, jobs, count, small, luts, out, per_cu);
-            if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11>, true>(ctx, jobs, count, small, luts, out, per_cu);
-        }
+    if (si_ilp_shape(ctx)) return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu);
+    if (ctx->keys->use_split) {
         if (P.pbs_l == 1) {
             if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, false>(ctx, jobs, count, small, luts, out, per_cu);
             if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11>, false>(ctx, jobs, count, small, luts, out, per_cu);
@@ -1896,7 +1910,7 @@ hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs
     // narrow batches stay on the vector-ALU kernel, whose key rows are split over workgroup slices: a matrix-core
     // wave walks the whole key column by column tile (0.23 ms whatever the width; vector ALU: 0.11 ms for 64, 0.37 ms
     // for 256 ciphertexts under PARAM_MESSAGE_2_CARRY_2)
-    if (K.planes && ctx->ks_mfma && count >= 160) {
+    if (K.planes && ctx->keys->ks_mfma && count >= 160) {
         const int64_t padded = (count + 63) / 64 * 64;
         const int LP = P.ks_l <= 1 ? 1 : P.ks_l <= 2 ? 2 : P.ks_l <= 4 ? 4 : 8;
         if (ctx->d_ksdig.ensure((size_t)padded * kN * LP) || ctx->d_ksdsum.ensure((size_t)padded) || ctx->d_ksbody.ensure((size_t)padded))
@@ -1952,14 +1966,14 @@ hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs
 hipError_t launch_ks64(helm_si_ctx *ctx, const Ks64Job *jobs, int64_t count, const uint64_t *big, uint64_t *out)
 {
     KsKey K;
-    K.key = ctx->ksk;
-    K.planes = ctx->ksk_planes;
+    K.key = ctx->keys->ksk;
+    K.planes = ctx->keys->ksk_planes;
     K.in_dim = ctx->P.k * ctx->P.N;
     K.out_dim = ctx->P.n;
     K.l = ctx->P.ks_l;
     K.logB = ctx->P.ks_logB;
-    K.kchunks = ctx->ks_kchunks;
-    K.ctiles = ctx->ks_ctiles;
+    K.kchunks = ctx->keys->ks_kchunks;
+    K.ctiles = ctx->keys->ks_ctiles;
     return launch_ks64_key(ctx, K, jobs, count, big, out);
 }
 
@@ -2056,7 +2070,7 @@ int apply_luts_device(helm_si_ctx *ctx, const uint64_t *src, uint64_t *dst, cons
                       const KsKey *other_key = nullptr) // other_key: keyswitch from another big key (WoP-PBS path)
 {
     const helm_si_params &P = ctx->P;
-    if (!ctx->have_bsk || !(ctx->have_ksk || other_key))
+    if (!ctx->keys->have_bsk || !(ctx->keys->have_ksk || other_key))
         return fail(HELM_ERR_STATE, "bootstrapping / keyswitching key not loaded");
     const int64_t count = (int64_t)pbs.size();
     if (count == 0) return 0;
@@ -2092,6 +2106,7 @@ int apply_luts_device(helm_si_ctx *ctx, const uint64_t *src, uint64_t *dst, cons
 // conversion kernel (one "key" of one polynomial) and look the values up among the powers of psi.
 int probe_spectrum_positions(helm_si_ctx *ctx)
 {
+    SiKeyState &K = *ctx->keys;
     const int N = ctx->P.N, H = N / 2;
     std::vector<uint64_t> xpoly((size_t)N, 0);
     xpoly[1] = 1;
@@ -2108,17 +2123,17 @@ int probe_spectrum_positions(helm_si_ctx *ctx)
     // one polynomial, K1 = 1: blocks (poly 0, half h) write d_out[(f * 2 + h) * N/2 ...] scaled by 1 (n_inv = 1)
 #define PROBE(LN)                                                                                                        \
     if (ctx->logN == LN) {                                                                                              \
-        hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, ctx->tw[0],        \
-                           ctx->tw_sub, 1.0, ctx->two32[0], 1, 0, 1);                                                    \
-        hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, ctx->tw[1],        \
-                           ctx->tw_sub + (size_t)2 * H, 1.0, ctx->two32[1], 1, 1, 1);                                    \
+        hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, K.tw[0],           \
+                           K.tw_sub, 1.0, K.two32[0], 1, 0, 1);                                                          \
+        hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, K.tw[1],           \
+                           K.tw_sub + (size_t)2 * H, 1.0, K.two32[1], 1, 1, 1);                                          \
     }
     PROBE(10) PROBE(11)
 #undef PROBE
     HIP_TRY(hipGetLastError());
     std::vector<double> val((size_t)4 * H), pw((size_t)4 * N);
     HIP_TRY(hipMemcpyAsync(val.data(), d_out, sizeof(double) * 4 * H, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(pw.data(), ctx->psi_pow, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pw.data(), K.psi_pow, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::vector<uint16_t> expo((size_t)2 * H);
     for (int f = 0; f < 2; f++) {
@@ -2151,8 +2166,8 @@ int probe_spectrum_positions(helm_si_ctx *ctx)
             fclose(fp);
         }
     }
-    HIP_TRY(hipMalloc(&ctx->expo, expo.size() * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(ctx->expo, expo.data(), expo.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&K.expo, expo.size() * sizeof(uint16_t)));
+    HIP_TRY(hipMemcpy(K.expo, expo.data(), expo.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -2202,39 +2217,53 @@ int apply_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx
     return 0;
 }
 
-// The forward twiddle tables (bit-reversed powers of a primitive 2N-th root psi), 1/N, 2^32 and the CRT constant of one pair
-// of fields.  pair 1 (the 46-bit fields): psi is chosen with psi^(N/4) = b, so that the first three table entries are b^2, b,
-// b^3 - what the plain radix-4 top of a forward transform on digits multiplies by (fwd_top2_digits).
+uint64_t si_modulus(int pair, int f) { return pair ? (f ? J1::P_U64 : J0::P_U64) : (f ? F1::P_U64 : F0::P_U64); }
+
+// psi of field f of a pair: a primitive 2N-th root of unity.  pair 1 (the 46-bit fields): the one with psi^(N/4) = b - it is
+// one of the primitive eighth roots b, b^3, -b, -b^3, and an odd power of psi puts it on b.  0: there is none.
+uint64_t si_psi(int N, int pair, int f)
+{
+    const uint64_t p = si_modulus(pair, f), gen = pair ? (f ? J1::GEN : J0::GEN) : (f ? F1::GEN : F0::GEN);
+    const uint64_t psi = powmod_u64(gen, (p - 1) / (2 * (uint64_t)N), p);
+    if (!pair) return psi;
+    for (uint64_t t = 1; t < 8; t += 2)
+        if (powmod_u64(powmod_u64(psi, t, p), (uint64_t)N / 4, p) == (uint64_t)(f ? J1::B1 : J0::B1)) return powmod_u64(psi, t, p);
+    return 0;
+}
+
+// out[i] = root^i mod p (centred), i < count; rev_bits > 0: power i goes to the bit-reversed index
+void power_table(double *out, uint64_t root, uint64_t p, int count, int rev_bits)
+{
+    uint64_t a = 1;
+    for (int i = 0; i < count; i++) {
+        out[rev_bits ? bitrev(i, rev_bits) : i] = centred(a, p);
+        a = mulmod_u64(a, root, p);
+    }
+}
+
+// The forward twiddle tables (bit-reversed powers of psi), 1/N, 2^32 and the CRT constant of one pair of fields.  pair 1: with
+// psi^(N/4) = b the first three table entries are b^2, b, b^3 - what the plain radix-4 top of a forward transform on digits
+// multiplies by (fwd_top2_digits).
 int setup_pair_tables(helm_si_ctx *ctx, int pair)
 {
-    const uint64_t pm[2] = {pair ? J0::P_U64 : F0::P_U64, pair ? J1::P_U64 : F1::P_U64};
-    const uint64_t gen[2] = {pair ? J0::GEN : F0::GEN, pair ? J1::GEN : F1::GEN};
+    SiKeyState &K = *ctx->keys;
+    const uint64_t pm[2] = {si_modulus(pair, 0), si_modulus(pair, 1)};
     const double b1[2] = {J0::B1, J1::B1}, b2[2] = {J0::B2, J1::B2}, b3[2] = {J0::B3, J1::B3};
-    const int N = ctx->P.N, logN = ctx->logN;
+    const int N = ctx->P.N;
     for (int f = 0; f < 2; f++) {
-        uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
-        if (pair) { // psi^(N/4) is one of the primitive eighth roots b, b^3, -b, -b^3: an odd power of psi puts it on b
-            uint64_t pick = 0;
-            for (uint64_t t = 1; t < 8 && !pick; t += 2)
-                if (powmod_u64(powmod_u64(psi, t, pm[f]), (uint64_t)N / 4, pm[f]) == (uint64_t)b1[f]) pick = t;
-            if (!pick) return fail(HELM_ERR_STATE, "internal: no 2N-th root of unity with psi^(N/4) = b");
-            psi = powmod_u64(psi, pick, pm[f]);
-        }
+        const uint64_t psi = si_psi(N, pair, f);
+        if (!psi) return fail(HELM_ERR_STATE, "internal: no 2N-th root of unity with psi^(N/4) = b");
         std::vector<double> tf(N);
-        uint64_t a = 1;
-        for (int i = 0; i < N; i++) {
-            tf[bitrev(i, logN)] = centred(a, pm[f]);
-            a = mulmod_u64(a, psi, pm[f]);
-        }
+        power_table(tf.data(), psi, pm[f], N, ctx->logN);
         if (pair && (tf[1] != b2[f] || tf[2] != b1[f] || tf[3] != b3[f]))
             return fail(HELM_ERR_STATE, "internal: the first twiddles are not the constants the kernels assume");
-        ctx->n_inv[f] = centred(powmod_u64((uint64_t)N, pm[f] - 2, pm[f]), pm[f]);
-        ctx->two32[f] = centred((1ull << 32) % pm[f], pm[f]);
-        if (!ctx->tw[f]) HIP_TRY(hipMalloc(&ctx->tw[f], sizeof(double) * N));
-        HIP_TRY(hipMemcpy(ctx->tw[f], tf.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        K.n_inv[f] = centred(powmod_u64((uint64_t)N, pm[f] - 2, pm[f]), pm[f]);
+        K.two32[f] = centred((1ull << 32) % pm[f], pm[f]);
+        if (!K.tw[f]) HIP_TRY(hipMalloc(&K.tw[f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(K.tw[f], tf.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     }
-    ctx->p0inv_mod_p1 = centred(powmod_u64(pm[0] % pm[1], pm[1] - 2, pm[1]), pm[1]);
-    ctx->pair = pair;
+    K.p0inv_mod_p1 = centred(powmod_u64(pm[0] % pm[1], pm[1] - 2, pm[1]), pm[1]);
+    K.pair = pair;
     return 0;
 }
 
@@ -2250,20 +2279,15 @@ int setup_generic(helm_si_ctx *ctx)
     return fail(HELM_ERR_STATE, "the generic kernel is not available in the bound-checking build (libhelm_hip_check.so): "
                                 "use the regular library for generic contexts");
 #endif
+    SiKeyState &K = *ctx->keys;
     const helm_si_params &P = ctx->P;
     const int N = P.N, logN = ctx->logN;
-    const uint64_t pm[2] = {F0::P_U64, F1::P_U64}, gen[2] = {F0::GEN, F1::GEN};
-    for (int f = 0; f < 2; f++) { // psi as setup_pair_tables chooses it for pair 0
-        const uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
-        const uint64_t psi_inv = powmod_u64(psi, pm[f] - 2, pm[f]);
+    for (int f = 0; f < 2; f++) {
+        const uint64_t p = si_modulus(0, f);
         std::vector<double> ti(N);
-        uint64_t b = 1;
-        for (int i = 0; i < N; i++) {
-            ti[bitrev(i, logN)] = centred(b, pm[f]);
-            b = mulmod_u64(b, psi_inv, pm[f]);
-        }
-        if (!ctx->twi[f]) HIP_TRY(hipMalloc(&ctx->twi[f], sizeof(double) * N));
-        HIP_TRY(hipMemcpy(ctx->twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        power_table(ti.data(), powmod_u64(si_psi(N, 0, f), p - 2, p), p, N, logN);
+        if (!K.twi[f]) HIP_TRY(hipMalloc(&K.twi[f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(K.twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     }
     const int group = P.grouping_factor > 1 ? P.grouping_factor : 1;
     const void *kern = pbs64_generic_kernel(logN, group);
@@ -2283,24 +2307,68 @@ int setup_generic(helm_si_ctx *ctx)
         return fail(HELM_ERR_INVALID, "k_pbs64_generic: no workgroup of " + std::to_string(Gen64Lds(N, P.k + 1, 1, P.n).bytes) +
                                           " B LDS fits a CU for this shape");
     // digit polynomials per batch: the most (<= gen64_batch) that cost no resident workgroup against one per batch
-    ctx->gen_d = 1;
+    K.gen_d = 1;
     for (int d = gen64_batch(N, P.k, P.pbs_l); d > 1; d--) {
         int nb = 0;
         if (int rc = occupancy(d, nb)) return rc;
         if (nb == nb1) {
-            ctx->gen_d = d;
+            K.gen_d = d;
             break;
         }
     }
-    ctx->gen_lds = Gen64Lds(N, P.k + 1, ctx->gen_d, P.n).bytes;
-    ctx->gen_per_cu = nb1;
-    ctx->gen = true;
+    K.gen_lds = Gen64Lds(N, P.k + 1, K.gen_d, P.n).bytes;
+    K.gen_per_cu = nb1;
+    K.gen = true;
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
         fprintf(stderr, "[helm_si] k_pbs64_generic N=%d k=%d l=%d g=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n",
-                N, P.k, P.pbs_l, group, ctx->gen_d, ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
+                N, P.k, P.pbs_l, group, K.gen_d, K.gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.gen_per_cu);
     }
+    return 0;
+}
+
+// The step bound of a bootstrapping key: the exact integer coefficient of one blind-rotation step is at most B/2 x the largest
+// l1-norm over the key polynomials (taken as centred 64-bit words) that meet in one output column - or, transposed, in one row.
+// A step sums `per_step` polynomials, laid out [...][r][c][N] (classical: the pbs_l (k+1)^2 of one GGSW; the generic multi-bit
+// form: those of the 2^g subsets of a group, whose products it adds up before the CRT lift).  Exact for the key at hand and every
+// input.
+long double key_step_bound(const helm_si_params &P, const uint64_t *bsk_std, size_t steps, size_t per_step)
+{
+    const size_t K1 = P.k + 1;
+    std::vector<long double> l1(per_step);
+    long double worst = 0;
+    for (size_t i = 0; i < steps; i++) {
+        for (size_t q = 0; q < per_step; q++) {
+            const uint64_t *poly = bsk_std + (i * per_step + q) * P.N;
+            long double sum = 0;
+            for (int j = 0; j < P.N; j++) {
+                const int64_t v = (int64_t)poly[j];
+                sum += v < 0 ? -(long double)v : (long double)v;
+            }
+            l1[q] = sum;
+        }
+        for (size_t c = 0; c < K1; c++) {
+            long double by_col = 0, by_row = 0;
+            for (size_t q = 0; q < per_step; q++) {
+                if (q % K1 == c) by_col += l1[q];
+                if ((q / K1) % K1 == c) by_row += l1[q];
+            }
+            worst = std::max(worst, std::max(by_col, by_row));
+        }
+    }
+    return worst * (long double)(1ull << (P.pbs_logB - 1));
+}
+
+// What both key loaders begin with.  A lane refuses a key: the keys are its primary's.  On a primary, nothing in flight - on
+// its own stream or on the stream of any of its lanes - may still read the tables and key buffers a load rewrites.
+int begin_key_load(helm_si_ctx *ctx, const char *what)
+{
+    if (ctx->lane_of)
+        return fail(HELM_ERR_INVALID, std::string(what) + ": this context is a lane; load keys into its primary (every lane sees them)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (helm_si_ctx *lane : ctx->lanes) HIP_TRY(hipStreamSynchronize(lane->stream));
     return 0;
 }
 
@@ -2383,9 +2451,15 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     ctx->n_cus = prop.multiProcessorCount;
     while ((1 << ctx->logN) < P.N) ctx->logN++;
     ctx->delta = (1ull << 63) / (uint64_t)t;
+    ctx->own_keys.reset(new (std::nothrow) SiKeyState());
+    ctx->keys = ctx->own_keys.get();
+    if (!ctx->keys) {
+        delete ctx;
+        return fail(HELM_ERR_OOM, "ctx");
+    }
+    SiKeyState &K = *ctx->keys;
     HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
-    const uint64_t pm[2] = {F0::P_U64, F1::P_U64}, gen[2] = {F0::GEN, F1::GEN};
     const int N = P.N;
     if (int rc = setup_pair_tables(ctx, 0)) {
         (void)helm_si_ctx_destroy(ctx);
@@ -2397,37 +2471,30 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
             return rc;
         }
     }
-    ctx->group = group;
+    K.group = group;
     if (group > 1) { // the 2N powers of psi per field: monomial products in the transform domain
         std::vector<double> pw((size_t)4 * N);
-        for (int f = 0; f < 2; f++) {
-            const uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
-            uint64_t a = 1;
-            for (int i = 0; i < 2 * N; i++) {
-                pw[(size_t)f * 2 * N + i] = centred(a, pm[f]);
-                a = mulmod_u64(a, psi, pm[f]);
-            }
-        }
-        HIP_TRY(hipMalloc(&ctx->psi_pow, pw.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(ctx->psi_pow, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
+        for (int f = 0; f < 2; f++) power_table(pw.data() + (size_t)f * 2 * N, si_psi(N, 0, f), si_modulus(0, f), 2 * N, 0);
+        HIP_TRY(hipMalloc(&K.psi_pow, pw.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(K.psi_pow, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     // eight-wave kernel (split transforms) where it exists: N >= 1024, one or two levels (HELM_SI_SPLIT=0: off)
     static_assert(Pbs64sCfg<11, 2>::BYTES <= 160 * 1024, "k_pbs64s<11, 2> must fit the LDS of a CU");
-    ctx->use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
-    if (const char *v = getenv("HELM_HIP_KS_MFMA")) ctx->ks_mfma = atoi(v);
-    if (const char *v = getenv("HELM_SI_SPLIT")) ctx->use_split = (ctx->use_split && atoi(v) != 0) || group > 1;
-    if (ctx->gen) ctx->use_split = false; // (a generic context reads one key layout, multi-bit too)
-    if (ctx->use_split) {
+    K.use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
+    if (const char *v = getenv("HELM_HIP_KS_MFMA")) K.ks_mfma = atoi(v);
+    if (const char *v = getenv("HELM_SI_SPLIT")) K.use_split = (K.use_split && atoi(v) != 0) || group > 1;
+    if (K.gen) K.use_split = false; // (a generic context reads one key layout, multi-bit too)
+    if (K.use_split) {
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
         for (int f = 0; f < 2; f++) {
-            HIP_TRY(hipMemcpy(full.data(), ctx->tw[f], sizeof(double) * N, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(full.data(), K.tw[f], sizeof(double) * N, hipMemcpyDeviceToHost));
             for (int h = 0; h < 2; h++)
                 for (int m = 1; m < N / 2; m <<= 1)
                     for (int i = 0; i < m; i++) sub[(size_t)(f * 2 + h) * (N / 2) + m + i] = full[2 * m + h * m + i];
         }
-        HIP_TRY(hipMalloc(&ctx->tw_sub, sub.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(ctx->tw_sub, sub.data(), sub.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&K.tw_sub, sub.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(K.tw_sub, sub.data(), sub.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     *out = ctx;
     return 0;
@@ -2438,40 +2505,15 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
     if (!primary || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
     if (primary->lane_of) return fail(HELM_ERR_INVALID, "fork the primary context, not one of its lanes");
-    if (!primary->have_bsk || !primary->have_ksk) return fail(HELM_ERR_STATE, "load the keys before forking a lane");
+    if (!primary->keys->have_bsk || !primary->keys->have_ksk) return fail(HELM_ERR_STATE, "load the keys before forking a lane");
     HIP_TRY(hipSetDevice(primary->device));
     helm_si_ctx *ctx = new (std::nothrow) helm_si_ctx();
     if (!ctx) return fail(HELM_ERR_OOM, "ctx");
     ctx->device = primary->device;
     ctx->lane_of = primary;
+    ctx->keys = primary->keys; // keys, tables and what a later load makes of them: the primary's, not a copy
     ctx->P = primary->P;
     ctx->logN = primary->logN;
-    for (int f = 0; f < 2; f++) {
-        ctx->tw[f] = primary->tw[f];
-        ctx->n_inv[f] = primary->n_inv[f];
-        ctx->two32[f] = primary->two32[f];
-    }
-    ctx->p0inv_mod_p1 = primary->p0inv_mod_p1;
-    ctx->pair = primary->pair;
-    ctx->bsk = primary->bsk;
-    ctx->bsk_split = primary->bsk_split;
-    ctx->tw_sub = primary->tw_sub;
-    ctx->group = primary->group;
-    ctx->expo = primary->expo;
-    ctx->psi_pow = primary->psi_pow;
-    ctx->use_split = primary->use_split;
-    ctx->gen = primary->gen;
-    ctx->gen_d = primary->gen_d;
-    ctx->gen_lds = primary->gen_lds;
-    ctx->gen_per_cu = primary->gen_per_cu;
-    ctx->twi[0] = primary->twi[0];
-    ctx->twi[1] = primary->twi[1];
-    ctx->ksk = primary->ksk;
-    ctx->ksk_planes = primary->ksk_planes;
-    ctx->ks_kchunks = primary->ks_kchunks;
-    ctx->ks_ctiles = primary->ks_ctiles;
-    ctx->ks_mfma = primary->ks_mfma;
-    ctx->have_bsk = ctx->have_ksk = true;
     ctx->delta = primary->delta;
     ctx->n_cus = primary->n_cus;
     ctx->audit_fn = primary->audit_fn; // a lane is audited like its primary
@@ -2482,6 +2524,7 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
         return fail(HELM_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
     }
     ctx->stream = ctx->own_stream;
+    primary->lanes.push_back(ctx);
     *out = ctx;
     return 0;
 }
@@ -2501,20 +2544,11 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx)
         w->d = nullptr;
         w->owner = nullptr;
     }
-    if (!ctx->lane_of) { // a lane borrows its keys and tables
-        (void)hipFree(ctx->tw[0]);
-        (void)hipFree(ctx->tw[1]);
-        (void)hipFree(ctx->twi[0]);
-        (void)hipFree(ctx->twi[1]);
-        (void)hipFree(ctx->bsk);
-        (void)hipFree(ctx->bsk_split);
-        (void)hipFree(ctx->tw_sub);
-        (void)hipFree(ctx->expo);
-        (void)hipFree(ctx->x_own);
-        (void)hipFree(ctx->psi_pow);
-        (void)hipFree(ctx->ksk);
-        (void)hipFree(ctx->ksk_planes);
+    if (ctx->lane_of) {
+        auto &ls = ctx->lane_of->lanes;
+        ls.erase(std::remove(ls.begin(), ls.end(), ctx), ls.end());
     }
+    (void)hipFree(ctx->x_own); // (helm_si_set_exchange_comm; a lane has none)
     for (auto &S : ctx->slots) {
         if (S.host) (void)hipHostFree(S.host);
         if (S.dev) (void)hipFree(S.dev);
@@ -2533,7 +2567,7 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx)
     ctx->d_idx2.release();
     ctx->d_coef.release();
     (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx; // (a primary's key state goes with it: SiKeyState frees its device memory)
     return 0;
 }
 
@@ -2547,13 +2581,13 @@ int helm_si_get_params(const helm_si_ctx *ctx, helm_si_params *out)
 int helm_si_field_bits(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return (ctx->lane_of ? ctx->lane_of : ctx)->pair ? 46 : 49;
+    return ctx->keys->pair ? 46 : 49;
 }
 
 int helm_si_kernel_class(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->gen ? 1 : 0;
+    return ctx->keys->gen ? 1 : 0;
 }
 
 int helm_si_set_stream(helm_si_ctx *ctx, void *hip_stream)
@@ -2595,44 +2629,23 @@ int helm_si_sync(helm_si_ctx *ctx)
 int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t n_words)
 {
     if (!ctx || !bsk_std) return fail(HELM_ERR_INVALID, "null argument");
+    SiKeyState &K = *ctx->keys;
     const helm_si_params &P = ctx->P;
     const size_t K1 = P.k + 1;
-    const size_t n_ggsw = ctx->group > 1 ? (size_t)(P.n / ctx->group) << ctx->group : (size_t)P.n;
-    const size_t polys = n_ggsw * P.pbs_l * K1 * K1;
+    const size_t n_ggsw = K.group > 1 ? (size_t)(P.n / K.group) << K.group : (size_t)P.n;
+    const size_t per_ggsw = (size_t)P.pbs_l * K1 * K1, polys = n_ggsw * per_ggsw;
     if (n_words != polys * P.N)
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->gen && ctx->group > 1) {
-        // The generic kernel's multi-bit form sums the 2^g subsets' products of a group before the CRT lift, so the exact
-        // integer coefficient of a group step is at most B/2 x the largest l1-norm over the key polynomials (taken as centred
-        // 64-bit words) of all subsets and levels that meet in one output column - or, transposed, in one row, as for the
-        // 46-bit pair below.  The creation-time capacity check does not carry the factor 2^g (a worst case no honest key
-        // comes near: a uniformly random key of k = 1, N = 2048, logB = 21, g = 3 stays at 0.71 of the limit); this one is
-        // sufficient for the key at hand and every input.  A key beyond it is refused and the context keeps its state.
-        const size_t per_ggsw = (size_t)P.pbs_l * K1 * K1, subsets = (size_t)1 << ctx->group; // src is [t][S][lev][r][c][N]
-        std::vector<long double> l1(subsets * per_ggsw);
-        long double worst = 0;
-        for (size_t t = 0; t < n_ggsw / subsets; t++) {
-            for (size_t q = 0; q < l1.size(); q++) {
-                const uint64_t *poly = bsk_std + (t * l1.size() + q) * P.N;
-                long double sum = 0;
-                for (int j = 0; j < P.N; j++) {
-                    const int64_t v = (int64_t)poly[j];
-                    sum += v < 0 ? -(long double)v : (long double)v;
-                }
-                l1[q] = sum;
-            }
-            for (size_t c = 0; c < K1; c++) {
-                long double by_col = 0, by_row = 0;
-                for (size_t q = 0; q < l1.size(); q++) {
-                    if (q % K1 == c) by_col += l1[q];
-                    if ((q / K1) % K1 == c) by_row += l1[q];
-                }
-                worst = std::max(worst, std::max(by_col, by_row));
-            }
-        }
-        const long double key_bound = worst * (long double)(1ull << (P.pbs_logB - 1));
+    if (int rc = begin_key_load(ctx, "helm_si_load_bootstrap_key")) return rc;
+    if (K.gen && K.group > 1) {
+        // The generic kernel's multi-bit form sums the 2^g subsets' products of a group before the CRT lift, so a step is the
+        // 2^g GGSWs of a group (src is [t][S][lev][r][c][N]).  The creation-time capacity check does not carry the factor 2^g
+        // (a worst case no honest key comes near: a uniformly random key of k = 1, N = 2048, logB = 21, g = 3 stays at 0.71 of
+        // the limit); this one is sufficient for the key at hand and every input.  A key beyond it is refused and the context
+        // keeps its state.
+        const size_t subsets = (size_t)1 << K.group;
+        const long double key_bound = key_step_bound(P, bsk_std, n_ggsw / subsets, subsets * per_ggsw);
         if (key_bound * 1.001L >= (long double)F0::P * (long double)F1::P / 2) {
             char ratio[32];
             snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / ((long double)F0::P * (long double)F1::P / 2));
@@ -2646,94 +2659,68 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     } t_std; // freed on every return path
     HIP_TRY(hipMalloc(&t_std.p, n_words * sizeof(uint64_t)));
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
-    if (!ctx->bsk && (ctx->group == 1 || ctx->gen)) HIP_TRY(hipMalloc(&ctx->bsk, n_words * 2 * sizeof(double)));
-    if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && ctx->group == 1 && !ctx->lane_of && !ctx->gen) {
+    if (!K.bsk && (K.group == 1 || K.gen)) HIP_TRY(hipMalloc(&K.bsk, n_words * 2 * sizeof(double)));
+    if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && K.group == 1 && !K.gen) {
         // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
-        // every k = 1 set's): the CRT pair follows the key at hand.  An exact product of a blind-rotation step is at most
-        // B/2 x the largest l1-norm over the key polynomials that meet in one output column (or, transposed, in one row) - an
-        // exact guarantee for this key and every input.  Below p p' / 2 of the 46-bit pair (and with digits of at most 17 bits,
-        // whose products with b^3 stay exact doubles): FpJ / FpJ2, whose headroom drops stage 2's modular multiplications and
-        // most recentrings (ntt_fp64.h); otherwise the 49-bit pair.  HELM_SI_FIELD=49 keeps the 49-bit pair.
-        long double worst = 0;
-        const size_t per_step = (size_t)P.pbs_l * K1 * K1; // src is [i][lev][r][c][N]
-        std::vector<long double> l1(per_step);
-        for (size_t i = 0; i < (size_t)P.n; i++) {
-            for (size_t q = 0; q < per_step; q++) {
-                const uint64_t *poly = bsk_std + (i * per_step + q) * P.N;
-                long double sum = 0;
-                for (int j = 0; j < P.N; j++) {
-                    const int64_t v = (int64_t)poly[j];
-                    sum += v < 0 ? -(long double)v : (long double)v;
-                }
-                l1[q] = sum;
-            }
-            for (size_t c = 0; c < K1; c++) {
-                long double by_col = 0, by_row = 0;
-                for (size_t q = 0; q < per_step; q++) {
-                    if (q % K1 == c) by_col += l1[q];
-                    if ((q / K1) % K1 == c) by_row += l1[q];
-                }
-                worst = std::max(worst, std::max(by_col, by_row));
-            }
-        }
-        const long double key_bound = worst * (long double)(1ull << (P.pbs_logB - 1));
+        // every k = 1 set's): the CRT pair follows the key at hand, a step being one GGSW (src is [i][lev][r][c][N]).  With the
+        // step bound below p p' / 2 of the 46-bit pair (and with digits of at most 17 bits, whose products with b^3 stay exact
+        // doubles): FpJ / FpJ2, whose headroom drops stage 2's modular multiplications and most recentrings (ntt_fp64.h);
+        // otherwise the 49-bit pair.  HELM_SI_FIELD=49 keeps the 49-bit pair.
+        const long double key_bound = key_step_bound(P, bsk_std, (size_t)P.n, per_ggsw);
         // (margin 5 %: the CRT's quotient t = (r1 - r0) / p0 mod p1 comes out of mulmod within 0.512 p1, so the lifted value is
         // the exact integer as long as that stays below 0.488 p0 p1)
         int want = (key_bound * 1.05L < (long double)J0::P * (long double)J1::P / 2 && P.pbs_logB <= 18) ? 1 : 0;
         if (const char *v = getenv("HELM_SI_FIELD")) if (atoi(v) == 49) want = 0;
-        if (want != ctx->pair) {
-            HIP_TRY(hipStreamSynchronize(ctx->stream)); // nothing in flight may still read the other pair's tables
-            ctx->have_bsk = false;
+        if (want != K.pair) {
+            K.have_bsk = false;
             if (int rc = setup_pair_tables(ctx, want)) return rc;
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->gen) {
+    if (K.gen) {
         // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
-        const helm_si_ctx *root = ctx->lane_of ? ctx->lane_of : ctx;
 #define GEN64_CONVERT(LN)                                                                                                 \
-    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(G64_THREADS), 0, ctx->stream, d_std, ctx->bsk, \
-                       root->tw[0], root->tw[1], root->n_inv[0], root->n_inv[1], root->two32[0], root->two32[1], (int)K1,      \
-                       P.pbs_l)
+    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(G64_THREADS), 0, ctx->stream, d_std, K.bsk,   \
+                       K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l)
         if (ctx->logN == 8) GEN64_CONVERT(8);
         else if (ctx->logN == 9) GEN64_CONVERT(9);
         else if (ctx->logN == 10) GEN64_CONVERT(10);
         else GEN64_CONVERT(11);
 #undef GEN64_CONVERT
-    } else if (ctx->pair) { // (N = 512 only)
-        hipLaunchKernelGGL((k_bsk_convert64<J0, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk,
-                           ctx->tw[0], ctx->n_inv[0], ctx->two32[0], (int)K1, P.pbs_l, 0);
-        hipLaunchKernelGGL((k_bsk_convert64<J1, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk,
-                           ctx->tw[1], ctx->n_inv[1], ctx->two32[1], (int)K1, P.pbs_l, 1);
+    } else if (K.pair) { // (N = 512 only)
+        hipLaunchKernelGGL((k_bsk_convert64<J0, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[0],
+                           K.n_inv[0], K.two32[0], (int)K1, P.pbs_l, 0);
+        hipLaunchKernelGGL((k_bsk_convert64<J1, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[1],
+                           K.n_inv[1], K.two32[1], (int)K1, P.pbs_l, 1);
     }
 #define CONV(LN)                                                                                                     \
-    if (ctx->logN == LN && ctx->group == 1 && !ctx->pair && !ctx->gen) {                                                                                         \
-        hipLaunchKernelGGL((k_bsk_convert64<F0, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk, \
-                           ctx->tw[0], ctx->n_inv[0], ctx->two32[0], (int)K1, P.pbs_l, 0);                           \
-        hipLaunchKernelGGL((k_bsk_convert64<F1, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, ctx->bsk, \
-                           ctx->tw[1], ctx->n_inv[1], ctx->two32[1], (int)K1, P.pbs_l, 1);                           \
+    if (ctx->logN == LN && K.group == 1 && !K.pair && !K.gen) {                                                      \
+        hipLaunchKernelGGL((k_bsk_convert64<F0, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, \
+                           K.tw[0], K.n_inv[0], K.two32[0], (int)K1, P.pbs_l, 0);                                    \
+        hipLaunchKernelGGL((k_bsk_convert64<F1, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, \
+                           K.tw[1], K.n_inv[1], K.two32[1], (int)K1, P.pbs_l, 1);                                    \
     }
     CONV(9) CONV(10) CONV(11)
 #undef CONV
-    if (ctx->use_split) {
-        if (!ctx->bsk_split) HIP_TRY(hipMalloc(&ctx->bsk_split, n_words * 2 * sizeof(double)));
+    if (K.use_split) {
+        if (!K.bsk_split) HIP_TRY(hipMalloc(&K.bsk_split, n_words * 2 * sizeof(double)));
 #define CONVS(LN)                                                                                                       \
     if (ctx->logN == LN) {                                                                                              \
         hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, d_std,     \
-                           ctx->bsk_split, ctx->tw[0], ctx->tw_sub, ctx->n_inv[0], ctx->two32[0], (int)K1, 0, P.pbs_l);  \
+                           K.bsk_split, K.tw[0], K.tw_sub, K.n_inv[0], K.two32[0], (int)K1, 0, P.pbs_l);                 \
         hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, d_std,     \
-                           ctx->bsk_split, ctx->tw[1], ctx->tw_sub + (size_t)2 * (P.N / 2), ctx->n_inv[1], ctx->two32[1], \
-                           (int)K1, 1, P.pbs_l);                                                                         \
+                           K.bsk_split, K.tw[1], K.tw_sub + (size_t)2 * (P.N / 2), K.n_inv[1], K.two32[1], (int)K1, 1,   \
+                           P.pbs_l);                                                                                     \
     }
         CONVS(10) CONVS(11)
 #undef CONVS
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->group > 1 && !ctx->gen && !ctx->expo) { // (the generic kernel derives its spectrum positions: helm_pbs64_generic.inc)
+    if (K.group > 1 && !K.gen && !K.expo) { // (the generic kernel derives its spectrum positions: helm_pbs64_generic.inc)
         if (int rc = probe_spectrum_positions(ctx)) return rc;
     }
-    ctx->have_bsk = true;
+    K.have_bsk = true;
     return 0;
 }
 
@@ -2745,9 +2732,10 @@ int helm_si_load_keyswitch_key(helm_si_ctx *ctx, const uint64_t *ksk, size_t n_w
     if (n_words != want)
         return fail(HELM_ERR_INVALID, "keyswitching key: expected " + std::to_string(want) + " words, got " +
                                           std::to_string(n_words));
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->ksk) HIP_TRY(hipMalloc(&ctx->ksk, want * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpyAsync(ctx->ksk, ksk, want * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = begin_key_load(ctx, "helm_si_load_keyswitch_key")) return rc;
+    SiKeyState &K = *ctx->keys;
+    if (!K.ksk) HIP_TRY(hipMalloc(&K.ksk, want * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpyAsync(K.ksk, ksk, want * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     {
         // byte planes for the matrix-core keyswitch (levels padded to LP: the padding rows pair zero digits with -128)
@@ -2772,13 +2760,13 @@ int helm_si_load_keyswitch_key(helm_si_ctx *ctx, const uint64_t *ksk, size_t n_w
                                     (int8_t)((int)((w >> (8 * b)) & 255u) - 128);
                         }
                     }
-            if (!ctx->ksk_planes) HIP_TRY(hipMalloc(&ctx->ksk_planes, planes.size()));
-            HIP_TRY(hipMemcpy(ctx->ksk_planes, planes.data(), planes.size(), hipMemcpyHostToDevice));
-            ctx->ks_kchunks = kchunks;
-            ctx->ks_ctiles = ctiles;
+            if (!K.ksk_planes) HIP_TRY(hipMalloc(&K.ksk_planes, planes.size()));
+            HIP_TRY(hipMemcpy(K.ksk_planes, planes.data(), planes.size(), hipMemcpyHostToDevice));
+            K.ks_kchunks = kchunks;
+            K.ks_ctiles = ctiles;
         }
     }
-    ctx->have_ksk = true;
+    K.have_ksk = true;
     return 0;
 }
 
@@ -3258,7 +3246,7 @@ int helm_si_eval_lut_level(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *ar
 int helm_si_keyswitch_batch(helm_si_ctx *ctx, const uint64_t *in_big, uint64_t *out_small, int64_t count)
 {
     if (!ctx || !in_big || !out_small || count < 0) return fail(HELM_ERR_INVALID, "bad argument");
-    if (!ctx->have_ksk) return fail(HELM_ERR_STATE, "keyswitching key not loaded");
+    if (!ctx->keys->have_ksk) return fail(HELM_ERR_STATE, "keyswitching key not loaded");
     if (count == 0) return 0;
     const helm_si_params &P = ctx->P;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -3284,7 +3272,7 @@ int helm_si_pbs_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t
 {
     if (!ctx || !in_small || !luts || !lut_idx || !out_big || count < 0 || n_luts <= 0)
         return fail(HELM_ERR_INVALID, "bad argument");
-    if (!ctx->have_bsk) return fail(HELM_ERR_STATE, "bootstrapping key not loaded");
+    if (!ctx->keys->have_bsk) return fail(HELM_ERR_STATE, "bootstrapping key not loaded");
     if (count == 0) return 0;
     const helm_si_params &P = ctx->P;
     HIP_TRY(hipSetDevice(ctx->device));

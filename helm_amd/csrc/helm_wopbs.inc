@@ -297,9 +297,9 @@ hipError_t launch_convert_ggsw(helm_wop_ctx *ctx, const uint64_t *d_std, double 
 #define CONV(LN)                                                                                                     \
     if (ctx->logN == LN) {                                                                                           \
         hipLaunchKernelGGL((k_bsk_convert64<F0, LN>), dim3((unsigned)polys), dim3(64), 0, W->stream, d_std, d_ntt,    \
-                           W->tw[0], W->n_inv[0], W->two32[0], K1, ctx->P.cbs_l, 0);                                 \
+                           W->keys->tw[0], W->keys->n_inv[0], W->keys->two32[0], K1, ctx->P.cbs_l, 0);               \
         hipLaunchKernelGGL((k_bsk_convert64<F1, LN>), dim3((unsigned)polys), dim3(64), 0, W->stream, d_std, d_ntt,    \
-                           W->tw[1], W->n_inv[1], W->two32[1], K1, ctx->P.cbs_l, 1);                                 \
+                           W->keys->tw[1], W->keys->n_inv[1], W->keys->two32[1], K1, ctx->P.cbs_l, 1);               \
     }
     CONV(9) CONV(10) CONV(11)
 #undef CONV
@@ -309,7 +309,7 @@ hipError_t launch_convert_ggsw(helm_wop_ctx *ctx, const uint64_t *d_std, double 
 // wide batches: digits once for all k+1 keys (the same input rows), then one matrix-core pass per key
 bool pfpks_on_matrix_cores(const helm_wop_ctx *ctx, int64_t count)
 {
-    return ctx->d_pf_planes && ctx->wop->ks_mfma && count >= 64;
+    return ctx->d_pf_planes && ctx->wop->keys->ks_mfma && count >= 64;
 }
 
 hipError_t launch_pfpks_mfma(helm_wop_ctx *ctx, const PfJob *const *jobs_per_key, int64_t count, const uint64_t *big,
@@ -589,7 +589,7 @@ int helm_wop_ctx_create(helm_si_ctx *pbs_side, const helm_wop_params *params, he
         return fail(HELM_ERR_INVALID, "WoP-PBS: circuit-bootstrap levels must be 2 or 3 (built variants), cbs_logB * cbs_l <= 31");
     if (P.pfks_l < 1 || P.pfks_l > 4 || P.pfks_logB < 2 || P.pfks_logB > 30 || P.pfks_logB * P.pfks_l > 63)
         return fail(HELM_ERR_INVALID, "WoP-PBS: bad packing-keyswitch decomposition (pfks_l <= 4, pfks_logB <= 30)");
-    if (pbs_side->gen)
+    if (pbs_side->keys->gen)
         return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context runs the generic bootstrap kernel (helm_si_kernel_class 1); "
                                       "the WoP path is built for the tuned kernels only");
     if (pbs_side->P.k != 1 || P.k != 1)

@@ -120,7 +120,10 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx);
  * per lane; the GPU overlaps their launches).  The reference's unit of parallelism is the level
  * (src/circuit.rs:1057, 1321: par_iter over the gates of a level); lanes add parallelism ACROSS levels for
  * sub-circuits that share no wire.  Fork after the keys are loaded; destroy every lane before its primary.
- * Rows written through one lane must not be touched through another until both have been synchronised. */
+ * Rows written through one lane must not be touched through another until both have been synchronised.
+ * A lane holds its primary's key state - keys, transform tables, CRT pair - not a copy of it: a key loaded into the primary
+ * later is the key every lane launches with from then on (helm_si_field_bits of a lane follows it), and keys are loaded
+ * into the primary only (below). */
 int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **lane_out);
 int helm_si_get_params(const helm_si_ctx *ctx, helm_si_params *out);
 /* The CRT pair of prime fields the bootstrap kernels of this context compute in, as its size class: 49 = 5072^4 + 1 and
@@ -140,6 +143,10 @@ int helm_si_sync(helm_si_ctx *ctx);
  * high-priority one are placed first - the host library gives it to the lane with the longest chain of bootstrap rounds.
  * Synchronises the stream it replaces. */
 int helm_si_set_priority(helm_si_ctx *ctx, int high);
+/* Keys are loaded into a primary context; a lane refuses them with HELM_ERR_INVALID and touches nothing (its keys are its
+ * primary's).  A key may be loaded again, into a primary that has lanes too: the load first synchronises the primary's
+ * stream and the stream of every lane forked from it, then rewrites the shared tables and key buffers, and every lane
+ * sees the new key.  The caller does not load while another thread drives one of the lanes. */
 int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t n_words);
 int helm_si_load_keyswitch_key(helm_si_ctx *ctx, const uint64_t *ksk, size_t n_words);
 

@@ -226,6 +226,63 @@ def test_k_pbs64k_crt_pair_follows_the_loaded_key(monkeypatch):
     sk2.close()
 
 
+def test_lane_follows_keys_reloaded_into_its_primary():
+    """A lane holds its primary's key state, not a copy: a bootstrapping key loaded into the primary after the fork moves
+    the lane's CRT pair with it (46 -> 49 -> 46 bits, the two keys of test_k_pbs64k_crt_pair_follows_the_loaded_key), and the
+    lane's rows are the oracle's under whichever key is loaded; a keyswitching key reloaded into the primary is the one the
+    lane switches with."""
+    from helm_amd._native import hip, hip_check, as_u64p
+    ck = helm_amd.SiClientKey.generate("si_toy_512_k3", seed=5)
+    sk = helm_amd.SiServerKey(ck)
+    lane = sk.fork()
+    assert lane.field_bits() == 46
+    small = sk.keyswitch_batch(ck.encrypt(np.arange(ck.t, dtype=np.uint64)))   # the same inputs for every key and pair
+    got46 = _pbs_rows_bit_exact(ck, lane, oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ck.ksk), 1, small)
+    worst = np.full_like(ck.bsk, 0x7FFFFFFFFFFFFFFF)
+    hip_check(hip.helm_si_load_bootstrap_key(sk._h, as_u64p(worst), worst.size))   # into the PRIMARY
+    assert lane.field_bits() == 49
+    _pbs_rows_bit_exact(ck, lane, oracle.Oracle64(ck.params.as_tuple(), worst, ck.ksk), 2, small)
+    own = np.ascontiguousarray(ck.bsk, dtype=np.uint64).reshape(-1)
+    hip_check(hip.helm_si_load_bootstrap_key(sk._h, as_u64p(own), own.size))
+    assert lane.field_bits() == 46
+    assert np.array_equal(_pbs_rows_bit_exact(ck, lane, oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ck.ksk), 1, small), got46)
+    ksk2 = np.ascontiguousarray(helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6).ksk, dtype=np.uint64).reshape(-1)
+    assert ksk2.size == np.asarray(ck.ksk).size and not np.array_equal(ksk2, np.asarray(ck.ksk).reshape(-1))
+    hip_check(hip.helm_si_load_keyswitch_key(sk._h, as_u64p(ksk2), ksk2.size))
+    cts = ck.encrypt(np.arange(4, dtype=np.uint64) % ck.t)
+    orc2 = oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ksk2)
+    got = lane.keyswitch_batch(cts)
+    for g in range(4):
+        assert np.array_equal(got[g], orc2.keyswitch(cts[g])), f"ciphertext {g}"
+    sk.close()
+
+
+def test_a_lane_refuses_keys():
+    """Keys are loaded into the primary: both loaders refuse a lane with HELM_ERR_INVALID and say where the key goes, and
+    leave primary and lane as they were."""
+    from helm_amd._native import hip, as_u64p
+    ck = helm_amd.SiClientKey.generate("si_toy_512_k3", seed=5)
+    sk = helm_amd.SiServerKey(ck)
+    lane = sk.fork()
+    orc = oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ck.ksk)
+    bits = sk.field_bits()
+    worst = np.full_like(np.ascontiguousarray(ck.bsk, dtype=np.uint64).reshape(-1), 0x7FFFFFFFFFFFFFFF)   # would move the pair
+    ksk2 = np.ascontiguousarray(helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6).ksk, dtype=np.uint64).reshape(-1)
+    HELM_ERR_INVALID = -1
+    assert hip.helm_si_load_bootstrap_key(lane._h, as_u64p(worst), worst.size) == HELM_ERR_INVALID
+    assert "primary" in hip.helm_hip_last_error().decode()
+    assert hip.helm_si_load_keyswitch_key(lane._h, as_u64p(ksk2), ksk2.size) == HELM_ERR_INVALID
+    assert "primary" in hip.helm_hip_last_error().decode()
+    assert sk.field_bits() == bits and lane.field_bits() == bits
+    cts = ck.encrypt(np.arange(ck.t, dtype=np.uint64))
+    for ctx in (sk, lane):
+        small = ctx.keyswitch_batch(cts)
+        for g in range(ck.t):
+            assert np.array_equal(small[g], orc.keyswitch(cts[g])), f"ciphertext {g}"
+        _pbs_rows_bit_exact(ck, ctx, orc, 1, small)
+    sk.close()
+
+
 def test_full_parameter_set_multibit3():
     """The reference's arithmetic-mode set (helm.rs:83, PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_3_KS_PBS: n = 888,
     g = 3, 296 group steps, 310 MB key) at full size: apply_lookup_table rows (keyswitch + multi-bit blind rotation
