@@ -239,6 +239,8 @@ SI_API = {
     "helm_si_lincomb": (C.c_int, [vp, vp, i32p, i64p, i64p, i32p, C.c_int32, C.c_int64]),
     "helm_si_make_lut": (C.c_int, [vp, u64p, u64p]),
     "helm_si_apply_luts": (C.c_int, [vp, vp, i32p, i32p, i32p, C.c_int64, u64p, C.c_int64]),
+    "helm_si_make_many_lut": (C.c_int, [vp, u64p, C.c_int32, u64p]),
+    "helm_si_apply_many_luts": (C.c_int, [vp, vp, i32p, i32p, i32p, C.c_int32, C.c_int64, u64p, C.c_int64]),
     "helm_si_eval_lut_level": (C.c_int, [vp, vp, i32p, i32p, C.c_int32, u64p, i32p, C.c_int64]),
     "helm_si_set_exchange": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int64, SI_EXCHANGE_FN, vp]),
     "helm_si_set_exchange_comm": (C.c_int, [vp, vp, C.c_int64, C.c_int64]),
@@ -250,6 +252,7 @@ SI_API = {
     "helm_si_set_priority": (C.c_int, [vp, C.c_int]),
     "helm_si_keyswitch_batch": (C.c_int, [vp, u64p, u64p, C.c_int64]),
     "helm_si_pbs_batch": (C.c_int, [vp, u64p, u64p, C.c_int64, i32p, u64p, C.c_int64]),
+    "helm_si_pbs_many_batch": (C.c_int, [vp, u64p, u64p, C.c_int64, i32p, C.c_int32, u64p, C.c_int64]),
     "helm_si_timing_enable": (C.c_int, [vp, C.c_int]),
     "helm_si_get_timing": (C.c_int, [vp, C.POINTER(Timing), C.c_int]),
 }

@@ -338,14 +338,17 @@ __global__ __launch_bounds__(G64_THREADS) void k_pbs64_generic(const Pbs64Job *_
         __syncthreads();
     }
 
-    // ---- sample extract (coefficient 0) ----------------------------------------------------
-    uint64_t *ob = out + (size_t)job.out_row * ((size_t)K * N + 1);
-    for (int idx = tid; idx < K * N; idx += G64_THREADS) {
-        const int r = idx >> LOGN, t = idx & (N - 1);
-        // out[r N + t] = (t == 0) ? A_r[0] : -A_r[N - t]
-        ob[idx] = t == 0 ? acc[(size_t)r * N] : 0ull - acc[(size_t)r * N + N - t];
+    // ---- sample extract: every output of the job (extract_put; pad = 0: the one at coefficient 0) ----------
+    const int n_out = pbs64_job_outputs(job.pad), ls = pbs64_job_log_stride(job.pad);
+    for (int x = 0; x < n_out; x++) {
+        const int h = x << ls;
+        uint64_t *ob = out + (size_t)(job.out_row + x) * ((size_t)K * N + 1);
+        for (int idx = tid; idx < K * N; idx += G64_THREADS) {
+            const int r = idx >> LOGN, j = idx & (N - 1);
+            extract_put(ob + (size_t)r * N, N, h, j, acc[idx]);
+        }
+        if (tid == 0) ob[(size_t)K * N] = acc[(size_t)K * N + h]; // body = B[h]
     }
-    if (tid == 0) ob[(size_t)K * N] = acc[(size_t)K * N]; // body = B[0]
 }
 
 // One workgroup per key polynomial: standard-domain u64 coefficients (taken as signed) -> both fields -> forward transform ->

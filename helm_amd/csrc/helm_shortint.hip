@@ -94,8 +94,12 @@ struct Pbs64Job {
     int32_t in_row;  // row of the small-LWE buffer (n+1 words)
     int32_t lut;     // row of the look-up-table buffer (N words)
     int32_t out_row; // row of the destination table (k*N+1 words)
-    int32_t pad;
+    int32_t pad;     // programmable bootstrap: 0 = one output, sample extract at coefficient 0; many-LUT (helm_si_apply_many_luts):
+                     // (n_out - 1) | log2(stride) << 16 - output x < n_out is the extract at coefficient x * stride, written to
+                     // row out_row + x.  Modes 1 and 2 of k_pbs64 (the WoP-PBS path): the index of the job's key.
 };
+__host__ __device__ __forceinline__ int pbs64_job_outputs(int32_t pad) { return (pad & 0xFFFF) + 1; }
+__host__ __device__ __forceinline__ int pbs64_job_log_stride(int32_t pad) { return pad >> 16; }
 
 struct Ks64Job {
     int32_t in_row;  // row of the big table
@@ -115,6 +119,40 @@ __device__ __forceinline__ int64_t to_int64(double v)
     const uint32_t lo = (uint32_t)__double2loint(m);
     const int32_t hi = (int32_t)((uint32_t)__double2hiint(m) & 0xFFFFFu) - 0x80000;
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | lo);
+}
+
+// Sample extract at coefficient h of the accumulator (A_0 .. A_{k-1}, B): mask word r N + u is A_r[h - u] for u <= h and
+// -A_r[N + h - u] for u > h, the body is B[h].  Seen from accumulator coefficient j of polynomial r: it goes to word
+// u = (h - j) mod N, with its own sign for j <= h and negated for j > h - a permutation of the row's words for every h, so a
+// wave that holds a set of coefficients writes as many words for any h (h = 0: word 0 is A_r[0], word N - j is -A_r[j]).
+__device__ __forceinline__ void extract_put(uint64_t *__restrict__ row_r, int N, int h, int j, uint64_t v)
+{
+    row_r[(h - j) & (N - 1)] = j <= h ? v : 0ull - v;
+}
+
+// The epilogue of the tuned bootstrap kernels: every output of the job (pbs64_job_outputs(pad), pad = 0: the one at
+// coefficient 0).  A mask wave (p < K) holds slots s0 .. s0 + CNT - 1 of polynomial p (coefficient jA(lane, slot)); one lane
+// of the workgroup (`body`) writes B[h].  acc_at(j): coefficient j of this wave's polynomial, complete in LDS since the
+// blind rotation's final barrier.
+template <typename G, int K, int CNT, typename ACC>
+__device__ __forceinline__ void sample_extract_outputs(uint64_t *__restrict__ out, int32_t out_row, int32_t pad, int p, int s0,
+                                                       bool body, int lane, const ACC &acc_at)
+{
+    constexpr int N = G::N;
+    const int n_out = pbs64_job_outputs(pad), ls = pbs64_job_log_stride(pad);
+    for (int x = 0; x < n_out; x++) {
+        const int h = x << ls;
+        uint64_t *ob = out + (size_t)(out_row + x) * ((size_t)K * N + 1);
+        if (p < K) {
+#pragma unroll
+            for (int e = 0; e < CNT; e++) {
+                const int j = G::jA(lane, s0 + e);
+                extract_put(ob + (size_t)p * N, N, h, j, acc_at(j));
+            }
+        } else if (body) {
+            ob[K * N] = acc_at(h);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -367,19 +405,9 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64(const Pbs64Job *__restr
         }
         return;
     }
-    // ---- sample extract (coefficient 0); wave (p, f) writes its half of the slots ------
-    uint64_t *ob = out + (size_t)job.out_row * ((size_t)K * N + 1);
-    if (p < K) {
-#pragma unroll
-        for (int e = 0; e < H; e++) {
-            const int j = G::jA(lane, f * H + e);
-            const uint64_t v = acc_p[j];
-            if (j == 0) ob[p * N] = v;
-            else ob[p * N + (N - j)] = 0ull - v;
-        }
-    } else if (f == 0 && lane == 0) {
-        ob[K * N] = acc_p[0];
-    }
+    // ---- sample extract; wave (p, f) writes its half of the slots (MODE 1: pad is the key index, one output) ------
+    sample_extract_outputs<G, K, H>(out, job.out_row, MODE == 0 ? job.pad : 0, p, f * H, f == 0 && lane == 0, lane,
+                                    [&](int j) { return acc_p[j]; });
 }
 
 // ------------------------------------------------------------------------------------
@@ -620,22 +648,11 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
     __syncthreads();
     if (f == 0) pbs64k_body<C, FA, FA, FB>(smem, bsk, n, logB, p0inv_mod_p1, p, 0, lane);
     else pbs64k_body<C, FB, FA, FB>(smem, bsk, n, logB, p0inv_mod_p1, p, 1, lane);
-    // ---- sample extract (coefficient 0); wave (p, f) writes its half of the slots ------
+    // ---- sample extract; wave (p, f) writes its half of the slots ------
     const uint64_t *acc_p = ACC + (size_t)p * C::ACC_LEN;
     const uint64_t *acc_xp = reinterpret_cast<const uint64_t *>(smem + C::X_OFF);
     auto acc_at = [&](int j) { return C::ACC_X ? acc_xp[C::acc_x(p, j)] : acc_p[j]; };
-    uint64_t *ob = out + (size_t)job.out_row * ((size_t)K * N + 1);
-    if (p < K) {
-#pragma unroll
-        for (int e = 0; e < H; e++) {
-            const int j = G::jA(lane, f * H + e);
-            const uint64_t v = acc_at(j);
-            if (j == 0) ob[p * N] = v;
-            else ob[p * N + (N - j)] = 0ull - v;
-        }
-    } else if (f == 0 && lane == 0) {
-        ob[K * N] = acc_at(0);
-    }
+    sample_extract_outputs<G, K, H>(out, job.out_row, job.pad, p, f * H, f == 0 && lane == 0, lane, acc_at);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1177,20 +1194,11 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64s(const Pbs64Job *__rest
     }
 #undef HELM_SI_BODY
 
-    uint64_t *ob = out + (size_t)job.out_row * ((size_t)K * N + 1);
+    // ---- sample extract; wave (p, f, h) writes its quarter of the slots ------
     const uint64_t *acc_p = ACC + (size_t)p * N;
     const int quarter = f * 2 + h;
-    if (p < K) {
-#pragma unroll
-        for (int u = 0; u < E / 4; u++) {
-            const int j = G::jA(lane, quarter * (E / 4) + u);
-            const uint64_t v = acc_p[j];
-            if (j == 0) ob[p * N] = v;
-            else ob[p * N + (N - j)] = 0ull - v;
-        }
-    } else if (w == K * 4 && lane == 0) {
-        ob[K * N] = acc_p[0];
-    }
+    sample_extract_outputs<G, K, E / 4>(out, job.out_row, job.pad, p, quarter * (E / 4), w == K * 4 && lane == 0, lane,
+                                        [&](int j) { return acc_p[j]; });
 }
 
 // key conversion for k_pbs64s: standard-domain u64 -> field F, stage 1 + half transform h, times N^-1:
@@ -2099,6 +2107,38 @@ int apply_luts_device(helm_si_ctx *ctx, const uint64_t *src, uint64_t *dst, cons
     ctx->tacc.pbs_launches++;
     ctx->tacc.pbs_count += count;
     return 0;
+}
+
+// Many-LUT: n functions share one blind rotation in M = the power of two >= n chunks of N/M coefficients (M <= t = message x
+// carry, so that a chunk holds whole boxes).  -> M and the `pad` of the bootstrap jobs (Pbs64Job).
+int many_lut_shape(const helm_si_ctx *ctx, int64_t n, int *M_out, int32_t *pad_out)
+{
+    const int t = ctx->P.message_modulus * ctx->P.carry_modulus;
+    if (n < 1 || n > t) // (t is a power of two: the power of two >= n exceeds t exactly when n does)
+        return fail(HELM_ERR_INVALID, "many-LUT: " + std::to_string(n) + " functions, this set holds 1 .. " + std::to_string(t));
+    int logM = 0;
+    while ((1 << logM) < n) logM++;
+    if (M_out) *M_out = 1 << logM;
+    if (pad_out) *pad_out = (int32_t)(n - 1) | (int32_t)(ctx->logN - logM) << 16;
+    return 0;
+}
+
+// keyswitch + one blind rotation per job + n_out sample extracts into rows g n_out + x of the stage buffer
+int apply_many_luts_stage(helm_si_ctx *ctx, const uint64_t *src, const int32_t *in_idx, const int32_t *lut_idx, int32_t n_out,
+                          int32_t pad, int64_t count, const uint64_t *luts, int64_t n_luts)
+{
+    const size_t brow = (size_t)ctx->P.k * ctx->P.N + 1;
+    std::vector<Ks64Job> ks((size_t)count);
+    std::vector<Pbs64Job> pbs((size_t)count);
+    for (int64_t g = 0; g < count; g++) {
+        ks[(size_t)g] = Ks64Job{in_idx[g], (int32_t)g};
+        pbs[(size_t)g] = Pbs64Job{(int32_t)g, lut_idx[g], (int32_t)(g * n_out), pad};
+    }
+    if (ctx->d_stage.cap < (size_t)count * n_out * brow) {
+        if (int rc = drain(ctx)) return rc; // growing the staging area frees the old one
+        if (ctx->d_stage.ensure((size_t)count * n_out * brow)) return fail(HELM_ERR_OOM, "staging");
+    }
+    return apply_luts_device(ctx, src, ctx->d_stage.p, ks, pbs, luts, n_luts);
 }
 
 // Multi-bit: which power of psi is the evaluation point of each spectrum position, in the order the key
@@ -3047,6 +3087,88 @@ int helm_si_apply_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx
     return 0;
 }
 
+int helm_si_make_many_lut(const helm_si_ctx *ctx, const uint64_t *f_values, int32_t n_funcs, uint64_t *tv)
+{
+    if (!ctx || !f_values || !tv) return fail(HELM_ERR_INVALID, "null argument");
+    int M = 1;
+    if (int rc = many_lut_shape(ctx, n_funcs, &M, nullptr)) return rc;
+    const int N = ctx->P.N, t = ctx->P.message_modulus * ctx->P.carry_modulus;
+    const int box = N / t, half = box / 2, per = t / M; // function i: boxes i per .. i per + per - 1, chunks >= n_funcs zero
+    std::vector<uint64_t> acc((size_t)N, 0);
+    for (int i = 0; i < n_funcs; i++)
+        for (int v = 0; v < per; v++)
+            for (int j = 0; j < box; j++) acc[((size_t)i * per + v) * box + j] = f_values[(size_t)i * per + v] * ctx->delta;
+    for (int j = 0; j < half; j++) acc[(size_t)j] = 0ull - acc[(size_t)j];
+    for (int j = 0; j < N; j++) tv[j] = acc[(size_t)((j + half) % N)]; // rotate_left(half)
+    return 0;
+}
+
+int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
+                            const int32_t *out_idx, int32_t n_out, int64_t count, const uint64_t *luts, int64_t n_luts)
+{
+    if (!ctx || !w || !in_idx || !lut_idx || !out_idx || !luts || count < 0 || n_luts <= 0)
+        return fail(HELM_ERR_INVALID, "bad argument");
+    if (!owns(ctx, w)) return fail(HELM_ERR_STATE, "table belongs to another context");
+    int32_t pad = 0;
+    if (int rc = many_lut_shape(ctx, n_out, nullptr, &pad)) return rc;
+    if (count == 0) return 0;
+    if (count * n_out > INT32_MAX) return fail(HELM_ERR_INVALID, "many-LUT: count * n_out exceeds the row index range");
+    const int64_t n_rows = count * n_out;
+    if (int rc = check_rows(w, in_idx, count, false)) return rc;
+    if (int rc = check_rows(w, out_idx, n_rows, true)) return rc;
+    for (int64_t g = 0; g < count; g++)
+        if (lut_idx[g] < 0 || lut_idx[g] >= n_luts) return fail(HELM_ERR_INVALID, "lut_idx out of range");
+    // the scatter list: stage row g n_out + x -> table row out_idx[g n_out + x]; skipped outputs (-1) are not on it
+    std::vector<int32_t> s_row, d_row;
+    for (int64_t q = 0; q < n_rows; q++)
+        if (out_idx[q] >= 0) {
+            s_row.push_back((int32_t)q);
+            d_row.push_back(out_idx[q]);
+        }
+    {
+        std::vector<int32_t> sorted(d_row);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end())
+            return fail(HELM_ERR_INVALID, "many-LUT: two outputs of the call name row " + std::to_string(*dup));
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<uint64_t> audit_in, audit_out;
+    if (ctx->audit_fn)
+        if (int rc = audit_fetch(ctx, w, in_idx, count, audit_in)) return rc;
+    // not sharded under an exchange: every rank computes the whole batch (helm_shortint.h).  Every keyswitch finishes
+    // (kernel boundary) before the scatter writes an output row: the bootstraps write the stage buffer only.
+    if (int rc = apply_many_luts_stage(ctx, w->d, in_idx, lut_idx, n_out, pad, count, luts, n_luts)) return rc;
+    if (!d_row.empty()) {
+        helm_si_ctx::CallSlot *S = nullptr;
+        if (int rc = slot_begin(ctx, 2 * d_row.size() * sizeof(int32_t), &S)) return rc;
+        const int32_t *d_src = slot_put(*S, s_row.data(), s_row.size());
+        const int32_t *d_dst = slot_put(*S, d_row.data(), d_row.size());
+        if (int rc = slot_flush(ctx, *S)) return rc;
+        {
+            Timed t(ctx, &ctx->ev_lin);
+            hipLaunchKernelGGL(k_rows64, dim3((unsigned)d_row.size()), dim3(256), 0, ctx->stream, ctx->d_stage.p, d_src, w->d,
+                               d_dst, ctx->P.k * ctx->P.N);
+            HIP_TRY(hipGetLastError());
+        }
+        if (int rc = slot_end(ctx, *S)) return rc;
+    }
+    if (!ctx->audit_fn) return 0;
+    if (int rc = audit_fetch(ctx, w, out_idx, n_rows, audit_out)) return rc;
+    helm_si_audit_record rec{};
+    rec.kind = 2;
+    rec.terms = n_out;
+    rec.count = count;
+    rec.n_luts = n_luts;
+    rec.in_rows = audit_in.data();
+    rec.out_rows = audit_out.data();
+    rec.lut_idx = lut_idx;
+    rec.luts = luts;
+    if (int rc = ctx->audit_fn(ctx->audit_user, &rec))
+        return fail(HELM_ERR_STATE, "helm_si_apply_many_luts: the audit callback rejected the batch (" + std::to_string(rc) + ")");
+    return 0;
+}
+
 int helm_si_set_exchange(helm_si_ctx *ctx, int32_t rank, int32_t world, int64_t min_batch, void *stage_dev,
                          void *gather_dev, int64_t capacity_rows, helm_si_exchange_fn fn, void *user)
 {
@@ -3296,6 +3418,41 @@ int helm_si_pbs_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t
     ctx->tacc.pbs_count += count;
     HIP_TRY(hipMemcpyAsync(out_big, ctx->d_stage.p, (size_t)count * brow * sizeof(uint64_t), hipMemcpyDeviceToHost,
                            ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int helm_si_pbs_many_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t *luts, int64_t n_luts,
+                           const int32_t *lut_idx, int32_t n_out, uint64_t *out_big, int64_t count)
+{
+    if (!ctx || !in_small || !luts || !lut_idx || !out_big || count < 0 || n_luts <= 0)
+        return fail(HELM_ERR_INVALID, "bad argument");
+    int32_t pad = 0;
+    if (int rc = many_lut_shape(ctx, n_out, nullptr, &pad)) return rc;
+    if (!ctx->keys->have_bsk) return fail(HELM_ERR_STATE, "bootstrapping key not loaded");
+    if (count == 0) return 0;
+    if (count * n_out > INT32_MAX) return fail(HELM_ERR_INVALID, "many-LUT: count * n_out exceeds the row index range");
+    const helm_si_params &P = ctx->P;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = drain(ctx)) return rc;
+    const size_t row = (size_t)P.n + 1, brow = (size_t)P.k * P.N + 1, n_rows = (size_t)count * n_out;
+    std::vector<Pbs64Job> jobs((size_t)count);
+    for (int64_t g = 0; g < count; g++) {
+        if (lut_idx[g] < 0 || lut_idx[g] >= n_luts) return fail(HELM_ERR_INVALID, "lut_idx out of range");
+        jobs[(size_t)g] = Pbs64Job{(int32_t)g, lut_idx[g], (int32_t)(g * n_out), pad};
+    }
+    if (int rc = upload(ctx, ctx->d_small, in_small, (size_t)count * row)) return rc;
+    ctx->luts_words = 0; // the resident tables of the call slots are overwritten
+    if (int rc = upload(ctx, ctx->d_luts, luts, (size_t)n_luts * P.N)) return rc;
+    if (int rc = upload(ctx, ctx->d_pbs, jobs.data(), jobs.size())) return rc;
+    if (ctx->d_stage.ensure(n_rows * brow)) return fail(HELM_ERR_OOM, "staging");
+    {
+        Timed t(ctx, &ctx->ev_pbs);
+        HIP_TRY(launch_pbs64(ctx, ctx->d_pbs.p, count, ctx->d_small.p, ctx->d_luts.p, ctx->d_stage.p));
+    }
+    ctx->tacc.pbs_launches++;
+    ctx->tacc.pbs_count += count;
+    HIP_TRY(hipMemcpyAsync(out_big, ctx->d_stage.p, n_rows * brow * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -203,7 +203,8 @@ class SiServerKey:
         """helm_si_set_audit: while set, every linear step and every look-up batch of this key - LUT levels, the radix
         operators of arithmetic mode - hands `fn` a dict with its operand rows (read before the call ran), its result rows
         and its arguments: kind "luts" -> in_rows, out_rows, lut_idx, luts; kind "lincomb" -> in_rows [count, terms, row],
-        out_rows, in_idx, coef, const_add (or None).  fn returning False (or raising) fails the call.  fn = None: off.
+        out_rows, in_idx, coef, const_add (or None); kind "many_luts" (helm_si_apply_many_luts,
+        record kind 2) -> n_out, in_rows, out_rows [count, n_out, row], lut_idx, luts.  fn returning False (or raising) fails the call.  fn = None: off.
         Set it BEFORE the evaluators fork their lanes."""
         if fn is None:
             hip_check(hip.helm_si_set_audit(self._h, nv.SI_AUDIT_FN(0), None))
@@ -217,7 +218,12 @@ class SiServerKey:
                 r = recp.contents
                 cnt = int(r.count)
                 arr = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).astype(dt, copy=True)
-                if r.kind == 0:
+                if r.kind == 2:
+                    t = int(r.terms)
+                    rec = {"kind": "many_luts", "n_out": t, "in_rows": arr(r.in_rows, (cnt, brow), np.uint64),
+                           "out_rows": arr(r.out_rows, (cnt, t, brow), np.uint64), "lut_idx": arr(r.lut_idx, (cnt,), np.int32),
+                           "luts": arr(r.luts, (int(r.n_luts), N), np.uint64), "raw_kind": 2, "terms": t}
+                elif r.kind == 0:
                     rec = {"kind": "luts", "in_rows": arr(r.in_rows, (cnt, brow), np.uint64), "out_rows": arr(r.out_rows, (cnt, brow), np.uint64),
                            "lut_idx": arr(r.lut_idx, (cnt,), np.int32), "luts": arr(r.luts, (int(r.n_luts), N), np.uint64)}
                 else:
@@ -301,6 +307,21 @@ class SiServerKey:
         hip_check(hip.helm_si_make_lut(self._h, nv.as_u64p(vals), nv.as_u64p(out)))
         return out
 
+    def many_lut_chunks(self, n):
+        """M of a many-LUT table of n functions: the smallest power of two >= n (each function takes inputs below t // M)."""
+        return 1 << max(0, int(n) - 1).bit_length()
+
+    def make_many_lut(self, fs):
+        """helm_si_make_many_lut: ONE test polynomial for the list of callables `fs`, each over range(t // M) with
+        M = many_lut_chunks(len(fs)); SiWires.apply_many_luts / pbs_many_batch then evaluate all of them with one blind
+        rotation.  The input must be below t // M (the caller's responsibility, as a ciphertext's degree in tfhe)."""
+        t = self.params.message_modulus * self.params.carry_modulus
+        per = max(1, t // self.many_lut_chunks(len(fs)))
+        vals = np.array([[f(v) for v in range(per)] for f in fs], dtype=np.uint64).reshape(-1)
+        out = np.zeros(self.params.N, dtype=np.uint64)
+        hip_check(hip.helm_si_make_many_lut(self._h, nv.as_u64p(vals), len(fs), nv.as_u64p(out)))
+        return out
+
     def keyswitch_batch(self, big):
         p = self.params
         big = np.ascontiguousarray(big, dtype=np.uint64).reshape(-1, self.dim + 1)
@@ -318,6 +339,19 @@ class SiServerKey:
         out = np.zeros((len(small), self.dim + 1), dtype=np.uint64)
         hip_check(hip.helm_si_pbs_batch(self._h, nv.as_u64p(small), nv.as_u64p(luts), len(luts), nv.as_i32p(lut_idx),
                                         nv.as_u64p(out), len(small)))
+        return out
+
+    def pbs_many_batch(self, small, luts, n_out, lut_idx=None):
+        """helm_si_pbs_many_batch: one blind rotation per row of `small`, n_out sample extracts -> [count, n_out, k*N+1]."""
+        p = self.params
+        small = np.ascontiguousarray(small, dtype=np.uint64).reshape(-1, p.n + 1)
+        luts = np.ascontiguousarray(luts, dtype=np.uint64).reshape(-1, p.N)
+        if lut_idx is None:
+            lut_idx = np.zeros(len(small), dtype=np.int32)
+        lut_idx = np.ascontiguousarray(lut_idx, dtype=np.int32)
+        out = np.zeros((len(small), max(int(n_out), 0), self.dim + 1), dtype=np.uint64)
+        hip_check(hip.helm_si_pbs_many_batch(self._h, nv.as_u64p(small), nv.as_u64p(luts), len(luts), nv.as_i32p(lut_idx),
+                                             int(n_out), nv.as_u64p(out), len(small)))
         return out
 
     def timing_enable(self, on=True):
@@ -387,6 +421,22 @@ class SiWires:
         lut_idx = np.ascontiguousarray(lut_idx, dtype=np.int32)
         hip_check(hip.helm_si_apply_luts(self.sk._h, self._h, nv.as_i32p(in_idx), nv.as_i32p(lut_idx),
                                          nv.as_i32p(out_idx), len(in_idx), nv.as_u64p(luts), len(luts)))
+
+    def apply_many_luts(self, in_idx, luts, out_idx, lut_idx=None):
+        """helm_si_apply_many_luts: out_idx is [count, n_out]; row out_idx[g, x] = output x of the one blind rotation of
+        row in_idx[g] with table lut_idx[g] (-1: that output is skipped)."""
+        in_idx = np.ascontiguousarray(in_idx, dtype=np.int32)
+        out_idx = np.ascontiguousarray(out_idx, dtype=np.int32)
+        if out_idx.ndim != 2:
+            out_idx = out_idx.reshape(len(in_idx), -1)
+        assert len(out_idx) == len(in_idx)
+        luts = np.ascontiguousarray(luts, dtype=np.uint64).reshape(-1, self.sk.params.N)
+        if lut_idx is None:
+            lut_idx = np.zeros(len(in_idx), dtype=np.int32)
+        lut_idx = np.ascontiguousarray(lut_idx, dtype=np.int32)
+        hip_check(hip.helm_si_apply_many_luts(self.sk._h, self._h, nv.as_i32p(in_idx), nv.as_i32p(lut_idx),
+                                              nv.as_i32p(out_idx), out_idx.shape[1], len(in_idx), nv.as_u64p(luts),
+                                              len(luts)))
 
     def eval_lut_level(self, arity, in_idx, table, out_idx):
         """gates::lut() for a level: in_idx [count, max_in] (-1 padded), table = truth tables as bit masks."""

@@ -180,6 +180,30 @@ int helm_si_make_lut(const helm_si_ctx *ctx, const uint64_t *f_values, uint64_t 
 int helm_si_apply_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
                        const int32_t *out_idx, int64_t count, const uint64_t *luts, int64_t n_luts);
 
+/* Many-LUT bootstrap: several functions of one input from ONE blind rotation (later tfhe releases:
+ * ServerKey::generate_many_lookup_table / apply_many_lookup_table).  With t = message_modulus * carry_modulus, box = N / t,
+ * n_funcs >= 1 and M = the smallest power of two >= n_funcs (M <= t), the test polynomial holds function i in chunk i of
+ * N / M coefficients: before the rotation, coefficient (i * (t / M) + v) * box + j is f_i(v) * delta for i < n_funcs,
+ * v < t / M, j < box; chunks i >= n_funcs are zero; then, as helm_si_make_lut, the first box / 2 coefficients are negated
+ * and the polynomial is rotated left by box / 2.  f_values is [n_funcs][t / M].  n_funcs = 1 gives helm_si_make_lut's
+ * polynomial word for word.  n_funcs < 1, M > t or a null pointer: HELM_ERR_INVALID.
+ * INPUT BOUND: such a table answers correctly only for an input v < t / M (as a ciphertext's degree in tfhe: a 2+2-bit
+ * block after one addition holds at most 6 < 8 = t / 2, so message v % 4 and carry v / 4 are two functions of one
+ * rotation).  The bound is the caller's responsibility; nothing checks it on the device. */
+int helm_si_make_many_lut(const helm_si_ctx *ctx, const uint64_t *f_values, int32_t n_funcs, uint64_t *test_poly_out);
+/* For each g < count: keyswitch row in_idx[g], ONE blind rotation with table lut_idx[g], then n_out sample extracts: output
+ * x < n_out is the extract at coefficient h = x * N / M of the rotated accumulator (A_0 .. A_{k-1}, B), M = the power of two
+ * >= n_out - mask word r * N + u is A_r[h - u] for u <= h and -A_r[N + h - u] for u > h, the body is B[h] (h = 0: what
+ * helm_si_apply_luts extracts) - and is written to row out_idx[g * n_out + x]; -1 there skips that output.  As
+ * helm_si_apply_luts: every keyswitch finishes before any output row is written (an output may be an input row), row
+ * indices are range-checked, lanes work alike, and n_out = 1 gives the rows of helm_si_apply_luts.  Two outputs of one call
+ * naming the same row, n_out < 1 or M > t: HELM_ERR_INVALID.  helm_si_get_timing counts blind rotations: pbs_count rises by
+ * count, not by count * n_out.  Under an exchange (helm_si_set_exchange*) a many-LUT batch is NOT sharded: every rank
+ * computes the whole batch - tables are replicated and the arithmetic is exact, so the ranks' tables stay identical - and no
+ * collective is issued.  The host library's operators do not use this call (yet): they keep to helm_si_apply_luts. */
+int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
+                            const int32_t *out_idx, int32_t n_out, int64_t count, const uint64_t *luts, int64_t n_luts);
+
 /* One netlist level of LUT gates = gates::lut() per gate (gates.rs:754-785):
  *   arity 1  : table all zero -> copy, else -> negation (smart_neg)
  *   arity 2  : bivariate f(x,y) = table[(x&1)*2 + (y&1)]
@@ -220,7 +244,7 @@ int helm_si_exchange_stats(const helm_si_ctx *ctx, int64_t *batches, int64_t *ro
  * that shard keep to the primary context (the host library's ArithCircuit does not fork its default lane then). */
 int helm_si_exchange_world(const helm_si_ctx *ctx);
 
-/* Audit (tracing): while a callback is set, every helm_si_lincomb() and helm_si_apply_luts() call - and with them everything
+/* Audit (tracing): while a callback is set, every helm_si_lincomb(), helm_si_apply_luts() and helm_si_apply_many_luts() call - and with them everything
  * built on the two: helm_si_eval_lut_level(), the LUT-mode and arithmetic-mode evaluators of the host library - copies its
  * operand rows (read BEFORE the call runs: a batch may work in place) and its result rows to the host and hands them to
  * `fn` together with the call's arguments; a non-zero return fails the call.  How tests/test_gpu_audit.py checks whole
@@ -228,8 +252,10 @@ int helm_si_exchange_world(const helm_si_ctx *ctx);
  * oracle's on the GPU's own inputs, hence every wire).  Slow by construction (two synchronous copies per call); lanes
  * forked AFTER this call inherit it.  fn = NULL switches it off. */
 typedef struct {
-    int32_t kind;             /* 0 = helm_si_apply_luts, 1 = helm_si_lincomb */
-    int32_t terms;            /* lincomb: operands per output */
+    int32_t kind;             /* 0 = helm_si_apply_luts, 1 = helm_si_lincomb, 2 = helm_si_apply_many_luts (fields as kind 0, but
+                               * terms = n_out and out_rows = count * n_out rows, output x of ciphertext g at row g * n_out + x,
+                               * a skipped output: zeros) */
+    int32_t terms;            /* lincomb: operands per output; apply_many_luts: n_out */
     int64_t count, n_luts;
     const uint64_t *in_rows;  /* apply_luts: count rows of k*N+1 words; lincomb: count * terms (a skipped operand: zeros) */
     const uint64_t *out_rows; /* count rows */
@@ -256,6 +282,10 @@ int64_t helm_si_round_capacity(helm_si_ctx *ctx);
 int helm_si_keyswitch_batch(helm_si_ctx *ctx, const uint64_t *in_big, uint64_t *out_small, int64_t count);
 int helm_si_pbs_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t *luts, int64_t n_luts,
                       const int32_t *lut_idx, uint64_t *out_big, int64_t count);
+/* The many-LUT primitive (helm_si_apply_many_luts without the keyswitch): out_big is count * n_out rows, output x of
+ * ciphertext g at row g * n_out + x. */
+int helm_si_pbs_many_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t *luts, int64_t n_luts,
+                           const int32_t *lut_idx, int32_t n_out, uint64_t *out_big, int64_t count);
 
 typedef struct {
     double pbs_ms, ks_ms, linear_ms;

@@ -215,6 +215,13 @@ extern "C" {
     pub fn helm_si_wires_set_trivial(ctx: *mut helm_si_ctx, w: *mut helm_si_wires, idx: *const i32, value: *const u64, count: i64) -> c_int;
     pub fn helm_si_eval_lut_level(ctx: *mut helm_si_ctx, w: *mut helm_si_wires, arity: *const i32, in_idx: *const i32, max_in: c_int,
                                   table: *const u64, out_idx: *const i32, count: i64) -> c_int;
+    // many-LUT bootstrap (generate_many_lookup_table / apply_many_lookup_table of later tfhe releases): n_out functions of
+    // one input, below t / M, from one blind rotation
+    pub fn helm_si_make_many_lut(ctx: *const helm_si_ctx, f_values: *const u64, n_funcs: i32, test_poly_out: *mut u64) -> c_int;
+    pub fn helm_si_apply_many_luts(ctx: *mut helm_si_ctx, w: *mut helm_si_wires, in_idx: *const i32, lut_idx: *const i32,
+                                   out_idx: *const i32, n_out: i32, count: i64, luts: *const u64, n_luts: i64) -> c_int;
+    pub fn helm_si_pbs_many_batch(ctx: *mut helm_si_ctx, in_small: *const u64, luts: *const u64, n_luts: i64,
+                                  lut_idx: *const i32, n_out: i32, out_big: *mut u64, count: i64) -> c_int;
     pub fn helm_si_sync(ctx: *mut helm_si_ctx) -> c_int;
     pub fn helm_si_set_priority(ctx: *mut helm_si_ctx, high: c_int) -> c_int;
     pub fn helm_si_round_capacity(ctx: *mut helm_si_ctx) -> i64;
