@@ -155,15 +155,17 @@ def negacyclic_plain(d, key_signed):
     return out
 
 
-def cmux_step_exact(acc, a_tilde, key_step, shape, width):
+def cmux_step_exact(acc, a_tilde, key_step, shape, width, c1=None):
     """acc: (k+1) polynomials of N Python integers mod 2^w; key_step: the words [l][k+1][k+1][N] of one blind-rotation step.
+    c1: None (the step of a blind rotation: the other operand is X^a_tilde acc), or the (k+1) polynomials of a given second
+    ciphertext (a CMUX of two ciphertexts, acc + GGSW (x) (c1 - acc); a_tilde is not read).
     -> (new accumulator, the largest |exact column-sum coefficient| before the reduction mod 2^w)."""
     k1, N, l = shape.k + 1, shape.N, shape.l
     key_step = np.asarray(key_step).reshape(l, k1, k1, N)
     mod = 1 << width
     dig = np.zeros((k1, l, N), dtype=np.int64)
     for r in range(k1):
-        rot = rotate(acc[r], a_tilde, width)
+        rot = rotate(acc[r], a_tilde, width) if c1 is None else c1[r]
         for t in range(N):
             dig[r, :, t] = digits((rot[t] - int(acc[r][t])) % mod, shape.logB, l, width)
     peak, new = 0, []

@@ -15,7 +15,9 @@ placed just under and just over the loaders' thresholds.  One child process repe
 (libhelm_hip_check.so) admits and requires all of its counters at zero.
 
 Out of scope, still: the multi-bit sets (si_toy_1024_mb2, si_toy_2048_mb3), whose nested key sums need another
-construction.  The keyswitch has its own edge construction: tests/ks_edges.py, tests/test_gpu_keyswitch_edges.py."""
+construction.  The keyswitch has its own edge construction: tests/ks_edges.py, tests/test_gpu_keyswitch_edges.py.  This
+file runs MODE 0 of k_pbs64 only (pbs_l 1 and 2); MODE 1 and MODE 2 - the blind rotation and the CMUX tree of vertical packing,
+with Pbs64Cfg<., 3> and cbs_logB - have theirs: tests/vp_edges.py, tests/test_gpu_vertical_packing_edges.py."""
 import contextlib
 import json
 import os

@@ -246,7 +246,8 @@ def test_lane_follows_keys_reloaded_into_its_primary():
     hip_check(hip.helm_si_load_bootstrap_key(sk._h, as_u64p(own), own.size))
     assert lane.field_bits() == 46
     assert np.array_equal(_pbs_rows_bit_exact(ck, lane, oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ck.ksk), 1, small), got46)
-    ksk2 = np.ascontiguousarray(helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6).ksk, dtype=np.uint64).reshape(-1)
+    ck6 = helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6)   # kept alive: .ksk is a view of the key's own memory
+    ksk2 = np.array(ck6.ksk, dtype=np.uint64).reshape(-1)
     assert ksk2.size == np.asarray(ck.ksk).size and not np.array_equal(ksk2, np.asarray(ck.ksk).reshape(-1))
     hip_check(hip.helm_si_load_keyswitch_key(sk._h, as_u64p(ksk2), ksk2.size))
     cts = ck.encrypt(np.arange(4, dtype=np.uint64) % ck.t)
@@ -267,7 +268,8 @@ def test_a_lane_refuses_keys():
     orc = oracle.Oracle64(ck.params.as_tuple(), ck.bsk, ck.ksk)
     bits = sk.field_bits()
     worst = np.full_like(np.ascontiguousarray(ck.bsk, dtype=np.uint64).reshape(-1), 0x7FFFFFFFFFFFFFFF)   # would move the pair
-    ksk2 = np.ascontiguousarray(helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6).ksk, dtype=np.uint64).reshape(-1)
+    ck6 = helm_amd.SiClientKey.generate("si_toy_512_k3", seed=6)   # kept alive: .ksk is a view of the key's own memory
+    ksk2 = np.array(ck6.ksk, dtype=np.uint64).reshape(-1)
     HELM_ERR_INVALID = -1
     assert hip.helm_si_load_bootstrap_key(lane._h, as_u64p(worst), worst.size) == HELM_ERR_INVALID
     assert "primary" in hip.helm_hip_last_error().decode()

@@ -66,6 +66,63 @@ def test_extract_bits_bit_exact(toy):
         assert [[int(b) for b in row] for row in dec] == [[(v >> i) & 1 for i in range(nb)] for v in vals]
 
 
+@pytest.fixture(scope="module")
+def byte_keys():
+    """message_modulus x carry_modulus = 256 = N / 2: eight bits per row, delta_log = 55"""
+    keys = make_keys("si_toy_512", "wop_toy_512", seed=51, moduli=(16, 16))
+    yield keys
+    keys[3].close()
+    keys[2].close()
+
+
+def test_extract_up_to_eight_bits_bit_exact(byte_keys):
+    """extract_bits_device builds eight constant accumulators: all of them (nb = 8 uses seven, the last bit needs none) and
+    a count in between, every row against the oracle and decrypted against the value's bits."""
+    ck, wk, sk, wsk, ow = byte_keys
+    assert (wk.t, wk.delta_log, wk.params.N) == (256, 55, 512)
+    rng = np.random.default_rng(3)
+    vals = [0, 255, 0b10101010, 0b01010101, 0b11110000, 1, 128]
+    cts = encrypt_wop_big(wk, vals, rng)
+    for nb in (5, 8):
+        got = wsk.extract_bits(cts, wk.delta_log, nb)  # [row][bit, least significant first][n+1]
+        for r in range(len(vals)):
+            want = ow.extract_bits(cts[r], wk.delta_log, nb)[::-1]  # the oracle lists the most significant first
+            assert np.array_equal(got[r], want), (nb, r)
+        ph = wk.phase(got.reshape(-1, wk.params.n + 1), small=True)
+        dec = ((ph + U64(1 << 62)) >> U64(63)).reshape(len(vals), nb)
+        assert [[int(b) for b in row] for row in dec] == [[(v >> i) & 1 for i in range(nb)] for v in vals]
+
+
+@pytest.mark.parametrize("delta_log", [1, 62])
+def test_extract_one_bit_at_the_ends_of_the_admitted_range(toy, delta_log):
+    """nb = 1 admits any delta_log in [1, 62] (no accumulator is used): the bit at position delta_log, shifted to the top."""
+    ck, wk, sk, wsk, ow = toy
+    rng = np.random.default_rng(delta_log)
+    bits = [0, 1, 1, 0, 1]
+    sec = wk.glwe_secret.astype(bool)
+    cts = rng.integers(0, 1 << 64, size=(len(bits), wk.dim + 1), dtype=U64)
+    # the bit at position delta_log under a little noise below it and an arbitrary word above it (shifted out)
+    plain = [(b << delta_log) + ((1 << delta_log) >> 4) + ((int(rng.integers(0, 1 << 62)) << (delta_log + 1)) % (1 << 64)) for b in bits]
+    cts[:, -1] = (cts[:, :-1] * sec).sum(axis=1, dtype=U64) + np.array(plain, dtype=U64)
+    got = wsk.extract_bits(cts, delta_log, 1)
+    for r in range(len(bits)):
+        assert np.array_equal(got[r], ow.extract_bits(cts[r], delta_log, 1)), (delta_log, r)
+    ph = wk.phase(got.reshape(-1, wk.params.n + 1), small=True)
+    assert [int(b) for b in (ph + U64(1 << 62)) >> U64(63)] == bits
+
+
+def test_extract_bits_refusals(toy):
+    from helm_amd import _native as nv
+    ck, wk, sk, wsk, ow = toy
+    cts = encrypt_wop_big(wk, [1, 2], np.random.default_rng(4))
+    assert wk.delta_log == 59
+    for delta_log, nb, why in ((63, 1, "bad bit range"), (wk.delta_log, 5, "bad bit range"), (0, 1, "bad bit range"),
+                               (wk.delta_log, 9, "1..8 bits"),
+                               (wk.delta_log - 1, 2, "more than one bit needs delta_log"), (30, 4, "more than one bit needs delta_log")):
+        with pytest.raises(nv.HelmError, match="error -1: extract_bits: " + why):
+            wsk.extract_bits(cts, delta_log, nb)
+
+
 def test_circuit_bootstrap_bit_exact(toy):
     ck, wk, sk, wsk, ow = toy
     rng = np.random.default_rng(2)
