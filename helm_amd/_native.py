@@ -242,6 +242,7 @@ SI_API = {
     "helm_si_make_many_lut": (C.c_int, [vp, u64p, C.c_int32, u64p]),
     "helm_si_apply_many_luts": (C.c_int, [vp, vp, i32p, i32p, i32p, C.c_int32, C.c_int64, u64p, C.c_int64]),
     "helm_si_eval_lut_level": (C.c_int, [vp, vp, i32p, i32p, C.c_int32, u64p, i32p, C.c_int64]),
+    "helm_si_set_level_many_lut": (C.c_int, [vp, C.c_int]),
     "helm_si_set_exchange": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int64, SI_EXCHANGE_FN, vp]),
     "helm_si_set_exchange_comm": (C.c_int, [vp, vp, C.c_int64, C.c_int64]),
     "helm_si_set_audit": (C.c_int, [vp, SI_AUDIT_FN, vp]),

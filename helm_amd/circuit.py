@@ -206,13 +206,22 @@ class SiEncWireMap:
 class _SiCircuit(EvalCircuit):
     MODE = 0
 
-    def __init__(self, client_key, server_key, circuit):
+    def __init__(self, client_key, server_key, circuit, many_lut=False):
         h = H.vp()
         # client_key None: evaluation only (the caller encrypts / decrypts and moves rows through SiEncWireMap)
         H.check(H.host.helm_host_si_circuit_new(self.MODE, client_key._h if client_key is not None else None, server_key._h,
                                                circuit._h, C.byref(h)))
         self._h = h
         self._ck, self._sk, self.circuit = client_key, server_key, circuit  # keep alive
+        if many_lut:
+            self.set_many_lut(True)
+
+    def set_many_lut(self, on=True):
+        """Share blind rotations through the many-LUT bootstrap (helm_host_si_circuit_set_many_lut; default off).  LUT mode:
+        the gates of a level on the same inputs share one (sets SiServerKey.set_level_many_lut on the server key); arithmetic
+        mode: the message and the carry state of a block in carry propagation's first round come from one rotation (2+2-bit
+        blocks only).  pbs_per_cycle() counts rotations; same values on every wire; resets the same-cycle memo."""
+        H.check(H.host.helm_host_si_circuit_set_many_lut(self._h, int(bool(on))))
 
     def __del__(self):
         if getattr(self, "_h", None):

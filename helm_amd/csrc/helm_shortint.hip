@@ -17,6 +17,7 @@
 #include "../../include/helm_shortint.h"
 #include "../../include/helm_comm.h"
 #include "ntt_fp64.h"
+#include "many_lut_rule.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -1626,6 +1627,7 @@ struct helm_si_ctx {
     // helm_si_set_audit: every helm_si_lincomb / helm_si_apply_luts call hands its operand rows and results to the host
     helm_si_audit_fn audit_fn = nullptr;
     void *audit_user = nullptr;
+    bool level_many = false; // helm_si_set_level_many_lut: the gates of a LUT level that share an input tuple share a rotation
     int x_rank = 0, x_world = 1;
     int64_t x_min = 0, x_cap = 0;
     uint64_t *x_stage = nullptr, *x_gather = nullptr;
@@ -2257,6 +2259,93 @@ int apply_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx
     return 0;
 }
 
+// helm_si_apply_many_luts with the batch sharded over the ranks of helm_si_set_exchange(): the ciphertexts are cut into
+// contiguous chunks as apply_luts_sharded cuts them, a rank's slot of a round holds its chunk's n_out extracts per
+// ciphertext (so a round takes x_cap / n_out ciphertexts per rank), and gathered row i n_out + x is output x of ciphertext
+// base + i.  This rank keyswitches its share of EVERY round before the first round is scattered: an output row of an early
+// ciphertext may be the input row of a later one, and the unsharded call reads every input before it writes any output.
+int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
+                            const int32_t *out_idx, int32_t n_out, int32_t pad, int64_t count, const uint64_t *luts,
+                            int64_t n_luts)
+{
+    const helm_si_params &P = ctx->P;
+    const int dim = P.k * P.N;
+    const int64_t world = ctx->x_world, cts = ctx->x_cap / n_out;
+    if (cts < 1)
+        return fail(HELM_ERR_INVALID, "many-LUT: n_out = " + std::to_string(n_out) + " exceeds the exchange's capacity_rows = " +
+                                          std::to_string(ctx->x_cap) + " (one ciphertext's outputs do not fit a rank's slot)");
+    if (!ctx->keys->have_bsk || !ctx->keys->have_ksk) return fail(HELM_ERR_STATE, "bootstrapping / keyswitching key not loaded");
+    struct Round {
+        int64_t rows;         // ciphertexts per rank
+        size_t first, mine;   // this rank's jobs: ks / pbs entries first .. first + mine
+        size_t s_first, s_n;  // scatter list entries
+    };
+    std::vector<Round> rounds;
+    std::vector<Ks64Job> ks;
+    std::vector<Pbs64Job> pbs;
+    std::vector<int32_t> s_row, d_row;
+    for (int64_t base = 0; base < count;) {
+        const int64_t per = std::min(count - base, cts * world);
+        const int64_t rows = (per + world - 1) / world;
+        const int64_t lo = std::min(base + per, base + ctx->x_rank * rows), hi = std::min(base + per, lo + rows);
+        Round R{rows, ks.size(), (size_t)(hi - lo), s_row.size(), 0};
+        for (int64_t g = lo; g < hi; g++) {
+            const int32_t q = (int32_t)ks.size();
+            ks.push_back(Ks64Job{in_idx[g], q});
+            pbs.push_back(Pbs64Job{q, lut_idx[g], (int32_t)((g - lo) * n_out), pad});
+        }
+        for (int64_t q = 0; q < per * n_out; q++) // the chunks are contiguous: gathered row q is output q % n_out of base + q / n_out
+            if (out_idx[base * n_out + q] >= 0) {
+                s_row.push_back((int32_t)q);
+                d_row.push_back(out_idx[base * n_out + q]);
+            }
+        R.s_n = s_row.size() - R.s_first;
+        rounds.push_back(R);
+        base += per;
+    }
+    const size_t mine = ks.size();
+    if (ctx->d_small.cap < mine * ((size_t)P.n + 1)) {
+        if (int rc = drain(ctx)) return rc; // growing the scratch frees the old one
+        if (ctx->d_small.ensure(mine * ((size_t)P.n + 1))) return fail(HELM_ERR_OOM, "small-LWE scratch");
+    }
+    if (int rc = luts_resident(ctx, luts, (size_t)n_luts * P.N)) return rc;
+    helm_si_ctx::CallSlot *S = nullptr;
+    if (int rc = slot_begin(ctx, mine * (sizeof(Ks64Job) + sizeof(Pbs64Job)) + 2 * s_row.size() * sizeof(int32_t) + 1024, &S))
+        return rc;
+    const Ks64Job *d_ks = slot_put(*S, ks.data(), ks.size());
+    const Pbs64Job *d_pbs = slot_put(*S, pbs.data(), pbs.size());
+    const int32_t *d_src = slot_put(*S, s_row.data(), s_row.size());
+    const int32_t *d_dst = slot_put(*S, d_row.data(), d_row.size());
+    if (int rc = slot_flush(ctx, *S)) return rc;
+    if (mine) {
+        Timed t(ctx, &ctx->ev_ks);
+        HIP_TRY(launch_ks64(ctx, d_ks, (int64_t)mine, w->d, ctx->d_small.p));
+        ctx->tacc.ks_launches++;
+        ctx->tacc.ks_count += (int64_t)mine;
+    }
+    for (const Round &R : rounds) {
+        const int64_t slot_rows = R.rows * n_out;
+        if (R.mine) {
+            Timed t(ctx, &ctx->ev_pbs);
+            HIP_TRY(launch_pbs64(ctx, d_pbs + R.first, (int64_t)R.mine, ctx->d_small.p, ctx->d_luts.p, ctx->x_slot(slot_rows)));
+            ctx->tacc.pbs_launches++;
+            ctx->tacc.pbs_count += (int64_t)R.mine;
+        }
+        // the collective on this context's stream: every rank calls it, also one whose chunk is empty
+        if (int rc = si_exchange(ctx, slot_rows)) return rc;
+        if (int rc = drain(ctx)) return rc;
+        if (R.s_n) {
+            hipLaunchKernelGGL(k_rows64, dim3((unsigned)R.s_n), dim3(256), 0, ctx->stream, ctx->x_gather, d_src + R.s_first, w->d,
+                               d_dst + R.s_first, dim);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream)); // the next round overwrites the slot and the gather buffer
+        ctx->x_batches++;
+        ctx->x_rows += slot_rows * world;
+    }
+    return slot_end(ctx, *S);
+}
+
 uint64_t si_modulus(int pair, int f) { return pair ? (f ? J1::P_U64 : J0::P_U64) : (f ? F1::P_U64 : F0::P_U64); }
 
 // psi of field f of a pair: a primitive 2N-th root of unity.  pair 1 (the 46-bit fields): the one with psi^(N/4) = b - it is
@@ -2558,6 +2647,7 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
     ctx->n_cus = primary->n_cus;
     ctx->audit_fn = primary->audit_fn; // a lane is audited like its primary
     ctx->audit_user = primary->audit_user;
+    ctx->level_many = primary->level_many; // ... and groups the gates of a level like it
     hipError_t e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete ctx;
@@ -3136,22 +3226,26 @@ int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
     std::vector<uint64_t> audit_in, audit_out;
     if (ctx->audit_fn)
         if (int rc = audit_fetch(ctx, w, in_idx, count, audit_in)) return rc;
-    // not sharded under an exchange: every rank computes the whole batch (helm_shortint.h).  Every keyswitch finishes
-    // (kernel boundary) before the scatter writes an output row: the bootstraps write the stage buffer only.
-    if (int rc = apply_many_luts_stage(ctx, w->d, in_idx, lut_idx, n_out, pad, count, luts, n_luts)) return rc;
-    if (!d_row.empty()) {
-        helm_si_ctx::CallSlot *S = nullptr;
-        if (int rc = slot_begin(ctx, 2 * d_row.size() * sizeof(int32_t), &S)) return rc;
-        const int32_t *d_src = slot_put(*S, s_row.data(), s_row.size());
-        const int32_t *d_dst = slot_put(*S, d_row.data(), d_row.size());
-        if (int rc = slot_flush(ctx, *S)) return rc;
-        {
-            Timed t(ctx, &ctx->ev_lin);
-            hipLaunchKernelGGL(k_rows64, dim3((unsigned)d_row.size()), dim3(256), 0, ctx->stream, ctx->d_stage.p, d_src, w->d,
-                               d_dst, ctx->P.k * ctx->P.N);
-            HIP_TRY(hipGetLastError());
+    if (ctx->x_on && count >= ctx->x_min) {
+        if (int rc = apply_many_luts_sharded(ctx, w, in_idx, lut_idx, out_idx, n_out, pad, count, luts, n_luts)) return rc;
+    } else {
+        // Every keyswitch finishes (kernel boundary) before the scatter writes an output row: the bootstraps write the stage
+        // buffer only.
+        if (int rc = apply_many_luts_stage(ctx, w->d, in_idx, lut_idx, n_out, pad, count, luts, n_luts)) return rc;
+        if (!d_row.empty()) {
+            helm_si_ctx::CallSlot *S = nullptr;
+            if (int rc = slot_begin(ctx, 2 * d_row.size() * sizeof(int32_t), &S)) return rc;
+            const int32_t *d_src = slot_put(*S, s_row.data(), s_row.size());
+            const int32_t *d_dst = slot_put(*S, d_row.data(), d_row.size());
+            if (int rc = slot_flush(ctx, *S)) return rc;
+            {
+                Timed t(ctx, &ctx->ev_lin);
+                hipLaunchKernelGGL(k_rows64, dim3((unsigned)d_row.size()), dim3(256), 0, ctx->stream, ctx->d_stage.p, d_src, w->d,
+                                   d_dst, ctx->P.k * ctx->P.N);
+                HIP_TRY(hipGetLastError());
+            }
+            if (int rc = slot_end(ctx, *S)) return rc;
         }
-        if (int rc = slot_end(ctx, *S)) return rc;
     }
     if (!ctx->audit_fn) return 0;
     if (int rc = audit_fetch(ctx, w, out_idx, n_rows, audit_out)) return rc;
@@ -3166,6 +3260,13 @@ int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
     rec.luts = luts;
     if (int rc = ctx->audit_fn(ctx->audit_user, &rec))
         return fail(HELM_ERR_STATE, "helm_si_apply_many_luts: the audit callback rejected the batch (" + std::to_string(rc) + ")");
+    return 0;
+}
+
+int helm_si_set_level_many_lut(helm_si_ctx *ctx, int on)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null context");
+    ctx->level_many = on != 0;
     return 0;
 }
 
@@ -3314,6 +3415,10 @@ int helm_si_eval_lut_level(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *ar
                 lin_in[(size_t)g * max_in + q] = in[q];
                 lin_coef[(size_t)g * max_in + q] = (int64_t)1 << (ar - 1 - q);
             }
+            if (ctx->level_many) { // tables per group of gates, below
+                pbs_gate.push_back((int32_t)g);
+                continue;
+            }
             const std::pair<int, uint64_t> key(ar, table[g]);
             auto it = lut_of.find(key);
             if (it == lut_of.end()) {
@@ -3348,7 +3453,76 @@ int helm_si_eval_lut_level(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *ar
             sub_out.push_back(out_idx[g]);
         }
     };
-    if (!pbs_gate.empty()) {
+    if (ctx->level_many && !pbs_gate.empty()) {
+        // helm_si_set_level_many_lut: gates with the same inputs in the same order pack the same index, so up to
+        // helm_many_lut::group_max of them are the functions of one many-LUT table and one blind rotation.  A group's index is
+        // packed into its first gate's output row; a group of n gates has a table of M_g = the power of two >= n chunks
+        // (n = 1: helm_si_make_lut's polynomial) and the level is ONE dispatch of n_out = M_d = the largest M_g: gate i of a
+        // group is output i M_d / M_g (the extract at coefficient i N / M_g), every other output is skipped.
+        struct Group {
+            std::vector<int32_t> gates;
+            int32_t lut = 0;
+            int M = 1;
+        };
+        std::vector<Group> groups;
+        std::map<std::pair<int, std::vector<int32_t>>, size_t> open; // (arity, inputs) -> the group that still has room
+        for (int32_t g : pbs_gate) {
+            const int ar = arity[g];
+            std::pair<int, std::vector<int32_t>> key(ar, std::vector<int32_t>(in_idx + (size_t)g * max_in, in_idx + (size_t)g * max_in + ar));
+            auto it = open.find(key);
+            if (it == open.end() || (int)groups[it->second].gates.size() >= helm_many_lut::group_max(ar, t)) {
+                open[key] = groups.size();
+                groups.push_back(Group());
+                groups.back().gates.push_back(g);
+            } else
+                groups[it->second].gates.push_back(g);
+        }
+        std::map<std::pair<int, std::vector<uint64_t>>, int32_t> tables_of; // one test polynomial per distinct function tuple
+        int Md = 1;
+        for (Group &G : groups) {
+            const int ar = arity[G.gates[0]], n = (int)G.gates.size();
+            while (G.M < n) G.M *= 2;
+            Md = std::max(Md, G.M);
+            std::pair<int, std::vector<uint64_t>> key(ar, std::vector<uint64_t>());
+            for (int32_t g : G.gates) key.second.push_back(table[g]);
+            auto it = tables_of.find(key);
+            if (it == tables_of.end()) {
+                const int per = t / G.M; // 2^ar <= per (helm_many_lut::group_max): the packed index is below it
+                std::vector<uint64_t> f((size_t)n * per, 0);
+                for (int i = 0; i < n; i++)
+                    for (int v = 0; v < per; v++) {
+                        const int idx = ar == 2 ? (((v >> 1) & 1) * 2 + (v & 1)) : (v & ((1 << ar) - 1));
+                        f[(size_t)i * per + v] = (key.second[(size_t)i] >> idx) & 1ull;
+                    }
+                const int32_t id = (int32_t)(luts.size() / P.N);
+                luts.resize(luts.size() + P.N);
+                if (int rc = n == 1 ? helm_si_make_lut(ctx, f.data(), luts.data() + (size_t)id * P.N)
+                                    : helm_si_make_many_lut(ctx, f.data(), n, luts.data() + (size_t)id * P.N))
+                    return rc;
+                it = tables_of.emplace(key, id).first;
+            }
+            G.lut = it->second;
+        }
+        std::vector<int32_t> g_in, g_row, g_out;
+        std::vector<int64_t> g_coef;
+        for (const Group &G : groups) {
+            const int32_t g0 = G.gates[0];
+            g_in.insert(g_in.end(), lin_in.begin() + (size_t)g0 * max_in, lin_in.begin() + (size_t)(g0 + 1) * max_in);
+            g_coef.insert(g_coef.end(), lin_coef.begin() + (size_t)g0 * max_in, lin_coef.begin() + (size_t)(g0 + 1) * max_in);
+            g_row.push_back(out_idx[g0]);
+            lut_idx.push_back(G.lut);
+            const size_t at = g_out.size();
+            g_out.resize(at + (size_t)Md, -1);
+            for (size_t i = 0; i < G.gates.size(); i++) g_out[at + i * (size_t)(Md / G.M)] = out_idx[G.gates[i]];
+        }
+        if (int rc = helm_si_lincomb(ctx, w, g_in.data(), g_coef.data(), nullptr, g_row.data(), max_in, (int64_t)g_row.size()))
+            return rc;
+        const int rc = Md == 1 ? helm_si_apply_luts(ctx, w, g_row.data(), lut_idx.data(), g_row.data(), (int64_t)g_row.size(),
+                                                    luts.data(), (int64_t)(luts.size() / P.N))
+                               : helm_si_apply_many_luts(ctx, w, g_row.data(), lut_idx.data(), g_out.data(), Md, (int64_t)g_row.size(),
+                                                         luts.data(), (int64_t)(luts.size() / P.N));
+        if (rc) return rc;
+    } else if (!pbs_gate.empty()) {
         gather(true);
         if (int rc = helm_si_lincomb(ctx, w, sub_in.data(), sub_coef.data(), nullptr, sub_out.data(), max_in,
                                      (int64_t)sub_out.size()))

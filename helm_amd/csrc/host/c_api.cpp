@@ -443,6 +443,38 @@ int helm_host_radix_level(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blocks
         if (rounds_out) *rounds_out = eng.pbs_rounds();
     });
 }
+int helm_host_radix_level_ex(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blocks, const helm_radix_op *ops, int64_t count,
+                             int32_t scratch_first_row, int64_t *pbs_out, int64_t *rounds_out, int flags)
+{
+    return guard([&] {
+        if (!ctx || !wires || blocks < 1 || scratch_first_row < 0) throw Panic("radix level: bad argument");
+        if (flags & ~HELM_RADIX_MANY_LUT) throw Panic("radix level: unknown flag bits");
+        RadixEngine eng(ctx, blocks);
+        eng.set_many_lut((flags & HELM_RADIX_MANY_LUT) != 0);
+        eng.run_level(wires, to_radix_ops(ops, count), scratch_first_row);
+        if (pbs_out) *pbs_out = eng.pbs_count();
+        if (rounds_out) *rounds_out = eng.pbs_rounds();
+    });
+}
+int helm_host_si_circuit_set_many_lut(helm_si_circuit *c, int on)
+{
+    if (!c) {
+        g_err = "set_many_lut: null circuit";
+        return -1;
+    }
+    return guard([&] {
+        if (c->lut) {
+            c->lut->set_many_lut(on != 0);
+            return;
+        }
+        helm_si_params P{};
+        if (helm_si_get_params(c->arith->server_key(), &P) != 0) throw Panic("set_many_lut: no parameters");
+        // a block sum of carry propagation is <= 7: the two-function table needs t / 2 > 7
+        if (on && (P.message_modulus != 4 || P.carry_modulus != 4))
+            throw Panic("set_many_lut: carry propagation on many-LUT needs 2+2-bit blocks (message_modulus = carry_modulus = 4)");
+        c->arith->set_many_lut(on != 0);
+    });
+}
 int helm_host_si_circuit_set_lazy_carries(helm_si_circuit *c, int on)
 {
     if (!c || !c->arith) {

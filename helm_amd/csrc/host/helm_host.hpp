@@ -23,6 +23,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../many_lut_rule.h"
 #include "../../../include/helm_client.h"
 #include "../../../include/helm_wopbs.h"
 #include "../../../include/helm_hip.h"
@@ -346,6 +347,9 @@ class LutCircuit : public EvalCircuit<SiEncWireMap> {
     // carrying its level's time, which costs one host synchronisation per level.  set_timing_lines(false) drops the
     // lines AND the per-level synchronisation: the host then prepares the next level while the GPU runs this one.
     void set_timing_lines(bool on) { timing_lines_ = on; }
+    // helm_si_set_level_many_lut on the server key's context: gates of a level on the same inputs share a blind rotation;
+    // pbs_per_cycle() then counts rotations (helm_many_lut::group_max is the engine's own rule)
+    void set_many_lut(bool on);
 
   private:
     helm_si_client_key *client_key_;
@@ -353,6 +357,7 @@ class LutCircuit : public EvalCircuit<SiEncWireMap> {
     helm_wop_ctx *wop_ = nullptr;
     int wop_bits_per_block_ = 1;
     bool timing_lines_ = true;
+    bool many_lut_ = false;
     Circuit circuit_;
     helm_si_params P_{};
     int64_t pbs_count_ = 0;
@@ -391,8 +396,11 @@ class RoundMerger {
     RoundMerger(helm_si_ctx *ctx, int chains, int64_t capacity, bool strict = false);
     void set_remaining(int chain, int64_t rounds) { remaining_[(size_t)chain] = rounds; }
     // the chain's next round; returns once all of it is ENQUEUED (stream order does the rest)
+    // out2 (optional, one entry per look-up, -1 = none): the row of the SECOND many-LUT output of that rotation.  A merged
+    // launch that holds any such entry is one helm_si_apply_many_luts with n_out = 2 (plain entries: second output skipped;
+    // a one-function table's extract at coefficient 0 is what helm_si_apply_luts gives).  `capacity` counts rotations.
     void submit(int chain, helm_si_wires *w, const std::vector<int32_t> &in, const std::vector<int32_t> &lut,
-                const std::vector<int32_t> &out, const uint64_t *luts, int64_t n_luts);
+                const std::vector<int32_t> &out, const uint64_t *luts, int64_t n_luts, const std::vector<int32_t> *out2 = nullptr);
     void finish(int chain); // no more rounds from this chain (also on error)
     std::mutex &device() { return mu_; } // every other device call of a chain holds it: one context, several threads
     int64_t launches() const { return launches_; }
@@ -400,7 +408,7 @@ class RoundMerger {
   private:
     struct Sub {
         helm_si_wires *w = nullptr;
-        const std::vector<int32_t> *in = nullptr, *lut = nullptr, *out = nullptr;
+        const std::vector<int32_t> *in = nullptr, *lut = nullptr, *out = nullptr, *out2 = nullptr;
         const uint64_t *luts = nullptr;
         int64_t n_luts = 0;
         size_t taken = 0;
@@ -427,14 +435,17 @@ class RadixEngine {
     void run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch);
     void propagate(helm_si_wires *w, const std::vector<int32_t> &bases, int scratch, int width,
                    const std::vector<int32_t> *carry_out_rows);
-    int64_t pbs_count() const { return pbs_count_; }
+    int64_t pbs_count() const { return pbs_count_; } // blind rotations
     int64_t pbs_rounds() const { return pbs_rounds_; }
+    // Round 1 of propagate() on many-LUT: a block sum is <= 7 < 8 = t / 2, so its message and its weighted carry state are
+    // two functions of ONE blind rotation (helm_si_apply_many_luts, n_out = 2) instead of two look-ups.  Off by default.
+    void set_many_lut(bool on);
 
   private:
     void lincomb(helm_si_wires *w, const std::vector<int32_t> &in_idx, const std::vector<int64_t> &coef,
                  const std::vector<int64_t> &cadd, const std::vector<int32_t> &out, int terms);
     void apply(helm_si_wires *w, const std::vector<int32_t> &in, const std::vector<int32_t> &lut,
-               const std::vector<int32_t> &out);
+               const std::vector<int32_t> &out, const std::vector<int32_t> *out2 = nullptr);
     struct Carries {
         std::vector<int32_t> row; // [integer * (need + 1) + item]
         bool bit = true;          // 0 / 4, else c form (4 c: carry <=> c >= 2)
@@ -453,6 +464,8 @@ class RadixEngine {
     int lut_t_[4] = {}, lut_s_[4] = {}, lut_q_[3] = {}, lut_gc_[3] = {}, lut_q3_ = 0, lut_gc3_ = 0, lut_resolve_ = 0, lut_final_ = 0,
         lut_cout_ = 0; // carry propagation, see propagate()
     int lut_bit0_ = 0, lut_bit1_ = 0, lut_shl1_ = 0, lut_shr1_ = 0, lut_sel_ = 0;
+    bool many_lut_ = false;
+    int lut_pair_[4] = {-1, -1, -1, -1}; // (message, carry state x 2^p) of a block sum <= 7: built by set_many_lut(true)
     int64_t pbs_count_ = 0, pbs_rounds_ = 0;
     std::vector<int32_t> pend_in_, pend_lut_, pend_out_; // look-ups waiting for the level's next batch
     RoundMerger *merger_ = nullptr; // set: look-up rounds go through the merger, other device calls under its lock
@@ -474,6 +487,7 @@ class ArithCircuit : public EvalCircuit<SiEncWireMap> {
     std::map<std::string, PtxtType> decrypt_outputs(const SiEncWireMap &enc_wire_map, bool verbose) override;
     int64_t pbs_per_cycle() const { return pbs_count_; }
     int64_t pbs_rounds_per_cycle() const { return pbs_rounds_; }
+    helm_si_ctx *server_key() const { return server_key_; }
     std::string log() { std::string s; s.swap(log_); return s; }
     // Lanes (helm_si_ctx_fork): sub-circuits that share no wire are evaluated concurrently, one lane each, instead of
     // meeting at every level boundary (circuit.rs:1321 joins the whole level).  Same ciphertexts, fewer rounds in a row.
@@ -492,6 +506,8 @@ class ArithCircuit : public EvalCircuit<SiEncWireMap> {
     // Merged rounds: launches of at most this many ciphertexts (0 = helm_si_round_capacity(), what the device
     // bootstraps at once).  Tests force 1 to cut every round into single-ciphertext launches.
     void set_round_capacity(int64_t capacity) { round_capacity_ = capacity; reset_memo(); }
+    // Carry propagation's first round on many-LUT (RadixEngine::set_many_lut); like every schedule switch it drops the memo
+    void set_many_lut(bool on) { many_lut_ = on; reset_memo(); }
 
   private:
     void encrypt_value(SiEncWireMap &m, const std::string &wire, unsigned __int128 value);
@@ -501,6 +517,7 @@ class ArithCircuit : public EvalCircuit<SiEncWireMap> {
     bool auto_lanes_ = true;
     bool lazy_carries_ = true; // carry-save products feeding additions / subtractions (set_lazy_carries)
     bool memo_on_ = true;
+    bool many_lut_ = false;
     int64_t round_capacity_ = 0;
     Circuit circuit_;
     helm_si_params P_{};

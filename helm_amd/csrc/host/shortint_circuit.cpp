@@ -268,6 +268,13 @@ void LutCircuit::set_wide_lut_key(helm_wop_ctx *wop, int bits_per_block)
     memo_.valid = false; // wide gates now take another path
 }
 
+void LutCircuit::set_many_lut(bool on)
+{
+    si_ok(helm_si_set_level_many_lut(server_key_, on ? 1 : 0), "set_level_many_lut");
+    many_lut_ = on;
+    memo_.valid = false; // the level dispatches change
+}
+
 // reference src/circuit.rs:1032-1083
 std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap &enc_wire_map, size_t cycle,
                                                              const std::string & /*ptxt_type*/)
@@ -337,6 +344,7 @@ std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap 
             std::vector<uint64_t> tables;
         };
         std::map<int, Wide> wide;
+        std::map<std::vector<int32_t>, int64_t> sharing; // many_lut_: bootstrapped gates per input tuple (in order)
         for (size_t gi = 0; gi < gates.size(); gi++) {
             const Gate &g = gates[gi];
             const auto &ins = g.get_input_wires();
@@ -364,7 +372,14 @@ std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap 
                     if ((*g.get_lut_const())[i] & 1) bits |= 1ull << i;
                 arity.push_back((int32_t)ins.size());
                 table.push_back(bits);
-                if (ins.size() >= 2) pbs_count_++;
+                if (ins.size() >= 2) {
+                    if (many_lut_) {
+                        std::vector<int32_t> key;
+                        for (auto &w : ins) key.push_back(in_row_of(w));
+                        sharing[key]++;
+                    } else
+                        pbs_count_++;
+                }
             } else { // evaluate_encrypted_dff: the output is a copy of the first input (circuit.rs:1067)
                 if (ins.empty()) throw Panic("gate \"" + g.get_gate_name() + "\" has no input");
                 arity.push_back(0);
@@ -374,6 +389,10 @@ std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap 
             in_idx.resize(slot + (size_t)max_in, -1);
             for (size_t q = 0; q < ins.size(); q++) in_idx[slot + q] = in_row_of(ins[q]);
             out.push_back(eval_values->row(g.get_output_wire()));
+        }
+        for (auto &kv2 : sharing) { // rotations: a tuple's gates in groups of the engine's size
+            const int64_t gm = helm_many_lut::group_max((int)kv2.first.size(), P_.message_modulus * P_.carry_modulus);
+            pbs_count_ += (kv2.second + gm - 1) / gm;
         }
         const auto level_start = std::chrono::steady_clock::now();
         // wide gates first: they read the level's inputs before a state copy of the same level overwrites one
@@ -482,6 +501,25 @@ RadixEngine::RadixEngine(helm_si_ctx *ctx, int nb) : ctx_(ctx), nb_(nb)
     lut_sel_ = add_lut([](int v) { return (v >> 2) ? (v & 3) : 0; }); // 4 * c + x -> c ? x : 0
 }
 
+void RadixEngine::set_many_lut(bool on)
+{
+    many_lut_ = on;
+    if (!on || lut_pair_[0] >= 0) return;
+    // the pair tables join the table set only on request: with the setting off every call passes the tables it always did
+    const int per = 8; // t / 2: the input bound of a two-function table; block sums are <= 7 (propagate())
+    for (int p = 0; p < 4; p++) {
+        std::vector<uint64_t> vals((size_t)2 * per);
+        for (int v = 0; v < per; v++) {
+            vals[(size_t)v] = (uint64_t)(v & 3);                                     // lut_msg_
+            vals[(size_t)per + v] = (uint64_t)((v >= 4 ? 2 : v == 3 ? 1 : 0) << p);  // lut_t_[p]
+        }
+        const size_t at = luts_.size();
+        luts_.resize(at + (size_t)P_.N);
+        si_ok(helm_si_make_many_lut(ctx_, vals.data(), 2, luts_.data() + at), "make_many_lut");
+        lut_pair_[p] = (int)(at / (size_t)P_.N);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // RoundMerger
 // ---------------------------------------------------------------------------------------
@@ -512,7 +550,7 @@ void RoundMerger::issue_locked()
         // a single chain left, or everything fits: one launch; otherwise fill the device once, most urgent chain first
         // (strict_: a capacity the caller set is honoured for a lone chain too - the tests' way to cut everywhere)
         const int64_t cap = ((present == 1 && !strict_) || total <= capacity_) ? total : capacity_;
-        std::vector<int32_t> in, lut, out;
+        std::vector<int32_t> in, lut, out, out2; // out2: filled from the first entry with a second output on
         in.reserve((size_t)cap), lut.reserve((size_t)cap), out.reserve((size_t)cap);
         const Sub &first = subs_[order[0]];
         for (size_t c : order) {
@@ -525,10 +563,21 @@ void RoundMerger::issue_locked()
             in.insert(in.end(), s.in->begin() + (long)s.taken, s.in->begin() + (long)(s.taken + n));
             lut.insert(lut.end(), s.lut->begin() + (long)s.taken, s.lut->begin() + (long)(s.taken + n));
             out.insert(out.end(), s.out->begin() + (long)s.taken, s.out->begin() + (long)(s.taken + n));
+            if (s.out2 && std::any_of(s.out2->begin() + (long)s.taken, s.out2->begin() + (long)(s.taken + n), [](int32_t r) { return r >= 0; })) {
+                out2.resize(in.size() - n, -1);
+                out2.insert(out2.end(), s.out2->begin() + (long)s.taken, s.out2->begin() + (long)(s.taken + n));
+            }
             s.taken += n;
         }
         if (error_.empty() && !in.empty()) {
-            if (helm_si_apply_luts(ctx_, first.w, in.data(), lut.data(), out.data(), (int64_t)in.size(), first.luts, first.n_luts) != 0)
+            if (!out2.empty()) { // a launch with a pair job: every entry is a rotation with two outputs, most of them skipped
+                out2.resize(in.size(), -1);
+                std::vector<int32_t> both(2 * in.size());
+                for (size_t i = 0; i < in.size(); i++) both[2 * i] = out[i], both[2 * i + 1] = out2[i];
+                if (helm_si_apply_many_luts(ctx_, first.w, in.data(), lut.data(), both.data(), 2, (int64_t)in.size(), first.luts,
+                                            first.n_luts) != 0)
+                    error_ = std::string("apply_many_luts: ") + helm_hip_last_error();
+            } else if (helm_si_apply_luts(ctx_, first.w, in.data(), lut.data(), out.data(), (int64_t)in.size(), first.luts, first.n_luts) != 0)
                 error_ = std::string("apply_luts: ") + helm_hip_last_error();
             launches_++;
         }
@@ -549,7 +598,7 @@ void RoundMerger::issue_locked()
 }
 
 void RoundMerger::submit(int chain, helm_si_wires *w, const std::vector<int32_t> &in, const std::vector<int32_t> &lut,
-                         const std::vector<int32_t> &out, const uint64_t *luts, int64_t n_luts)
+                         const std::vector<int32_t> &out, const uint64_t *luts, int64_t n_luts, const std::vector<int32_t> *out2)
 {
     // Ordering contract of a round (RadixEngine::apply): the merger may cut a round into several launches, so the
     // guarantee of ONE helm_si_apply_luts call - every keyswitch reads its input before any bootstrap writes - only holds
@@ -565,12 +614,13 @@ void RoundMerger::submit(int chain, helm_si_wires *w, const std::vector<int32_t>
                 throw Panic("round merger: entry " + std::to_string(i) + " of a look-up round reads row " + std::to_string(in[i]) +
                             ", which an earlier entry of the same round writes - list the readers of a row before its in-place writer");
             written.insert(out[i]);
+            if (out2 && (*out2)[i] >= 0) written.insert((*out2)[i]);
         }
     }
     std::unique_lock<std::mutex> lk(mu_);
     if (!error_.empty()) throw Panic(error_);
     Sub &s = subs_[(size_t)chain];
-    s.w = w, s.in = &in, s.lut = &lut, s.out = &out, s.luts = luts, s.n_luts = n_luts, s.taken = 0, s.present = true;
+    s.w = w, s.in = &in, s.lut = &lut, s.out = &out, s.out2 = out2, s.luts = luts, s.n_luts = n_luts, s.taken = 0, s.present = true;
     issue_locked();
     cv_.wait(lk, [&] { return !s.present; });
     if (!error_.empty()) throw Panic(error_);
@@ -595,26 +645,35 @@ void RadixEngine::lincomb(helm_si_wires *w, const std::vector<int32_t> &in_idx, 
 }
 
 void RadixEngine::apply(helm_si_wires *w, const std::vector<int32_t> &in, const std::vector<int32_t> &lut,
-                        const std::vector<int32_t> &out)
+                        const std::vector<int32_t> &out, const std::vector<int32_t> *out2)
 {
     // look-ups that wait for a batch to ride in (shift_scalar): independent rows, so any batch of the level will do
     if (!pend_in_.empty()) {
-        std::vector<int32_t> i2(in), l2(lut), o2(out);
+        std::vector<int32_t> i2(in), l2(lut), o2(out), p2;
         i2.insert(i2.end(), pend_in_.begin(), pend_in_.end());
         l2.insert(l2.end(), pend_lut_.begin(), pend_lut_.end());
         o2.insert(o2.end(), pend_out_.begin(), pend_out_.end());
+        if (out2) {
+            p2 = *out2;
+            p2.resize(i2.size(), -1); // the riders have one output
+        }
         pend_in_.clear();
         pend_lut_.clear();
         pend_out_.clear();
-        apply(w, i2, l2, o2);
+        apply(w, i2, l2, o2, out2 ? &p2 : nullptr);
         return;
     }
     if (in.empty()) return;
+    const int64_t n_luts = (int64_t)(luts_.size() / (size_t)P_.N);
     if (merger_)
-        merger_->submit(chain_, w, in, lut, out, luts_.data(), (int64_t)(luts_.size() / (size_t)P_.N));
-    else
-        si_ok(helm_si_apply_luts(ctx_, w, in.data(), lut.data(), out.data(), (int64_t)in.size(), luts_.data(),
-                                 (int64_t)(luts_.size() / (size_t)P_.N)),
+        merger_->submit(chain_, w, in, lut, out, luts_.data(), n_luts, out2);
+    else if (out2) { // one rotation per entry, two outputs (the second may be skipped: -1)
+        std::vector<int32_t> both(2 * in.size());
+        for (size_t i = 0; i < in.size(); i++) both[2 * i] = out[i], both[2 * i + 1] = (*out2)[i];
+        si_ok(helm_si_apply_many_luts(ctx_, w, in.data(), lut.data(), both.data(), 2, (int64_t)in.size(), luts_.data(), n_luts),
+              "apply_many_luts");
+    } else
+        si_ok(helm_si_apply_luts(ctx_, w, in.data(), lut.data(), out.data(), (int64_t)in.size(), luts_.data(), n_luts),
               "apply_luts");
     pbs_count_ += (int64_t)in.size();
     pbs_rounds_++;
@@ -768,10 +827,20 @@ void RadixEngine::propagate(helm_si_wires *w, const std::vector<int32_t> &bases,
             if (i < need) in.push_back(bases[(size_t)g] + i), lut.push_back(lut_t_[i % 4]), out.push_back(tbase + g * W + i);
             in2.push_back(bases[(size_t)g] + i), lut2.push_back(lut_msg_), out2.push_back(bases[(size_t)g] + i);
         }
-    in.insert(in.end(), in2.begin(), in2.end());
-    lut.insert(lut.end(), lut2.begin(), lut2.end());
-    out.insert(out.end(), out2.begin(), out2.end());
-    apply(w, in, lut, out);
+    if (many_lut_) { // one rotation per block: output 0 = the message (in place), output 1 = the weighted state
+        std::vector<int32_t> pin, plut, pout, pst;
+        for (int g = 0; g < G; g++)
+            for (int i = 0; i < W; i++) {
+                pin.push_back(bases[(size_t)g] + i), plut.push_back(lut_pair_[i % 4]), pout.push_back(bases[(size_t)g] + i);
+                pst.push_back(i < need ? tbase + g * W + i : -1);
+            }
+        apply(w, pin, plut, pout, &pst);
+    } else {
+        in.insert(in.end(), in2.begin(), in2.end());
+        lut.insert(lut.end(), lut2.begin(), lut2.end());
+        out.insert(out.end(), out2.begin(), out2.end());
+        apply(w, in, lut, out);
+    }
     if (need == 0) return;
     Carries C = carries(w, st, G, W, need, false, sp, false);
     // last round: message + 4 c -> (message + [c >= 2]) & 3; bit-form carries are c = 1 + bit
@@ -1523,6 +1592,7 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
     const int bits = 2 * nb;
     const unsigned __int128 vmask = bits >= 128 ? ~(unsigned __int128)0 : (((unsigned __int128)1 << bits) - 1);
     RadixEngine eng(server_key_, nb);
+    eng.set_many_lut(many_lut_);
     // plan every level first: the scratch region is sized once
     std::vector<std::vector<RadixOp>> plan;
     auto eval_values = enc_wire_map.clone(0);
@@ -1775,6 +1845,7 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
         int64_t total_scratch = 0;
         for (size_t lane = 0; lane < n_ctx; lane++) {
             engines.emplace_back(new RadixEngine(ctx_of(lane), nb));
+            engines.back()->set_many_lut(many_lut_);
             if (merger) engines.back()->attach(merger.get(), (int)lane);
             for (auto &ops : lane_plan[lane]) lane_scratch[lane] = std::max(lane_scratch[lane], engines[lane]->scratch_rows(ops));
             total_scratch += lane_scratch[lane];

@@ -188,6 +188,12 @@ class SiServerKey:
             hip_check(v)
         return "generic" if v == 1 else "tuned"
 
+    def set_level_many_lut(self, on=True):
+        """helm_si_set_level_many_lut: SiWires.eval_lut_level groups the gates of a level that have the same inputs in the same
+        order - up to t >> arity of them are the functions of one many-LUT table and cost one blind rotation (a full adder's
+        0x96 and 0xE8: one instead of two).  Default off; a lane forked afterwards inherits the setting."""
+        hip_check(hip.helm_si_set_level_many_lut(self._h, int(bool(on))))
+
     def set_stream(self, stream_ptr):
         nv.require_one_hip_runtime(type(self).__name__ + ".set_stream")  # the handle is another framework's
         hip_check(hip.helm_si_set_stream(self._h, nv.vp(stream_ptr)))

@@ -172,6 +172,16 @@ int helm_host_si_circuit_set_lazy_carries(helm_si_circuit *c, int on);
  * A round that does not fit is cut; the cut is safe because every round lists the readers of a row before its in-place
  * writer - checked for every round, a violation is an error whatever the capacity.  Tests force capacity 1. */
 int helm_host_si_circuit_set_round_capacity(helm_si_circuit *c, int64_t capacity);
+/* Blind rotations shared through the many-LUT bootstrap (helm_si_apply_many_luts; default off, everything as without it).
+ * LUT mode: sets helm_si_set_level_many_lut on the circuit's server key - the gates of a level with the same inputs in the
+ * same order share a rotation (a full adder's sum and carry: one instead of two).  Arithmetic mode: round 1 of carry
+ * propagation issues ONE rotation per block - a block sum is <= 7 < 8 = t / 2, so its message (written in place) and its
+ * weighted carry state are the two outputs of one two-function table - instead of two look-ups on the same row; needs
+ * 2+2-bit blocks (message_modulus = carry_modulus = 4), an error otherwise.  Merged rounds that hold such a job are issued
+ * as one helm_si_apply_many_luts with n_out = 2 (the other look-ups skip their second output); the round capacity counts
+ * rotations.  helm_host_si_circuit_pbs_per_cycle counts rotations.  Same values on every wire; changing the setting resets
+ * the same-cycle memo. */
+int helm_host_si_circuit_set_many_lut(helm_si_circuit *c, int on);
 /* Arithmetic mode, same-cycle memo (see helm_host_si_circuit_memo_hits): on by default and keyed on the cycle ALONE as the
  * reference's (src/gates.rs:307-312) - evaluate_encrypted with an already evaluated cycle returns that cycle's gate outputs
  * WHATEVER the inputs.  set_memo(0) switches it off, reset_memo() forgets the remembered cycle; changing lanes, lazy carries
@@ -201,6 +211,12 @@ typedef struct {
 int64_t helm_host_radix_scratch_rows(helm_si_ctx *ctx, int32_t blocks, const helm_radix_op *ops, int64_t count);
 int helm_host_radix_level(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blocks, const helm_radix_op *ops, int64_t count,
                           int32_t scratch_first_row, int64_t *pbs_out, int64_t *rounds_out);
+/* helm_host_radix_level with flags: HELM_RADIX_MANY_LUT = carry propagation's first round on many-LUT (see
+ * helm_host_si_circuit_set_many_lut: one rotation per block instead of two look-ups; pbs_out counts rotations).  flags = 0 is
+ * helm_host_radix_level; unknown bits are an error. */
+enum { HELM_RADIX_MANY_LUT = 1 };
+int helm_host_radix_level_ex(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blocks, const helm_radix_op *ops, int64_t count,
+                             int32_t scratch_first_row, int64_t *pbs_out, int64_t *rounds_out, int flags);
 char *helm_host_si_circuit_log(helm_si_circuit *c);
 /* bootstraps of the last evaluate_encrypted, and (arithmetic) the number of batched rounds */
 int64_t helm_host_si_circuit_pbs_per_cycle(const helm_si_circuit *c);

@@ -198,9 +198,15 @@ int helm_si_make_many_lut(const helm_si_ctx *ctx, const uint64_t *f_values, int3
  * helm_si_apply_luts: every keyswitch finishes before any output row is written (an output may be an input row), row
  * indices are range-checked, lanes work alike, and n_out = 1 gives the rows of helm_si_apply_luts.  Two outputs of one call
  * naming the same row, n_out < 1 or M > t: HELM_ERR_INVALID.  helm_si_get_timing counts blind rotations: pbs_count rises by
- * count, not by count * n_out.  Under an exchange (helm_si_set_exchange*) a many-LUT batch is NOT sharded: every rank
- * computes the whole batch - tables are replicated and the arithmetic is exact, so the ranks' tables stay identical - and no
- * collective is issued.  The host library's operators do not use this call (yet): they keep to helm_si_apply_luts. */
+ * count, not by count * n_out.  Under an exchange (helm_si_set_exchange*) a batch of at least min_batch
+ * ciphertexts is sharded as helm_si_apply_luts shards: `world` contiguous chunks of ciphertexts, this rank keyswitches and
+ * rotates its chunk only, its chunk * n_out extracted rows go into its exchange slot (row g * n_out + x of the chunk), the
+ * collective runs, and the gathered rows are scattered to out_idx without the -1 outputs.  capacity_rows counts rows: a round
+ * holds at most capacity_rows / n_out ciphertexts per rank (larger batches go in several rounds), and n_out > capacity_rows
+ * is HELM_ERR_INVALID.  This rank keyswitches its share of every round before the first round is scattered, so the table is
+ * word for word what the unsharded call leaves - also where an output row of an early ciphertext is the input row of a later
+ * one.  helm_si_exchange_stats counts these rounds and rows; pbs_count rises by this rank's ciphertexts.  The host library's
+ * operators use this call on request (helm_host_si_circuit_set_many_lut, helm_host_radix_level_ex in helm_host.h). */
 int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
                             const int32_t *out_idx, int32_t n_out, int64_t count, const uint64_t *luts, int64_t n_luts);
 
@@ -213,6 +219,20 @@ int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
  * table[g] holds the truth table as bits (bit i = entry i), in_idx is [count][max_in]. */
 int helm_si_eval_lut_level(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *arity, const int32_t *in_idx,
                            int32_t max_in, const uint64_t *table, const int32_t *out_idx, int64_t count);
+/* LUT levels that share rotations (default 0: off; a lane forked afterwards inherits the setting).  With on != 0,
+ * helm_si_eval_lut_level groups the bootstrapped gates of a level that have the same arity and the identical input rows in the
+ * same order: they pack the same index, which is below 2^arity, so up to M = t >> arity of them (the largest M with
+ * 2^arity <= t / M; t = message_modulus * carry_modulus) are the functions of one many-LUT table and cost ONE blind rotation -
+ * M = 2 for arity 3 and M <= 4 for arity 2 at t = 16, M = 2 for arity 2 at t = 8, no grouping at t = 4 or where
+ * 2^arity = t.  A full adder (0x96 and 0xE8 on the same three inputs) is one rotation instead of two.  The index of a group is
+ * packed once, into its first gate's output row; the level's groups are the jobs of ONE helm_si_apply_many_luts dispatch
+ * (sharded and audited as that call: kind 2 records) with n_out = M_d, the largest group's power of two: gate i of a group
+ * of n is output i * M_d / M_n (M_n = the power of two >= n), the other outputs are skipped.  A gate without a partner rides
+ * in the same dispatch with helm_si_make_lut's table and output 0 only: its row is word for word what the setting off
+ * gives.  A level without any group is evaluated exactly as with the setting off (helm_si_apply_luts).  Gates of arity 0 / 1,
+ * flip-flops and every refusal of helm_si_eval_lut_level are unchanged.  Test polynomials are built once per distinct tuple
+ * of functions per level. */
+int helm_si_set_level_many_lut(helm_si_ctx *ctx, int on);
 
 /* Multi-GPU (one process per GPU, keys and wire tables replicated): after this call every
  * bootstrap batch of at least `min_batch` ciphertexts - helm_si_apply_luts() and everything

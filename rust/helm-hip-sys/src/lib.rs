@@ -79,6 +79,7 @@ pub const HELM_RADIX_MUL_SCALAR: i32 = 9;
 pub const HELM_RADIX_DIV_SCALAR: i32 = 10;
 pub const HELM_RADIX_SHL_SCALAR: i32 = 11;
 pub const HELM_RADIX_SHR_SCALAR: i32 = 12;
+pub const HELM_RADIX_MANY_LUT: c_int = 1; // flags of helm_host_radix_level_ex
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct helm_radix_op {
@@ -170,6 +171,9 @@ extern "C" {
     pub fn helm_host_radix_scratch_rows(ctx: *mut helm_si_ctx, blocks: i32, ops: *const helm_radix_op, count: i64) -> i64;
     pub fn helm_host_radix_level(ctx: *mut helm_si_ctx, wires: *mut helm_si_wires, blocks: i32, ops: *const helm_radix_op,
                                  count: i64, scratch_first_row: i32, pbs_out: *mut i64, rounds_out: *mut i64) -> c_int;
+    // ... with flags: HELM_RADIX_MANY_LUT = carry propagation's first round on the many-LUT bootstrap (one rotation per block)
+    pub fn helm_host_radix_level_ex(ctx: *mut helm_si_ctx, wires: *mut helm_si_wires, blocks: i32, ops: *const helm_radix_op,
+                                    count: i64, scratch_first_row: i32, pbs_out: *mut i64, rounds_out: *mut i64, flags: c_int) -> c_int;
 
     // whole-circuit arithmetic / LUT evaluation inside the host library (merged rounds, carry-save planning): the netlist is
     // parsed by the library from the same file; client_key = NULL makes an evaluation-only circuit
@@ -184,6 +188,7 @@ extern "C" {
     pub fn helm_host_si_circuit_new(mode: c_int, client_key: *mut helm_si_client_key, server_key: *mut helm_si_ctx, circuit: *const helm_circuit,
                                     out: *mut *mut helm_si_circuit) -> c_int;
     pub fn helm_host_si_circuit_free(c: *mut helm_si_circuit);
+    pub fn helm_host_si_circuit_set_many_lut(c: *mut helm_si_circuit, on: c_int) -> c_int; // rotations shared through many-LUT
     pub fn helm_host_si_circuit_evaluate_encrypted(c: *mut helm_si_circuit, enc_wire_map: *const helm_si_enc_map,
                                                    current_cycle: i64, ptxt_type: *const c_char,
                                                    out: *mut *mut helm_si_enc_map) -> c_int;
@@ -215,6 +220,8 @@ extern "C" {
     pub fn helm_si_wires_set_trivial(ctx: *mut helm_si_ctx, w: *mut helm_si_wires, idx: *const i32, value: *const u64, count: i64) -> c_int;
     pub fn helm_si_eval_lut_level(ctx: *mut helm_si_ctx, w: *mut helm_si_wires, arity: *const i32, in_idx: *const i32, max_in: c_int,
                                   table: *const u64, out_idx: *const i32, count: i64) -> c_int;
+    // gates of a level on the same inputs share one blind rotation (default 0)
+    pub fn helm_si_set_level_many_lut(ctx: *mut helm_si_ctx, on: c_int) -> c_int;
     // many-LUT bootstrap (generate_many_lookup_table / apply_many_lookup_table of later tfhe releases): n_out functions of
     // one input, below t / M, from one blind rotation
     pub fn helm_si_make_many_lut(ctx: *const helm_si_ctx, f_values: *const u64, n_funcs: i32, test_poly_out: *mut u64) -> c_int;

@@ -26,6 +26,7 @@ pub struct HipArithCircuit<'a> {
     row_words: usize,
     scratch_first_row: i32,
     evaluated_cycle: Option<usize>,
+    many_lut: bool, // set_many_lut: flags of helm_host_radix_level_ex
 }
 
 fn is_numeric_string(s: &str) -> bool { s.chars().all(|c| c.is_ascii_digit()) } // circuit.rs:100-102
@@ -42,7 +43,14 @@ impl<'a> HipArithCircuit<'a> {
         crate::check(unsafe { sys::helm_si_load_keyswitch_key(ctx, keys.ksk.as_ptr(), keys.ksk.len()) });
         let row_words = (keys.params.k * keys.params.N) as usize + 1;
         HipArithCircuit { circuit, client_key, ctx, wires: std::ptr::null_mut(), row_of: HashMap::new(), blocks: 0,
-                          row_words, scratch_first_row: 0, evaluated_cycle: None }
+                          row_words, scratch_first_row: 0, evaluated_cycle: None, many_lut: false }
+    }
+
+    /// Carry propagation's first round on the many-LUT bootstrap: a block's message and carry state from ONE blind rotation
+    /// (helm_host_radix_level_ex with HELM_RADIX_MANY_LUT).  Default off; same values on every wire.
+    pub fn set_many_lut(&mut self, on: bool) {
+        self.many_lut = on;
+        self.evaluated_cycle = None;
     }
 
     /// The operators of one level as the engine's structs: an all-digit operand is a plaintext scalar
@@ -134,8 +142,9 @@ impl<'a> EvalCircuit<DeviceWire> for HipArithCircuit<'a> {
         for (level, gates) in levels {
             let ops = self.level_ops(gates, 2 * self.blocks as u32);
             let (mut pbs, mut rounds) = (0i64, 0i64);
-            check_host(unsafe { sys::helm_host_radix_level(self.ctx, self.wires, self.blocks, ops.as_ptr(), ops.len() as i64,
-                                                           self.scratch_first_row, &mut pbs, &mut rounds) });
+            let flags = if self.many_lut { sys::HELM_RADIX_MANY_LUT } else { 0 };
+            check_host(unsafe { sys::helm_host_radix_level_ex(self.ctx, self.wires, self.blocks, ops.as_ptr(), ops.len() as i64,
+                                                              self.scratch_first_row, &mut pbs, &mut rounds, flags) });
             println!("  Evaluated gates in level [{}/{}]", level, total_levels);
         }
         crate::check(unsafe { sys::helm_si_sync(self.ctx) });

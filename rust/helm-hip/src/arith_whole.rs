@@ -51,6 +51,12 @@ impl HipArithCircuitWhole {
         HipArithCircuitWhole { client_key, ctx, circuit, evaluator, row_words }
     }
 
+    /// Carry propagation's first round on the many-LUT bootstrap (helm_host_si_circuit_set_many_lut): one blind rotation per
+    /// block instead of two look-ups.  Default off; same values on every wire; resets the same-cycle memo.
+    pub fn set_many_lut(&mut self, on: bool) {
+        check_host(unsafe { sys::helm_host_si_circuit_set_many_lut(self.evaluator, on as i32) });
+    }
+
     /// circuit.rs:1113-1191 + 1198-1483 in one call: every wire of `wire_set` goes in (inputs encrypted under tfhe's key,
     /// the others as trivial zeros, as the reference's encrypt_inputs leaves them), every wire comes back.
     pub fn evaluate(&mut self, wire_set: &HashSet<String>, inputs: &HashMap<String, PtxtType>, cycle: usize, ptxt_type: &str)

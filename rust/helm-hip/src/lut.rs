@@ -39,6 +39,13 @@ impl<'a> HipLutCircuit<'a> {
                         evaluated_cycle: None }
     }
 
+    /// Gates of a level on the same inputs share one blind rotation (helm_si_set_level_many_lut): a full adder's sum and
+    /// carry cost one bootstrap instead of two.  Default off; same values on every wire.
+    pub fn set_many_lut(&mut self, on: bool) {
+        check(unsafe { sys::helm_si_set_level_many_lut(self.ctx, on as i32) });
+        self.evaluated_cycle = None;
+    }
+
     fn upload(&mut self, rows: &[i32], values: &[u64]) {
         let mut words = Vec::with_capacity(rows.len() * self.row_words);
         for v in values {
