@@ -744,7 +744,12 @@ __device__ __forceinline__ void lift_pairs(const double (&mine)[C::GS::E], const
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const double r0 = f == 0 ? own[u] : oth[u], r1 = f == 0 ? oth[u] : own[u];
-            const double t = mulmod<F1>(r1 - r0, p0inv_mod_p1);
+            // The quotient leaves mulmod within (0.5 + 0.75 |r1 - r0| 2^-52) p1 = 0.61 p1, so taken as it comes the lifted
+            // value is the exact integer only up to 0.78 of p0 p1 / 2: enough for the classical step (ADD), whose shapes end
+            // at 0.71 of it by their creation bound.  The multi-bit group step is admitted by its key up to the half itself
+            // (helm_si_load_bootstrap_key) and recentres the quotient, as k_pbs64_generic does.
+            const double tq = mulmod<F1>(r1 - r0, p0inv_mod_p1);
+            const double t = ADD ? tq : reduce<F1>(tq);
             const uint64_t xv = (uint64_t)to_int64(r0) + F0::P_U64 * (uint64_t)to_int64(t);
             uint64_t *dst = acc_p + u * (N / 2) + s * 64 + lane;
             *dst = ADD ? *dst + xv : xv;
@@ -2768,19 +2773,20 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
     if (int rc = begin_key_load(ctx, "helm_si_load_bootstrap_key")) return rc;
-    if (K.gen && K.group > 1) {
-        // The generic kernel's multi-bit form sums the 2^g subsets' products of a group before the CRT lift, so a step is the
-        // 2^g GGSWs of a group (src is [t][S][lev][r][c][N]).  The creation-time capacity check does not carry the factor 2^g
-        // (a worst case no honest key comes near: a uniformly random key of k = 1, N = 2048, logB = 21, g = 3 stays at 0.71 of
-        // the limit); this one is sufficient for the key at hand and every input.  A key beyond it is refused and the context
-        // keeps its state.
+    if (K.group > 1) {
+        // Both multi-bit kernels (k_pbs64s<., true> and the generic kernel's multi-bit form) sum the 2^g subsets' products of a
+        // group before the CRT lift, so a step is the 2^g GGSWs of a group (src is [t][S][lev][r][c][N]).  The creation-time
+        // capacity check does not carry the factor 2^g (a worst case no honest key comes near: a uniformly random key of k = 1,
+        // N = 2048, logB = 21, g = 3 stays at 0.71 of the limit); this one is sufficient for the key at hand and every input.
+        // A key beyond it is refused before anything of the context is touched: the context keeps the key and state it had.
         const size_t subsets = (size_t)1 << K.group;
         const long double key_bound = key_step_bound(P, bsk_std, n_ggsw / subsets, subsets * per_ggsw);
         if (key_bound * 1.001L >= (long double)F0::P * (long double)F1::P / 2) {
             char ratio[32];
             snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / ((long double)F0::P * (long double)F1::P / 2));
-            return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the generic multi-bit "
-                                                      "kernel: its largest group sum is ") + ratio + " of p0 p1 / 2");
+            return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the ") +
+                                              (K.gen ? "generic" : "tuned") + " multi-bit kernel: its largest group sum is " +
+                                              ratio + " of p0 p1 / 2");
         }
     }
     struct Tmp {

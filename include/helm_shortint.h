@@ -101,7 +101,7 @@ enum {
  * domain runs generic - also a tuned classical shape whose multi-bit form does not exist (k = 1, N = 512; pbs_l = 2); with
  * FORCE every launch runs generic, the tuned multi-bit sets included.  Shapes with grouping_factor <= 1 behave exactly as
  * without the bit, and without the bit every multi-bit refusal above stands.  The creation-time capacity bound is only a
- * necessary condition for a generic multi-bit context: a group step sums 2^grouping_factor subsets' products, so
+ * necessary condition for a multi-bit context, tuned or generic: a group step sums 2^grouping_factor subsets' products, so
  * helm_si_load_bootstrap_key checks the key at hand - B/2 x the largest l1-norm (key words as centred 64-bit integers) over
  * the polynomials of a group, all subsets and levels, that meet in one column or one row must stay below
  * p0 p1 / 2 / 1.001 - and otherwise returns HELM_ERR_INVALID ("... capacity ...") and leaves the context as it was, usable

@@ -14,8 +14,8 @@ Keys that follow the loaded key (N = 1024 boolean: the lazy field FpI; k_pbs64k 
 placed just under and just over the loaders' thresholds.  One child process repeats every case the bound-counting build
 (libhelm_hip_check.so) admits and requires all of its counters at zero.
 
-Out of scope, still: the multi-bit sets (si_toy_1024_mb2, si_toy_2048_mb3), whose nested key sums need another
-construction.  The keyswitch has its own edge construction: tests/ks_edges.py, tests/test_gpu_keyswitch_edges.py.  This
+The multi-bit kernels (k_pbs64s<., true>, k_pbs64_generic<LOGN, 2 | 3>), whose group sums need another construction, have
+theirs: tests/saturation_mb.py, tests/test_gpu_multibit_saturation.py.  The keyswitch has its own edge construction: tests/ks_edges.py, tests/test_gpu_keyswitch_edges.py.  This
 file runs MODE 0 of k_pbs64 only (pbs_l 1 and 2); MODE 1 and MODE 2 - the blind rotation and the CMUX tree of vertical packing,
 with Pbs64Cfg<., 3> and cbs_logB - have theirs: tests/vp_edges.py, tests/test_gpu_vertical_packing_edges.py."""
 import contextlib
