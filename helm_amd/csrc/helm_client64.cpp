@@ -99,6 +99,30 @@ int helm_si_client_named_params(const char *name, helm_si_params *p, double *lwe
         p->grouping_factor = 2;
         *lwe_std = 1e-9;
         *glwe_std = 1e-15;
+    } else if (s == "shortint_m2c3") {
+        // A 5-bit set, message_modulus 4 x carry_modulus 8 (tfhe's PARAM_MESSAGE_2_CARRY_3_KS_PBS): k = 1, N = 4096, one PBS
+        // level of 22 bits [shape recalled; n, the keyswitch decomposition and both noise values are NOT recalled: an
+        // approximate set, chosen as shortint_m2c1's were.  Taken here: n = 1024 (the engine's limit) with an LWE noise
+        // extrapolated along tfhe's security line through its n = 684 (2.04e-5) and n = 742 (7.07e-6) sets -
+        // log2 sigma = -15.58 - 0.02643 (n - 684) gives 2^-24.56 = 4.0e-8 - a keyswitch of 8 levels x 3 bits (the engine's
+        // deepest), and tfhe's GLWE noise for N >= 4096, recalled as 2^-62 = 2.168e-19.
+        // By the formulas of tests/test_gpu_noise.py (variances, torus units): blind rotation 2^-27.6 (all of it the
+        // decomposition's rounding, n (1 + N/2) / (24 B^2): the key's noise through the digits is 2^-60.6), keyswitch 2^-31.7,
+        // modulus switch (1 + n/2) / (48 N^2) = 2^-20.6 - the dominant term.  Half a box is 1 / (4 t) = 2^-7 at t = 32.
+        // Failure probability per look-up: 2^-72 on one look-up output or a fresh encryption (sigma 2^-10.3: 9.8 standard
+        // deviations), 2^-70 on a bivariate operand, 2^-63 on 4x + 2y + z of three outputs - and 2^-21.6 on
+        // 16x + 8y + 4z + 2u + v of FIVE look-up outputs, where 341 x the blind rotation's rounding (2^-19.2) takes over: a
+        // chain of 5-input gates wants a finer PBS decomposition than the recalled 22 x 1, which the capacity of the
+        // kernel's pair stops at (23 x 1 is refused); 5-input gates on fresh inputs are at 2^-72]
+        p->n = 1024; p->N = 4096; p->pbs_l = 1; p->pbs_logB = 22; p->ks_l = 8; p->ks_logB = 3;
+        p->carry_modulus = 8;
+        *lwe_std = 0.00000004;
+        *glwe_std = 0.0000000000000000002168404344971009;
+    } else if (s == "si_toy_4096") { // shortint_m2c3's shape at toy size (oracle-sized): 32 plaintext values
+        p->n = 12; p->N = 4096; p->pbs_l = 1; p->pbs_logB = 22; p->ks_l = 3; p->ks_logB = 5;
+        p->carry_modulus = 8;
+        *lwe_std = 1e-9;
+        *glwe_std = 1e-17;
     } else if (s == "si_toy_512") {
         p->n = 12; p->N = 512; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 4; p->ks_logB = 4;
         *lwe_std = 1e-9;

@@ -1555,7 +1555,7 @@ struct SiKeyState {
     double n_inv[2] = {0, 0}, two32[2] = {0, 0};
     double p0inv_mod_p1 = 0;
     int pair = 0;                // CRT pair of the tables above: 0 = FpG / FpG2 (49 bits), 1 = FpJ / FpJ2 (46 bits: k_pbs64k contexts
-                                 // whose loaded key fits, helm_si_load_bootstrap_key)
+                                 // whose loaded key fits, helm_si_load_bootstrap_key), 2 = FpG / FpI (k_pbs64_large: N = 4096)
     double *bsk = nullptr;
     double *bsk_split = nullptr; // layout of k_pbs64s (N >= 1024, pbs_l = 1)
     double *tw_sub = nullptr;    // derived half-transform tables [2 fields][2 halves][N/2]
@@ -1571,6 +1571,11 @@ struct SiKeyState {
     size_t gen_lds = 0;                   // LDS bytes per workgroup (Gen64Lds)
     int gen_per_cu = 1;                   // resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
     double *twi[2] = {nullptr, nullptr};  // bit-reversed powers of psi^-1 per field (the generic kernel's inverse transforms)
+    // helm_si_ctx_create_ex under HELM_SI_CREATE_LARGE_N at N = 4096: k_pbs64_large runs every bootstrap launch, in the pair
+    // FpG / FpI (pair 2), with the generic key layout (k_bsk_convert64_large) and the inverse tables above
+    bool large = false;
+    size_t large_lds = 0;                 // LDS bytes per workgroup (Large64Lds)
+    int large_per_cu = 1;                 // resident workgroups per CU
     uint64_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: eight byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0, ks_mfma = 1; // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
@@ -1834,6 +1839,25 @@ namespace {
 // k_pbs64_generic: k, pbs_l and pbs_logB at run time (helm_si_ctx_create_ex)
 #include "helm_pbs64_generic.inc"
 
+// k_pbs64_large: k = 1, N = 4096 (helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N)
+#include "helm_pbs64_large.inc"
+
+hipError_t launch_pbs64_large(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                              const uint64_t *luts, uint64_t *out, int *per_cu)
+{
+    // (the dynamic LDS attribute is set by helm_si_ctx_create_ex: setup_large)
+    const SiKeyState &K = *ctx->keys;
+    if (per_cu) {
+        *per_cu = K.large_per_cu;
+        return hipSuccess;
+    }
+    if (ctx->logN != 12 || ctx->P.k != 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pbs64_large<12>, dim3((unsigned)count), dim3(L64_THREADS), K.large_lds, ctx->stream, jobs, small, luts,
+                       K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], out, ctx->P.n, ctx->P.pbs_l, ctx->P.pbs_logB,
+                       K.p0inv_mod_p1);
+    return hipGetLastError();
+}
+
 template <int LOGN, int GG>
 hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                                   const uint64_t *luts, uint64_t *out)
@@ -1889,6 +1913,7 @@ const void *pbs64_generic_kernel(int logN, int group)
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                         const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
+    if (ctx->keys->large) return launch_pbs64_large(ctx, jobs, count, small, luts, out, per_cu);
     if (ctx->keys->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
     const helm_si_params &P = ctx->P;
     if (si_ilp_shape(ctx)) return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu);
@@ -2351,15 +2376,20 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
     return slot_end(ctx, *S);
 }
 
-uint64_t si_modulus(int pair, int f) { return pair ? (f ? J1::P_U64 : J0::P_U64) : (f ? F1::P_U64 : F0::P_U64); }
+uint64_t si_modulus(int pair, int f)
+{
+    if (pair == 2) return f ? L1::P_U64 : L0::P_U64;
+    return pair ? (f ? J1::P_U64 : J0::P_U64) : (f ? F1::P_U64 : F0::P_U64);
+}
 
 // psi of field f of a pair: a primitive 2N-th root of unity.  pair 1 (the 46-bit fields): the one with psi^(N/4) = b - it is
 // one of the primitive eighth roots b, b^3, -b, -b^3, and an odd power of psi puts it on b.  0: there is none.
 uint64_t si_psi(int N, int pair, int f)
 {
-    const uint64_t p = si_modulus(pair, f), gen = pair ? (f ? J1::GEN : J0::GEN) : (f ? F1::GEN : F0::GEN);
+    const uint64_t p = si_modulus(pair, f);
+    const uint64_t gen = pair == 2 ? (f ? L1::GEN : L0::GEN) : pair ? (f ? J1::GEN : J0::GEN) : (f ? F1::GEN : F0::GEN);
     const uint64_t psi = powmod_u64(gen, (p - 1) / (2 * (uint64_t)N), p);
-    if (!pair) return psi;
+    if (pair != 1) return psi;
     for (uint64_t t = 1; t < 8; t += 2)
         if (powmod_u64(powmod_u64(psi, t, p), (uint64_t)N / 4, p) == (uint64_t)(f ? J1::B1 : J0::B1)) return powmod_u64(psi, t, p);
     return 0;
@@ -2389,7 +2419,7 @@ int setup_pair_tables(helm_si_ctx *ctx, int pair)
         if (!psi) return fail(HELM_ERR_STATE, "internal: no 2N-th root of unity with psi^(N/4) = b");
         std::vector<double> tf(N);
         power_table(tf.data(), psi, pm[f], N, ctx->logN);
-        if (pair && (tf[1] != b2[f] || tf[2] != b1[f] || tf[3] != b3[f]))
+        if (pair == 1 && (tf[1] != b2[f] || tf[2] != b1[f] || tf[3] != b3[f]))
             return fail(HELM_ERR_STATE, "internal: the first twiddles are not the constants the kernels assume");
         K.n_inv[f] = centred(powmod_u64((uint64_t)N, pm[f] - 2, pm[f]), pm[f]);
         K.two32[f] = centred((1ull << 32) % pm[f], pm[f]);
@@ -2462,6 +2492,53 @@ int setup_generic(helm_si_ctx *ctx)
     return 0;
 }
 
+// the shapes k_pbs64_large takes (helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N): k = 1, N = 4096, classical blind rotation
+bool si_large_domain(const helm_si_params &P)
+{
+    return P.k == 1 && P.N == 4096 && P.pbs_l >= 1 && P.grouping_factor <= 1;
+}
+
+// A context whose launches run k_pbs64_large: the inverse twiddle tables of the pair FpG / FpI, the kernel's LDS attribute
+// and its occupancy.
+int setup_large(helm_si_ctx *ctx)
+{
+#ifdef HELM_CHECK_BOUNDS
+    // as setup_generic: the bound-checking build runs the tuned kernels only, and refuses before anything is launched
+    (void)ctx;
+    return fail(HELM_ERR_STATE, "the large-N kernel is not available in the bound-checking build (libhelm_hip_check.so): "
+                                "use the regular library for HELM_SI_CREATE_LARGE_N contexts");
+#else
+    SiKeyState &K = *ctx->keys;
+    const helm_si_params &P = ctx->P;
+    const int N = P.N, logN = ctx->logN;
+    for (int f = 0; f < 2; f++) {
+        const uint64_t p = si_modulus(2, f);
+        std::vector<double> ti(N);
+        power_table(ti.data(), powmod_u64(si_psi(N, 2, f), p - 2, p), p, N, logN);
+        if (!K.twi[f]) HIP_TRY(hipMalloc(&K.twi[f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(K.twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    // the attribute is the kernel's, shared by every context of the process: the layout at the largest n
+    static std::atomic<bool> attr_done[64];
+    const void *kern = reinterpret_cast<const void *>(k_pbs64_large<12>);
+    HIP_TRY(lds_attr_once(attr_done, ctx->device, {kern}, Large64Lds(N, 1024).bytes));
+    K.large_lds = Large64Lds(N, P.n).bytes;
+    int nb = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, L64_THREADS, K.large_lds));
+    if (nb < 1)
+        return fail(HELM_ERR_INVALID, "k_pbs64_large: no workgroup of " + std::to_string(K.large_lds) + " B LDS fits a CU");
+    K.large_per_cu = nb;
+    K.large = true;
+    if (getenv("HELM_HIP_VERBOSE")) {
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, kern);
+        fprintf(stderr, "[helm_si] k_pbs64_large N=%d l=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.pbs_l,
+                K.large_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.large_per_cu);
+    }
+    return 0;
+#endif
+}
+
 // The step bound of a bootstrapping key: the exact integer coefficient of one blind-rotation step is at most B/2 x the largest
 // l1-norm over the key polynomials (taken as centred 64-bit words) that meet in one output column - or, transposed, in one row.
 // A step sums `per_step` polynomials, laid out [...][r][c][N] (classical: the pbs_l (k+1)^2 of one GGSW; the generic multi-bit
@@ -2520,10 +2597,16 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
     const helm_si_params &P = *params;
-    if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT))
+    // HELM_SI_CREATE_LARGE_N matters at N >= 4096 only: below, the call is the same call without the bit
+    const bool large = (flags & HELM_SI_CREATE_LARGE_N) != 0 && P.N >= 4096;
+    if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT |
+                  HELM_SI_CREATE_LARGE_N))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
                                           " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2, "
-                                          "HELM_SI_CREATE_GENERIC_MULTIBIT = 16; 4 and 8 are reserved)");
+                                          "HELM_SI_CREATE_GENERIC_MULTIBIT = 16" +
+                                          ((flags & HELM_SI_CREATE_LARGE_N) ? ", HELM_SI_CREATE_LARGE_N = 32" : "") +
+                                          "; 4 and 8 are reserved)");
+    flags &= ~HELM_SI_CREATE_LARGE_N;
     const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
     const bool multibit = (flags & HELM_SI_CREATE_GENERIC_MULTIBIT) != 0;
     if (multibit && !(flags & (HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC)))
@@ -2532,13 +2615,17 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (force && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "HELM_SI_CREATE_FORCE_GENERIC: the generic kernel has no multi-bit form (grouping_factor > 1)");
     // with HELM_SI_CREATE_GENERIC_MULTIBIT a multi-bit shape is tuned only where the tuned multi-bit build serves it
-    const bool tuned = si_supported(P) && !(multibit && P.grouping_factor > 1 && !si_tuned_multibit(P));
+    if (large && !si_large_domain(P))
+        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the large-N kernel: its domain under HELM_SI_CREATE_LARGE_N is "
+                                      "k = 1, N = 4096, pbs_l >= 1, grouping_factor <= 1 (k > 1 at N = 4096, multi-bit at "
+                                      "N = 4096 and N = 8192 are out of scope)");
+    const bool tuned = large || (si_supported(P) && !(multibit && P.grouping_factor > 1 && !si_tuned_multibit(P)));
     if (!tuned && flags == 0)
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1; k = 2, N = 1024, pbs_l = 1");
     if (!tuned && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation (grouping_factor > 1) runs on the tuned builds only: this shape "
                                       "(k,N,pbs_l) has none, and the generic kernel has no multi-bit form");
-    const bool run_generic = force || !tuned;
+    const bool run_generic = !large && (force || !tuned); // (the large-N shape has one kernel, under every generic bit)
     const bool gen_mb = run_generic && multibit && P.grouping_factor > 1; // the generic kernel's multi-bit form
     if (gen_mb && (P.grouping_factor > 3 || P.n % P.grouping_factor))
         return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
@@ -2564,8 +2651,9 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     {
         const long double bound = (long double)(P.k + 1) * P.pbs_l * P.N * (long double)(1ull << (P.pbs_logB - 1)) *
                                   9223372036854775808.0L;
-        if (bound * 1.001L >= (long double)F0::P * (long double)F1::P / 2)
-            return fail(HELM_ERR_INVALID, "parameter set exceeds the two-prime NTT capacity");
+        // (a large-N context computes in its own pair: p0 p1 / 2 = 2^97.87)
+        const long double half = large ? (long double)L0::P * (long double)L1::P / 2 : (long double)F0::P * (long double)F1::P / 2;
+        if (bound * 1.001L >= half) return fail(HELM_ERR_INVALID, "parameter set exceeds the two-prime NTT capacity");
         // per-field operands: digits must be far below p
         if ((double)(1ull << (P.pbs_logB - 1)) * 4 >= F1::P / 2) return fail(HELM_ERR_INVALID, "pbs_logB too large");
     }
@@ -2595,9 +2683,15 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
     const int N = P.N;
-    if (int rc = setup_pair_tables(ctx, 0)) {
+    if (int rc = setup_pair_tables(ctx, large ? 2 : 0)) {
         (void)helm_si_ctx_destroy(ctx);
         return rc;
+    }
+    if (large) {
+        if (int rc = setup_large(ctx)) {
+            (void)helm_si_ctx_destroy(ctx);
+            return rc;
+        }
     }
     if (run_generic) {
         if (int rc = setup_generic(ctx)) {
@@ -2617,7 +2711,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     K.use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
     if (const char *v = getenv("HELM_HIP_KS_MFMA")) K.ks_mfma = atoi(v);
     if (const char *v = getenv("HELM_SI_SPLIT")) K.use_split = (K.use_split && atoi(v) != 0) || group > 1;
-    if (K.gen) K.use_split = false; // (a generic context reads one key layout, multi-bit too)
+    if (K.gen || K.large) K.use_split = false; // (a generic or large-N context reads one key layout, multi-bit too)
     if (K.use_split) {
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
@@ -2716,13 +2810,13 @@ int helm_si_get_params(const helm_si_ctx *ctx, helm_si_params *out)
 int helm_si_field_bits(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->keys->pair ? 46 : 49;
+    return ctx->keys->pair == 2 ? 50 : ctx->keys->pair ? 46 : 49;
 }
 
 int helm_si_kernel_class(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->keys->gen ? 1 : 0;
+    return ctx->keys->large ? 2 : ctx->keys->gen ? 1 : 0;
 }
 
 int helm_si_set_stream(helm_si_ctx *ctx, void *hip_stream)
@@ -2813,7 +2907,10 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (K.gen) {
+    if (K.large) { // the generic layout in the pair FpG / FpI (k_bsk_convert64_large)
+        hipLaunchKernelGGL(k_bsk_convert64_large<12>, dim3((unsigned)polys), dim3(L64_THREADS), 0, ctx->stream, d_std, K.bsk,
+                           K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l);
+    } else if (K.gen) {
         // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
 #define GEN64_CONVERT(LN)                                                                                                 \
     hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(G64_THREADS), 0, ctx->stream, d_std, K.bsk,   \
@@ -2823,7 +2920,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         else if (ctx->logN == 10) GEN64_CONVERT(10);
         else GEN64_CONVERT(11);
 #undef GEN64_CONVERT
-    } else if (K.pair) { // (N = 512 only)
+    } else if (K.pair == 1) { // (N = 512 only)
         hipLaunchKernelGGL((k_bsk_convert64<J0, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[0],
                            K.n_inv[0], K.two32[0], (int)K1, P.pbs_l, 0);
         hipLaunchKernelGGL((k_bsk_convert64<J1, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[1],

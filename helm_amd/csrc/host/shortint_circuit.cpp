@@ -454,17 +454,26 @@ std::map<std::string, PtxtType> LutCircuit::decrypt_outputs(const SiEncWireMap &
 // ---------------------------------------------------------------------------------------
 // RadixEngine: level-batched radix-integer operators on rows of one ciphertext table.
 // An integer = `nb` consecutive rows (block 0 least significant), every block a shortint
-// with a 2-bit message (message_modulus 4) and value below 16.
+// with a 2-bit message (message_modulus 4) and value below 16 (carry_modulus 4, or 8 with the upper half unused).
 // ---------------------------------------------------------------------------------------
 RadixEngine::RadixEngine(helm_si_ctx *ctx, int nb) : ctx_(ctx), nb_(nb)
 {
     si_ok(helm_si_get_params(ctx, &P_), "get_params");
-    if (P_.message_modulus != 4 || P_.carry_modulus != 4)
-        throw Panic("the radix layer needs message_modulus = carry_modulus = 4 (PARAM_MESSAGE_2_CARRY_2)");
-    const int t = 16;
+    if (P_.message_modulus != 4 || (P_.carry_modulus != 4 && P_.carry_modulus != 8))
+        throw Panic("the radix layer needs message_modulus = 4 and carry_modulus = 4 (PARAM_MESSAGE_2_CARRY_2) or 8");
+    // The tables below are written for t = 16: values mod 32, 16 the padding bit, an entry 32 - x meaning -x, and a look-up
+    // at v in [16, 32) (V_3 only) answering -f(v - 16) through the negacyclic wrap.  At t = 32 (carry_modulus 8: values mod 64,
+    // 32 the padding bit) the same machine runs on the native encoding: an entry 32 - x becomes 64 - x, and what the wrap gave
+    // at v in [16, 32) is written into the table's upper half.  Every look-up input of the layer is non-negative and at most
+    // 30, and every other constant is a small positive one, so nothing else depends on t.
+    const int t = P_.message_modulus * P_.carry_modulus;
     auto add_lut = [&](auto f) {
         std::vector<uint64_t> vals((size_t)t);
-        for (int v = 0; v < t; v++) vals[(size_t)v] = (uint64_t)f(v);
+        for (int v = 0; v < 16; v++) {
+            const int e = (int)f(v), sv = e >= 16 ? e - 32 : e; // the entry as a signed value
+            vals[(size_t)v] = (uint64_t)((sv + 2 * t) % (2 * t));
+            if (t == 32) vals[(size_t)v + 16] = (uint64_t)((2 * t - sv) % (2 * t));
+        }
         const size_t at = luts_.size();
         luts_.resize(at + (size_t)P_.N);
         si_ok(helm_si_make_lut(ctx_, vals.data(), luts_.data() + at), "make_lut");
@@ -506,7 +515,8 @@ void RadixEngine::set_many_lut(bool on)
     many_lut_ = on;
     if (!on || lut_pair_[0] >= 0) return;
     // the pair tables join the table set only on request: with the setting off every call passes the tables it always did
-    const int per = 8; // t / 2: the input bound of a two-function table; block sums are <= 7 (propagate())
+    // t / 2: the input bound of a two-function table; block sums are <= 7 (propagate()), the entries from 8 on are never read
+    const int per = P_.message_modulus * P_.carry_modulus / 2;
     for (int p = 0; p < 4; p++) {
         std::vector<uint64_t> vals((size_t)2 * per);
         for (int v = 0; v < per; v++) {

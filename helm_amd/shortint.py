@@ -110,9 +110,12 @@ class SiClientKey:
 SI_CREATE_ALLOW_GENERIC = 1  # include/helm_shortint.h HELM_SI_CREATE_*
 SI_CREATE_FORCE_GENERIC = 2
 SI_CREATE_GENERIC_MULTIBIT = 16
+SI_CREATE_LARGE_N = 32
 _GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC,
                   "allow+multibit": SI_CREATE_ALLOW_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
-                  "force+multibit": SI_CREATE_FORCE_GENERIC | SI_CREATE_GENERIC_MULTIBIT}
+                  "force+multibit": SI_CREATE_FORCE_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
+                  "large": SI_CREATE_LARGE_N, "allow+large": SI_CREATE_ALLOW_GENERIC | SI_CREATE_LARGE_N,
+                  "force+large": SI_CREATE_FORCE_GENERIC | SI_CREATE_LARGE_N}
 
 
 class SiServerKey:
@@ -123,11 +126,15 @@ class SiServerKey:
     bootstrap on the generic kernel, tuned shapes too (HELM_SI_CREATE_FORCE_GENERIC).  "allow+multibit" and
     "force+multibit" add HELM_SI_CREATE_GENERIC_MULTIBIT: multi-bit shapes (grouping_factor 2 or 3) the tuned multi-bit
     build does not serve run on the generic kernel's multi-bit form, under "force+multibit" every multi-bit shape does; the
-    bootstrapping key must then pass the load-time capacity check (include/helm_shortint.h)."""
+    bootstrapping key must then pass the load-time capacity check (include/helm_shortint.h).  "large" (alone, or as
+    "allow+large" / "force+large" beside the generic settings) adds HELM_SI_CREATE_LARGE_N: k = 1, N = 4096 - the 5-bit sets,
+    message_modulus * carry_modulus = 32 - is admitted and runs on the large-N kernel; any smaller shape behaves as without
+    it.  Lanes inherit the setting."""
 
     def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, generic=None):
         if generic not in _GENERIC_FLAGS:
-            raise ValueError(f"generic must be None, 'allow', 'force', 'allow+multibit' or 'force+multibit', not {generic!r}")
+            raise ValueError("generic must be None, 'allow', 'force', 'allow+multibit', 'force+multibit', 'large', "
+                             f"'allow+large' or 'force+large', not {generic!r}")
         self.params = client_key.params if client_key is not None else params
         self.generic = generic
         h = nv.vp()
@@ -176,17 +183,18 @@ class SiServerKey:
         return v
 
     def field_bits(self):
-        """49 or 46: the CRT pair of prime fields this context's bootstrap kernels compute in (helm_si_field_bits: it follows
-        the loaded key for k > 1 contexts)."""
+        """49, 46 or 50: the CRT pair of prime fields this context's bootstrap kernels compute in (helm_si_field_bits: it
+        follows the loaded key for k > 1 contexts; 50 is the large-N kernel's pair)."""
         return int(hip.helm_si_field_bits(self._h))
 
     def kernel_class(self):
         """"tuned" when a tuned bootstrap build runs this context's launches, "generic" when the generic kernel does (a shape
-        no tuned build covers under generic="allow", or any shape under generic="force"; helm_si_kernel_class)."""
+        no tuned build covers under generic="allow", or any shape under generic="force"), "large" when the large-N kernel
+        does (k = 1, N = 4096 under generic="large"; helm_si_kernel_class)."""
         v = int(hip.helm_si_kernel_class(self._h))
         if v < 0:
             hip_check(v)
-        return "generic" if v == 1 else "tuned"
+        return "large" if v == 2 else "generic" if v == 1 else "tuned"
 
     def set_level_many_lut(self, on=True):
         """helm_si_set_level_many_lut: SiWires.eval_lut_level groups the gates of a level that have the same inputs in the same

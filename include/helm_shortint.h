@@ -81,7 +81,8 @@ enum {
     HELM_SI_CREATE_ALLOW_GENERIC = 1, /* admit shapes no tuned build covers: they run on the generic kernel */
     HELM_SI_CREATE_FORCE_GENERIC = 2, /* run every launch on the generic kernel, tuned shapes too (implies 1) */
     /* 4 and 8 are reserved: refused as unknown bits */
-    HELM_SI_CREATE_GENERIC_MULTIBIT = 16 /* with 1 or 2: multi-bit shapes may run on the generic kernel's multi-bit form */
+    HELM_SI_CREATE_GENERIC_MULTIBIT = 16, /* with 1 or 2: multi-bit shapes may run on the generic kernel's multi-bit form */
+    HELM_SI_CREATE_LARGE_N = 32 /* admit k = 1, N = 4096 (the 5-bit shortint sets): it runs on the large-N kernel */
 };
 /* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
  * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
@@ -107,9 +108,21 @@ enum {
  * p0 p1 / 2 / 1.001 - and otherwise returns HELM_ERR_INVALID ("... capacity ...") and leaves the context as it was, usable
  * for another key.  Keys with the noise and size of a tfhe parameter set stay well below it (about 0.71 of the limit for a
  * uniformly random key at k = 1, N = 2048, pbs_logB = 21, grouping_factor = 3).
+ * HELM_SI_CREATE_LARGE_N (alone or beside the bits above) admits the one shape above the generic domain: k = 1, N = 4096,
+ * pbs_l >= 1, grouping_factor <= 1 - every 5-bit set (message_modulus * carry_modulus = 32).  It matters at N >= 4096 only:
+ * on any smaller N the call is the same call without the bit, and without the bit every call is what it was.  With it, such
+ * a shape passes every other check of helm_si_ctx_create in the same order (n, the decompositions,
+ * message_modulus * carry_modulus <= N/2, and the capacity bound with the product of ITS pair of fields:
+ * 2 pbs_l N 2^(pbs_logB-1) 2^63 x 1.001 < p0 p1 / 2 = 2^97.87 - one level of 22 bits is at 0.547 of it, 23 bits are refused)
+ * and its bootstraps run on k_pbs64_large: one workgroup of 1024 threads per bootstrap, one per CU, in the pair 5072^4 + 1
+ * and 5440^4 + 1 (helm_si_field_bits() returns 50, helm_si_kernel_class() 2).  Everything above the bootstrap kernel works
+ * unchanged, many-LUT included.  Refused with a message that names the large-N domain: k > 1 at N = 4096, multi-bit at
+ * N = 4096, and N = 8192 (its accumulator alone is 128 KiB of LDS, and its products exceed the pair).  helm_wop_ctx_create
+ * refuses a PBS-side context of this class, and the bound-checking build refuses the class at creation.
  * Unknown flag bits (4 and 8 are reserved): HELM_ERR_INVALID. */
 int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
-/* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic).  Unlike
+/* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic), 2 = the large-N
+ * kernel (k_pbs64_large: k = 1, N = 4096 under HELM_SI_CREATE_LARGE_N, whatever generic bits stand beside it).  Unlike
  * helm_hip_kernel_class of the boolean engine, which reports the parameter shape only (its forcing is a debug variable),
  * this reports the kernel the launches actually run on: HELM_SI_CREATE_FORCE_GENERIC is part of this API, so a forced
  * tuned shape reports 1.  A lane reports its primary's class.  Negative on error. */
@@ -127,7 +140,8 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx);
 int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **lane_out);
 int helm_si_get_params(const helm_si_ctx *ctx, helm_si_params *out);
 /* The CRT pair of prime fields the bootstrap kernels of this context compute in, as its size class: 49 = 5072^4 + 1 and
- * 5096^4 + 1 (every parameter set), 46 = 2736^4 + 1 and 2872^4 + 1 - k > 1 contexts (k_pbs64k: the set reference
+ * 5096^4 + 1 (every parameter set up to N = 2048), 50 = 5072^4 + 1 and 5440^4 + 1 (the large-N kernel: N = 4096, where
+ * 5096^4 + 1 has no 2N-th root of unity; fixed for the context's life), 46 = 2736^4 + 1 and 2872^4 + 1 - k > 1 contexts (k_pbs64k: the set reference
  * src/bin/helm.rs:301 installs for LUT mode) whose LOADED key keeps the exact products of a blind-rotation step below
  * p p' / 2 = 2^90.6: helm_si_load_bootstrap_key computes B/2 x the largest l1-norm of a key column for the key at hand (an
  * exact guarantee for that key and every input; a generated key fits, the worst case of the set does not and keeps 49), so
@@ -294,7 +308,7 @@ int helm_si_set_audit(helm_si_ctx *ctx, helm_si_audit_fn fn, void *user);
 int helm_si_bound_violations(helm_si_ctx *ctx, uint32_t counts[8], int reset);
 
 /* Programmable bootstraps the device holds at once under this parameter set: CUs x workgroups of the set's bootstrap kernel
- * per CU (1 at N = 2048, 2 for k_pbs64k; on the generic kernel, its resident workgroups per CU at the context's LDS size).  A batch of at most this many ciphertexts takes one bootstrap's time whatever its
+ * per CU (1 at N = 2048, 2 for k_pbs64k; on the generic kernel, its resident workgroups per CU at the context's LDS size; 1 on the large-N kernel).  A batch of at most this many ciphertexts takes one bootstrap's time whatever its
  * size; the host library merges the look-up rounds of concurrent operators into launches of at most this size. */
 int64_t helm_si_round_capacity(helm_si_ctx *ctx);
 

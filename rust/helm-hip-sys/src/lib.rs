@@ -64,6 +64,7 @@ pub const HELM_GATE_CONST_ZERO: i32 = 12;
 pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
 pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
 pub const HELM_SI_CREATE_GENERIC_MULTIBIT: i32 = 16; // with one of the two above: the generic kernel's multi-bit form
+pub const HELM_SI_CREATE_LARGE_N: i32 = 32; // admit k = 1, N = 4096 (the 5-bit shortint sets): the large-N kernel
 
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
