@@ -239,21 +239,22 @@ def keyswitch_plain(row, key, logB, l, width, body=True):
     return out
 
 
-def keyswitch_exact(rows, key, logB, l, width, body=True):
+def keyswitch_exact(rows, key, logB, l, width, body=True, limb=16):
     """Whole launches: the same sums with the key cut into 16-bit limbs, so that every partial sum (|digit| <= 2^(logB-1),
     limb < 2^16, in_dim x l terms) stays below 2^53 and is exact as a float64 matrix product; the limbs are recombined
-    mod 2^w in unsigned wrapping arithmetic.  -> [rows, out_words] words"""
+    mod 2^w in unsigned wrapping arithmetic.  limb=8: narrower limbs, for the packing keyswitch's digits of up to 30 bits.
+    -> [rows, out_words] words"""
     key = np.asarray(key)
     in_dim, _, out_words = key.shape
     rows = np.asarray(rows)
-    assert in_dim * l * (1 << (logB - 1)) * (1 << 16) < (1 << 53)
+    assert limb in (8, 16) and in_dim * l * (1 << (logB - 1)) * (1 << limb) < (1 << 53)
     D = digits_rows(rows[:, :in_dim], logB, l, width).reshape(len(rows), in_dim * l).astype(np.float64)
     K = key.reshape(in_dim * l, out_words).astype(np.uint64)
     total = np.zeros((len(rows), out_words), dtype=np.uint64)
-    for i in range(width // 16):
-        limb = ((K >> np.uint64(16 * i)) & np.uint64(0xFFFF)).astype(np.float64)
-        part = (D @ limb).astype(np.int64)                                                   # exact: see the assert
-        total += part.astype(np.uint64) << np.uint64(16 * i)                                 # two's complement, wrapping
+    for i in range(width // limb):
+        piece = ((K >> np.uint64(limb * i)) & np.uint64((1 << limb) - 1)).astype(np.float64)
+        part = (D @ piece).astype(np.int64)                                                  # exact: see the assert
+        total += part.astype(np.uint64) << np.uint64(limb * i)                               # two's complement, wrapping
     out = np.uint64(0) - total
     if body:
         out[:, out_words - 1] += rows[:, in_dim].astype(np.uint64)

@@ -270,8 +270,8 @@ def test_wop_packing_keyswitch_under_extreme_key_bytes(wop_side, l, logB):
     packing keys of extreme bytes: a batch of 5 (k_pfpks64<l>) and of 70 (pfks_logB <= 15: k_pfpks_digits<l> + k_ks64_mfma on
     the byte planes k_pfpks_planes built; above 15 the loader builds no planes - the high byte of a digit would not fit
     [-64, 64] - and k_pfpks64<l> serves every width) against the oracle under the same key, and against each other.  The
-    rows the packing keyswitch reads are bootstrap outputs - the ABI has no entry that feeds it chosen rows, so the crafted
-    rows of ks_edges reach its oracle and its byte split on the CPU only (tests/test_keyswitch_edges.py)."""
+    rows the packing keyswitch reads here are the bootstrap outputs of an honest key: uniform words.  The crafted rows of
+    ks_edges reach it on the device through a programmed bootstrapping key, in tests/test_gpu_wop_programmed_rows.py."""
     ck, sk = wop_side
     wp, c, d = wopbs.wop_named_params("wop_toy_512")
     assert (wp.pfks_l, wp.pfks_logB) == PFKS[0]

@@ -22,7 +22,7 @@ three gates), the crafted gates at both ends of a batch of seven (the per-gate k
 process on the bound-counting build (libhelm_hip_check.so) that repeats the six per-shape launches and requires every
 counter at zero.
 
-Out of scope: the chunk boundary of helm_wop_eval_luts and its sharded form; multi-bit saturation."""
+Out of scope: the sharded form of helm_wop_eval_luts (its chunk boundary: tests/test_gpu_wopbs.py); multi-bit saturation."""
 import json
 import os
 import subprocess

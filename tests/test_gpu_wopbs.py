@@ -185,6 +185,48 @@ def test_wide_lut_gates_bit_exact(toy, n_inputs, bits_per_block):
             assert np.array_equal(got[g], want), g
 
 
+def test_a_batch_across_the_gate_chunk_edge():
+    """helm_wop_eval_luts runs a call in passes of max(1, 16384 / bits) gates (tests/test_keyswitch_edges.py pins the rule to
+    the source), synchronising and reusing its scratch between passes, with per-pass offsets into the tables, the input
+    rows and out_idx.  At 12 index bits a pass is 1365 gates: 1367 gates in one call (passes of 1365 and 2) must give the rows
+    of the same gates issued in two calls that stay inside a pass (700 and 667 gates), bit for bit; so must a call of
+    exactly one pass, gates 2..1366.  Every gate has its own table and its own input tuple (three blocks of 0..15), decrypts
+    to its table entry, and the gates either side of the edge are the oracle's."""
+    ck, wk, sk, wsk, ow = make_keys("si_toy_512", "wop_toy_512", seed=61)
+    try:
+        n_inputs, bpb, count, chunk = 3, 4, 1367, 16384 // 12
+        assert chunk == 1365 and count == chunk + 2
+        rng = np.random.default_rng(61)
+        truth = rng.integers(0, 2, size=(count, 4 ** n_inputs), dtype=U64)
+        assert len({t.tobytes() for t in truth}) == count                        # a distinct table per gate
+        tuples = rng.permutation(16 ** n_inputs)[:count]                         # a distinct input tuple per gate
+        vals = np.array([[(int(x) >> (4 * (n_inputs - 1 - q))) & 15 for q in range(n_inputs)] for x in tuples], dtype=U64)
+        cts = ck.encrypt(vals.reshape(-1))
+        in_idx = np.arange(count * n_inputs, dtype=np.int32).reshape(count, n_inputs)
+        out_idx = np.arange(count * n_inputs, count * (n_inputs + 1), dtype=np.int32)
+
+        def run(lo, hi):
+            w = sk.wires(count * (n_inputs + 1))
+            w.upload(np.arange(count * n_inputs), cts)
+            wsk.eval_luts(w, in_idx[lo:hi], truth[lo:hi], out_idx[lo:hi], bits_per_block=bpb)
+            rows = w.download(out_idx[lo:hi])
+            w.free()
+            return rows
+
+        whole = run(0, count)
+        parts = np.concatenate([run(0, 700), run(700, count)])
+        assert np.array_equal(whole, parts), "gates %s differ across the chunk edge" % sorted({int(g) for g in np.argwhere(whole != parts)[:, 0]})[:8]
+        assert np.array_equal(run(2, count), parts[2:])                          # exactly one pass, at another offset
+        # the index rule (gates.rs:845-848): block j = input n - 1 - j, x = sum block_j 4^j mod 4^n
+        want = [int(truth[g, sum(int(v) * 4 ** j for j, v in enumerate(vals[g][::-1])) % 4 ** n_inputs]) for g in range(count)]
+        assert [int(v) for v in ck.decrypt_message_and_carry(whole)] == want
+        for g in (0, chunk - 1, chunk, chunk + 1):
+            assert np.array_equal(whole[g], ow.wide_lut(cts[g * n_inputs:(g + 1) * n_inputs], truth[g], bpb)), g
+    finally:
+        wsk.close()
+        sk.close()
+
+
 def test_reference_encoding_two_bits_per_block():
     """The encoding the reference's LUT mode names (helm.rs:301: message_modulus = carry_modulus = 2): six-input
     gates, two bits per block as tfhe extracts after the cleaning bootstrap = 12 index bits = a CMUX tree over

@@ -20,6 +20,7 @@ import oracle
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ks_edges as E  # noqa: E402
 import saturation as S  # noqa: E402
+import wop_program as W  # noqa: E402
 
 ALL_SHAPES = [(32, l, b) for l, b in E.ks_shapes(32)] + [(64, l, b) for l, b in E.ks_shapes(64)]
 
@@ -235,3 +236,119 @@ def test_wop_packing_keyswitch_oracle_is_the_integer_reference(l, logB):
             oracle.libw().orcw_pfpks(in_dim, glwe, l, logB, flat.ctypes.data_as(u64p), row.ctypes.data_as(u64p),
                                      out.ctypes.data_as(u64p))
             assert [int(v) for v in out] == E.keyswitch_plain(rows[r], key, logB, l, 64, body=False), (kind, r)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# chosen rows for the packing keyswitch through a programmed bootstrapping key (tests/wop_program.py)
+# ------------------------------------------------------------------------------------------------------------------
+def test_the_programme_digits_and_refusals():
+    """Between the three programmes every level of cbs_l = 2 and of cbs_l = 3 is a target (d = 1); the by-products' digits
+    are the powers of two the construction states; a level without a digit and a digit other than 1 are refused."""
+    shapes = {name: W.Shape(12, 512, *prm) for name, prm in W.PROGRAMMES.items()}
+    assert [W.level_digit(shapes["l2"], j) for j in range(2)] == [(0, 1), (1, 1)]
+    assert [W.level_digit(shapes["l3_01"], j) for j in range(3)] == [(0, 1), (1, 1), None]
+    assert [W.level_digit(shapes["l3_2"], j) for j in range(3)] == [(0, 1 << 10), (0, 1 << 5), (0, 1)]
+    assert [W.level_digit(W.Shape(12, 512, 2, 10, 3, 5), j) for j in range(3)] == [(0, 1 << 5), (0, 1), (1, 1 << 5)]
+    assert W.targeted_levels(shapes["l2"]) == [0, 1] and W.targeted_levels(shapes["l3_01"]) == [0, 1]
+    assert W.targeted_levels(shapes["l3_2"]) == [2]
+    row = np.arange(513, dtype=np.uint64)
+    with pytest.raises(ValueError, match="has no digit"):
+        W.program(shapes["l3_01"], [(0, 2, row)])
+    with pytest.raises(AssertionError, match="is no target"):
+        W.program(shapes["l3_2"], [(0, 0, row)])
+    with pytest.raises(ValueError, match="share the key row"):
+        W.program(W.Shape(12, 512, 2, 10, 3, 10), [(0, 0, row), (0, 0, row)])
+    with pytest.raises(ValueError, match="no such step"):
+        W.program(shapes["l2"], [(12, 0, row)])
+    # the input rows: one mask word at the rotation 1, the body 0 after the + q/4
+    rows = W.input_rows(shapes["l2"])
+    assert rows.shape == (12, 13) and int(rows[3, 3]) == 1 << 54 and (int(rows[3, 12]) + (1 << 62)) % (1 << 64) == 0
+    assert np.count_nonzero(rows[:, :12]) == 12
+
+
+@pytest.mark.parametrize("l,logB", W.PFKS, ids=lambda v: str(v))
+def test_the_programmed_key_feeds_the_packing_keyswitch_its_crafted_rows(l, logB):
+    """OracleW.circuit_bootstrap under the programmed key == the integer reference on the predicted rows, for every step
+    (crafted and control), every level (targets and by-products) and both packing keys r; the targeted rows are
+    crafted_rows(k N, logB, l, 64) word for word; under the "follow" key their byte-split plane accumulators reach what
+    test_the_packing_keyswitch_split_reaches_its_bytes asserts of the crafted rows."""
+    N = 512
+    cr = E.crafted_rows(N, logB, l, 64)
+    seen = set()
+    for name in W.PROGRAMMES:
+        shape, bsk, small, where = W.crafted_programme(name, N, l, logB)
+        steps = np.arange(shape.n)
+        pred = W.predicted_rows(shape, bsk, steps)
+        assert sorted({j for _, j in where}) == W.targeted_levels(shape) and len(where) == 8 * len(W.targeted_levels(shape))
+        for (i, j), r in where.items():
+            assert np.array_equal(pred[i, j, :N], cr[r, :N]) and int(pred[i, j, N]) & 1, (name, i, j)
+            seen.add((shape.cbs_l, j, r))
+        if name == "l3_01":
+            assert not pred[:, 2].any()                                          # the level without a digit: the zero row
+        flat = pred.reshape(-1, N + 1)
+        for kind in ("random", "ff", "follow"):
+            pf = E.make_key(kind, 2 * (N + 1), 2 * N, logB, l, 64).reshape(2, N + 1, l, 2 * N)
+            params = (shape.n, 1, N, shape.pbs_l, shape.pbs_logB, 4, 4, l, logB, shape.cbs_l, shape.cbs_logB, 4, 4)
+            ow = oracle.OracleW(params, bsk.reshape(-1), np.zeros(1, np.uint64), pf.reshape(-1))
+            got = np.stack([ow.circuit_bootstrap(small[i]) for i in steps])      # [step][level][r][2 N]
+            cols = [0, 1, 255, 256, N - 1, N, 2 * N - 1]
+            for r in range(2):
+                want = W.packing_reference(flat, pf[r], l, logB).reshape(shape.n, shape.cbs_l, 2 * N)
+                assert np.array_equal(got[:, :, r], want), (name, kind, r)
+                if logB == 30:                                                   # keyswitch_exact's 2^53 assertion fails here:
+                    for i, j in ((0, 0), (2, shape.cbs_l - 1), (7, 1), (shape.n - 1, 0)):   # Python integers on a column sample
+                        plain = E.keyswitch_plain(pred[i, j], pf[r][:, :, cols], logB, l, 64, body=False)
+                        assert [int(got[i, j, r, c]) for c in cols] == plain, (name, kind, r, i, j)
+        if logB <= 15:
+            # the reach of the two-byte split: the mask words' share of the bound - reach_fraction of the digits' magnitudes,
+            # of which a digit wider than a byte puts |hi| / (|hi| + 128) into the high byte (a digit of +-B/2 is all high
+            # byte) - less what the body word, an odd constant, can take away
+            follow = E.make_key("follow", N + 1, 3, logB, l, 64)
+            hi = 0 if logB < 8 else max(1, (1 << (logB - 1)) >> 8)
+            share = 1.0 if logB < 8 else hi / (hi + 128)
+            want = E.reach_fraction(l, logB) * share * E.pfks_plane_bound(N, l, logB) - E.pfks_plane_bound(1, l, logB)
+            top = max(int(np.abs(E.plane_accumulators(pred[i, j], follow, logB, l, 64, split_bytes=True)[0]).max())
+                      for (i, j) in where)
+            assert top >= want > 0, (name, top, want)
+            table = {(2, 15): 0.32, (4, 15): 0.32, (1, 15): 0.32, (4, 2): 0.74}     # the figures of the test named above
+            if (l, logB) in table:
+                assert want >= table[(l, logB)] * E.pfks_plane_bound(N + 1, l, logB)
+    # every (cbs_l, level, crafted row) is a target of some programme
+    assert seen == {(L, j, r) for L in (2, 3) for j in range(L) for r in range(8)}
+
+
+def test_the_exact_reference_in_narrow_limbs():
+    """keyswitch_exact(limb=8), what the device tests use at logB 30 == keyswitch_plain, whole rows at a small shape."""
+    for l, logB in ((2, 30), (1, 30), (3, 21)):
+        rows = E.crafted_rows(40, logB, l, 64)
+        for kind in E.KEYS:
+            key = E.make_key(kind, 41, 5, logB, l, 64)
+            fast = E.keyswitch_exact(rows, key, logB, l, 64, body=False, limb=8)
+            for r in range(len(rows)):
+                assert [int(v) for v in fast[r]] == E.keyswitch_plain(rows[r], key, logB, l, 64, body=False), (kind, r)
+
+
+def test_the_launch_rules_are_those_of_the_sources():
+    """wop_program's restatements of pfpks_on_matrix_cores, of the slicing of k_pfpks64's launches and of the gate chunk of
+    helm_wop_eval_luts, read back from helm_wopbs.inc (a tripwire on the text, as the admission rules above), and the
+    numbers the device tests build on."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    wop = open(os.path.join(root, "helm_amd", "csrc", "helm_wopbs.inc")).read()
+    assert "const int64_t chunk = std::max<int64_t>(1, 16384 / bits);" in wop
+    assert "for (int64_t base = 0; base < count; base += chunk)" in wop
+    assert "return ctx->d_pf_planes && ctx->wop->keys->ks_mfma && count >= 64;" in wop
+    assert wop.count("while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)W->n_cus && in_words / (slices * 2) >= 64) slices *= 2;") == 2
+    assert "const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((glwe_words + 255) / 256);" in wop
+    assert "if (gridDim.z == 1) *dst = 0ull - acc[g];" in wop
+    assert (W.gate_chunk(12), W.gate_chunk(1), W.gate_chunk(16385), W.gate_chunk(3)) == (1365, 16384, 1, 5461)
+    # N = 512: the grid is X workgroups wide in all, one slice from X = 2 n_cus on (256 compute units: 512)
+    assert [W.pfpks_slices(X, 512, 256) for X in (2, 66, 195, 508, 509, 512, 513)] == [8, 8, 4, 2, 1, 1, 1]
+    assert W.pfpks_slices(1, 2048, 256) == 16 and W.pfpks_slices(10 ** 6, 2048, 256) == 1
+    assert [W.pfpks_route(X, 15, 512, None) for X in (63, 64)] == ["valu", "mfma"]
+    assert W.pfpks_route(640, 15, 512, "0") == "valu" and W.pfpks_route(640, 21, 512, None) == "valu"
+    # crafted rows at the tile positions the device tests name
+    for bits, L, levels in ((32, 2, [0, 1]), (33, 2, [0, 1]), (21, 3, [0, 1]), (22, 3, [2]), (80, 2, [0, 1])):
+        steps, crafted = W.steps_for(bits, L, levels)
+        X = bits * L
+        assert len(steps) == bits and {x for x in (0, 15, 16, 63, 64) if x < X and x % L in levels} <= set(crafted)
+        assert any(x >= (X - 1) // 16 * 16 for x in crafted) and (steps >= 8).sum() >= bits // 4
