@@ -16,10 +16,11 @@ from .circuit import (Circuit, GateCircuit, EvalCircuit, EncWireMap, LutCircuit,
 from .gates import PtxtType, GateType, Gate  # noqa: F401,E402
 
 
-def gen_keys(name="boolean_default", seed=None, device=0):
-    """tfhe::boolean::gen_keys() (reference src/bin/helm.rs:241) -> (client_key, server_key)."""
+def gen_keys(name="boolean_default", seed=None, device=0, crt=None):
+    """tfhe::boolean::gen_keys() (reference src/bin/helm.rs:241) -> (client_key, server_key).  crt: ServerKey's option - the
+    sets beyond the single-prime capacity bound ("boolean_tfhe_lib", "toy_crt") need crt="allow"."""
     ck = ClientKey.generate(name, seed)
-    return ck, ServerKey(ck, device=device)
+    return ck, ServerKey(ck, device=device, crt=crt)
 
 
 def gen_keys_shortint(name="shortint_m2c2", seed=None, device=0):

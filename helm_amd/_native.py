@@ -164,12 +164,14 @@ HIP_API = {
     "helm_hip_device_count": (C.c_int, []),
     "helm_hip_runtime_copies": (C.c_int, [C.c_char_p, C.c_size_t]),
     "helm_hip_ctx_create": (C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(vp)]),
+    "helm_hip_ctx_create_ex": (C.c_int, [C.c_int, C.POINTER(Params), C.c_uint32, C.POINTER(vp)]),
     "helm_hip_ctx_destroy": (C.c_int, [vp]),
     "helm_hip_get_params": (C.c_int, [vp, C.POINTER(Params)]),
     "helm_hip_set_stream": (C.c_int, [vp, vp]),
     "helm_hip_sync": (C.c_int, [vp]),
     "helm_hip_launch_quantum": (C.c_int64, [vp]),
     "helm_hip_kernel_class": (C.c_int, [vp]),
+    "helm_hip_digit_batch": (C.c_int, [vp]),
     "helm_hip_launch_costs": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "helm_hip_field_bits": (C.c_int, [vp]),
     "helm_hip_short_root_stages": (C.c_int, [vp]),

@@ -72,6 +72,21 @@ int helm_client_named_params(const char *name, helm_hip_params *p, double *lwe_s
         p->n = 16; p->k = 1; p->N = 1024; p->pbs_l = 2; p->pbs_logB = 7; p->ks_l = 8; p->ks_logB = 2;
         *lwe_std = 1e-7;
         *glwe_std = 1e-9;
+    } else if (s == "boolean_tfhe_lib") {
+        // tfhe boolean::TFHE_LIB_PARAMETERS [recalled from memory, in the sense of SURVEY.md App. B, with low-to-medium
+        // confidence: check against the tfhe release at hand before relying on its security or failure probability].  One
+        // bootstrap level of 23 bits puts it beyond the single-prime capacity bound: it runs on the two-prime kernel only
+        // (helm_hip_ctx_create_ex with HELM_HIP_CREATE_ALLOW_CRT)
+        p->n = 830; p->k = 2; p->N = 1024; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 3; p->ks_logB = 5;
+        *lwe_std = 0.00000141;
+        *glwe_std = 0.000000000000000294;
+    } else if (s == "toy_crt") {
+        // boolean_tfhe_lib's GLWE shape with a toy n (two-prime kernel).  One level of 23 bits multiplies the key's noise by
+        // up to 2^22 per digit: the other toy sets' glwe std of 1e-9 does not decrypt here (a bootstrap of an encryption of
+        // True came out False under the CPU oracle), tfhe's own value for the shape does
+        p->n = 16; p->k = 2; p->N = 1024; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 4; p->ks_logB = 4;
+        *lwe_std = 1e-7;
+        *glwe_std = 3e-16;
     } else
         return fail(HELM_ERR_INVALID, "unknown parameter set '" + s + "'");
     return 0;

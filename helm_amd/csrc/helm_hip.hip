@@ -2022,6 +2022,8 @@ __global__ __launch_bounds__(64) void k_ntt_roundtrip(const uint32_t *__restrict
 
 // k_pbs_generic: k and pbs_l at run time, every admitted shape the tuned builds do not cover (and HELM_HIP_PBS_VARIANT=10)
 #include "helm_pbs_generic.inc"
+// k_pbs_crt: the same in the CRT pair FpG x FpG2, for shapes beyond the single-prime capacity bound (helm_hip_ctx_create_ex)
+#include "helm_pbs_crt.inc"
 
 #endif // HELM_HIP_TU == 0
 
@@ -2136,6 +2138,13 @@ struct helm_hip_ctx {
     int gen_d = 1;           // k_pbs_generic: digit polynomials per batch (gen_batch)
     size_t gen_lds = 0;      // k_pbs_generic: LDS bytes per workgroup (GenLds)
     int gen_per_cu = 1;      // k_pbs_generic: resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+    bool crt_class = false;  // the shape is beyond the single-prime capacity bound: only k_pbs_crt serves it (kernel class 2)
+    bool crt_path = false;   // k_pbs_crt runs every launch (a class-2 shape, or HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout
+    int crt_d = 1;           // k_pbs_crt: digit polynomials per batch (crt_batch)
+    size_t crt_lds = 0;      // k_pbs_crt: LDS bytes per workgroup (CrtLds)
+    int crt_per_cu = 1;      // k_pbs_crt: resident workgroups per CU at crt_lds
+    double *crt_tw[4] = {nullptr, nullptr, nullptr, nullptr}; // k_pbs_crt: forward tables of FpG, FpG2, then the inverse ones
+    double crt_n_inv[2] = {0, 0}, crt_p0inv = 0;              // 1/N in each field, p0^-1 mod p1
     // per-call scratch
     DevBuf<PbsJob> d_pbs;
     DevBuf<KsJob> d_ks;
@@ -2632,10 +2641,60 @@ static hipError_t launch_pbs_generic(helm_hip_ctx *ctx, const PbsJob *jobs, int6
     }
 }
 
+// the CRT domain, whole (helm_hip_ctx_create_ex under HELM_HIP_CREATE_ALLOW_CRT / FORCE_CRT, as include/helm_hip.h states
+// it): N stops at 2048 because FpG2 has 2-adicity 2^12; (k+1) N <= 4096 is the kernel's LDS budget (helm_pbs_crt.inc);
+// n <= 1024 is what setup_crt sizes the kernel's LDS attribute for; pbs_logB pbs_l <= 31 is what gen_decompose_step's 32-bit
+// recurrence and the static_assert below rest on.  helm_hip_ctx_create_ex checks n, the decomposition, pbs_order and
+// grouping_factor on their own as well (with helm_hip_ctx_create's messages, before this function is asked): they are
+// repeated here so that this function alone is the domain.
+static bool crt_admitted(const helm_hip_params &P)
+{
+    return (P.N == 256 || P.N == 512 || P.N == 1024 || P.N == 2048) && P.k >= 1 && (int64_t)(P.k + 1) * P.N <= 4096 &&
+           P.pbs_l >= 1 && P.pbs_logB >= 1 && (int64_t)P.pbs_logB * P.pbs_l <= 31 && P.n >= 1 && P.n <= 1024 &&
+           P.pbs_order == 0 && P.grouping_factor == 1;
+}
+// The CRT domain needs no capacity check: the largest exact product over it, (k+1) N <= 4096 times l 2^(logB-1) <= 31 x 2^30
+// (logB l <= 31) times 2^31, is 4096 x 31 x 2^61 = 2^77.96 < 2^78, and p0 p1 / 2 = 2^97.5.
+static_assert(((unsigned __int128)4096 * 31 << 61) < ((unsigned __int128)1 << 78) &&
+                  ((unsigned __int128)1 << 78) < (unsigned __int128)CrtF0::P_U64 * CrtF1::P_U64 / 2,
+              "the CRT domain's largest exact product is below p0 p1 / 2");
+
+[[maybe_unused]] static const void *crt_kernel(int logN)
+{
+    return logN == 8    ? reinterpret_cast<const void *>(k_pbs_crt<8>)
+           : logN == 9  ? reinterpret_cast<const void *>(k_pbs_crt<9>)
+           : logN == 10 ? reinterpret_cast<const void *>(k_pbs_crt<10>)
+                        : reinterpret_cast<const void *>(k_pbs_crt<11>);
+}
+
+template <int LOGN>
+static hipError_t launch_pbs_crt_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                                   const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+{
+    // (the dynamic LDS attribute is set by setup_crt, at the largest layout of this N)
+    hipLaunchKernelGGL(k_pbs_crt<LOGN>, dim3((unsigned)count), dim3(CRT_THREADS), ctx->crt_lds, ctx->stream, jobs, wires, raw, tvs,
+                       ctx->bsk, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], out_big, ctx->P.n, ctx->P.k,
+                       ctx->P.pbs_l, ctx->P.pbs_logB, ctx->crt_d, ctx->crt_p0inv);
+    return hipGetLastError();
+}
+
+static hipError_t launch_pbs_crt(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                                 const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+{
+    switch (ctx->P.N) {
+    case 256: return launch_pbs_crt_t<8>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 512: return launch_pbs_crt_t<9>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 1024: return launch_pbs_crt_t<10>(ctx, jobs, count, wires, raw, tvs, out_big);
+    case 2048: return launch_pbs_crt_t<11>(ctx, jobs, count, wires, raw, tvs, out_big);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 static hipError_t launch_pbs(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                              const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     const helm_hip_params &P = ctx->P;
+    if (ctx->crt_path) return launch_pbs_crt(ctx, jobs, count, wires, raw, tvs, out_big);
     if (ctx->gen_path) return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 512 && P.k == 2 && P.pbs_l == 3) return launch_pbs_t<9, 2, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
     if (P.N == 512 && P.k == 1 && P.pbs_l == 3) return launch_pbs_t<9, 1, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
@@ -2781,14 +2840,101 @@ static int setup_field_tables(helm_hip_ctx *ctx)
     return 0;
 }
 
+// A context whose launches run k_pbs_crt: the four twiddle tables of the pair FpG / FpG2 (any primitive 2N-th root serves:
+// no stage of this kernel assumes a short root), 1/N in each field and p0^-1 mod p1, the kernel's LDS attribute, its occupancy
+// and the digit batch D.
+static int setup_crt(helm_hip_ctx *ctx)
+{
+#ifdef HELM_CHECK_BOUNDS
+    // k_pbs_crt is built like the 64-bit engine's k_pbs64_generic, whose -O0 counting build faulted on its first launch for a
+    // cause that was never found: until it is, this build refuses the CRT class before anything is launched.
+    (void)ctx;
+    return fail(HELM_ERR_STATE, "the two-prime CRT kernel is not available in the bound-checking build (libhelm_hip_check.so): "
+                                "use the regular library for CRT contexts");
+#else
+    const helm_hip_params &P = ctx->P;
+    const int N = P.N, logN = ctx->logN;
+    const uint64_t pm[2] = {CrtF0::P_U64, CrtF1::P_U64}, gen[2] = {CrtF0::GEN, CrtF1::GEN};
+    for (int f = 0; f < 2; f++) {
+        const uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
+        if (powmod_u64(psi, (uint64_t)N, pm[f]) != pm[f] - 1) return fail(HELM_ERR_STATE, "internal: no primitive 2N-th root of unity");
+        const uint64_t psi_inv = powmod_u64(psi, pm[f] - 2, pm[f]);
+        std::vector<double> tf(N), ti(N);
+        uint64_t a = 1, b = 1;
+        for (int i = 0; i < N; i++) {
+            tf[bitrev(i, logN)] = centred(a, pm[f]);
+            ti[bitrev(i, logN)] = centred(b, pm[f]);
+            a = mulmod_u64(a, psi, pm[f]);
+            b = mulmod_u64(b, psi_inv, pm[f]);
+        }
+        ctx->crt_n_inv[f] = centred(powmod_u64((uint64_t)N, pm[f] - 2, pm[f]), pm[f]);
+        HIP_TRY(hipMalloc(&ctx->crt_tw[f], sizeof(double) * N));
+        HIP_TRY(hipMalloc(&ctx->crt_tw[2 + f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(ctx->crt_tw[f], tf.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ctx->crt_tw[2 + f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    ctx->crt_p0inv = centred(powmod_u64(pm[0] % pm[1], pm[1] - 2, pm[1]), pm[1]);
+    const void *kern = crt_kernel(logN);
+    // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a context
+    // created later with a smaller one cannot lower it under an earlier context's launches
+    const int K1max = 4096 / N;
+    const size_t lds_max = CrtLds(N, K1max, crt_batch(N, K1max - 1, 31), 1024).bytes;
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    auto occupancy = [&](int d, int &nb) -> int {
+        nb = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CRT_THREADS, CrtLds(N, P.k + 1, d, P.n).bytes));
+        return 0;
+    };
+    int nb1 = 0;
+    if (int rc = occupancy(1, nb1)) return rc;
+    if (nb1 < 1)
+        return fail(HELM_ERR_STATE, "k_pbs_crt: no workgroup of " + std::to_string(CrtLds(N, P.k + 1, 1, P.n).bytes) + " B LDS fits a CU");
+    // digit polynomials per batch: the most (<= crt_batch) that cost no resident workgroup against one per batch
+    ctx->crt_d = 1;
+    for (int d = crt_batch(N, P.k, P.pbs_l); d > 1; d--) {
+        int nb = 0;
+        if (int rc = occupancy(d, nb)) return rc;
+        if (nb == nb1) {
+            ctx->crt_d = d;
+            break;
+        }
+    }
+    ctx->crt_lds = CrtLds(N, P.k + 1, ctx->crt_d, P.n).bytes;
+    ctx->crt_per_cu = nb1;
+    if (getenv("HELM_HIP_VERBOSE")) {
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, kern);
+        fprintf(stderr, "[helm_hip] k_pbs_crt N=%d k=%d l=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.k, P.pbs_l,
+                ctx->crt_d, ctx->crt_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->crt_per_cu);
+    }
+    return 0;
+#endif
+}
+
 int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_ctx **out)
+{
+    return helm_hip_ctx_create_ex(device_id, params, 0, out);
+}
+
+int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_t flags, helm_hip_ctx **out)
 {
     if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (flags & ~(uint32_t)(HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
+        return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
+                                          " (HELM_HIP_CREATE_ALLOW_CRT = 1, HELM_HIP_CREATE_FORCE_CRT = 2)");
+    if (flags == (HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
+        return fail(HELM_ERR_INVALID, "flags 3: HELM_HIP_CREATE_ALLOW_CRT and HELM_HIP_CREATE_FORCE_CRT exclude each other");
+    const bool allow_crt = flags == HELM_HIP_CREATE_ALLOW_CRT, force_crt = flags == HELM_HIP_CREATE_FORCE_CRT;
+    static const char *const crt_domain = "the CRT domain (HELM_HIP_CREATE_ALLOW_CRT / HELM_HIP_CREATE_FORCE_CRT) is N in {256, 512, 1024, "
+                                          "2048}, k >= 1 with (k+1) N <= 4096, pbs_l >= 1 with pbs_logB pbs_l <= 31, n in [1,1024], "
+                                          "pbs_order 0, grouping_factor 1";
     const helm_hip_params &P = *params;
     if (P.torus_bits != 32) return fail(HELM_ERR_INVALID, "only torus_bits = 32 is implemented");
     if (P.pbs_order != 0) return fail(HELM_ERR_INVALID, "only pbs_order = 0 (bootstrap then keyswitch)");
     if (P.grouping_factor != 1) return fail(HELM_ERR_INVALID, "multi-bit PBS (grouping_factor > 1) not implemented");
+    if (force_crt && !crt_admitted(P))
+        return fail(HELM_ERR_INVALID, std::string("HELM_HIP_CREATE_FORCE_CRT: unsupported (N,k,pbs_l): ") + crt_domain);
     if (!pbs_admitted(P))
         return fail(HELM_ERR_INVALID, "unsupported (N,k,pbs_l): N must be 256, 512, 1024 or 2048, k >= 1 with (k+1) N <= 8192, "
                                       "pbs_l >= 1 (tuned builds: (512,2,3) (512,1,3) (512,1,2) (1024,1,3) (1024,1,2); "
@@ -2800,7 +2946,14 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
         return fail(HELM_ERR_INVALID, "bad keyswitch decomposition (ks_logB <= 7, ks_l in {1..6,8})");
     // exactness: |sum| <= (k+1) * l * N * (B/2) * 2^31 must stay below p/2
     const double bound = (double)(P.k + 1) * P.pbs_l * P.N * (double)(1u << (P.pbs_logB - 1)) * 2147483648.0;
-    if (bound * 1.0001 >= FpH::P / 2) return fail(HELM_ERR_INVALID, "parameter set exceeds the single-prime NTT capacity");
+    bool crt_class = false; // beyond the single prime, inside the CRT domain, and the caller allows the two-prime kernel
+    if (bound * 1.0001 >= FpH::P / 2) {
+        if (!allow_crt && !force_crt) return fail(HELM_ERR_INVALID, "parameter set exceeds the single-prime NTT capacity");
+        if (!crt_admitted(P))
+            return fail(HELM_ERR_INVALID, std::string("parameter set exceeds the single-prime NTT capacity and lies outside the "
+                                                      "two-prime kernel's LDS budget: ") + crt_domain);
+        crt_class = true; // (no capacity check of its own: see the static_assert at crt_admitted)
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(HELM_ERR_NO_DEVICE, "no HIP device visible (this engine has no CPU fallback)");
@@ -2845,11 +2998,22 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
         // the generic class (a shape no tuned build covers, or every launch under HELM_HIP_PBS_VARIANT=10): always FpH, its
         // own key layout, one workgroup of GEN_THREADS per bootstrap; the quantum follows its occupancy
         ctx->generic = !pbs_tuned(P);
-        if (ctx->generic && ctx->pbs_variant != 0 && ctx->pbs_variant != 10)
+        // the CRT class (a shape beyond the single-prime bound under HELM_HIP_CREATE_ALLOW_CRT, or every launch of a shape of
+        // the CRT domain under HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout and tables, no single-prime table
+        ctx->crt_class = crt_class;
+        ctx->crt_path = crt_class || force_crt;
+        if (ctx->crt_path) {
+            if (ctx->pbs_variant != 0)
+                return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(ctx->pbs_variant) +
+                                                  " names a single-prime build: a CRT context runs the two-prime kernel only "
+                                                  "(leave the variable unset, or 0)");
+            ctx->field = 98;
+            if (int rc = setup_crt(ctx)) return rc;
+        } else if (ctx->generic && ctx->pbs_variant != 0 && ctx->pbs_variant != 10)
             return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(ctx->pbs_variant) +
                                               " names a tuned build, which this shape (N,k,pbs_l) has not: it runs the generic kernel "
                                               "(variant 10, or leave the variable unset)");
-        ctx->gen_path = ctx->generic || ctx->pbs_variant == 10;
+        ctx->gen_path = !ctx->crt_path && (ctx->generic || ctx->pbs_variant == 10);
         if (ctx->gen_path) {
             ctx->field = 51;
             const void *kern = ctx->logN == 8    ? reinterpret_cast<const void *>(k_pbs_generic<8>)
@@ -2885,7 +3049,8 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
             ctx->gen_lds = GenLds(N, P.k + 1, ctx->gen_d, P.n).bytes;
             ctx->gen_per_cu = nb1;
         }
-        if (int rc = setup_field_tables(ctx)) return rc;
+        if (!ctx->crt_path)
+            if (int rc = setup_field_tables(ctx)) return rc;
         std::vector<uint32_t> tv(N, PT_TRUE);
         HIP_TRY(hipMalloc(&ctx->tv_bool, sizeof(uint32_t) * N));
         HIP_TRY(hipMemcpy(ctx->tv_bool, tv.data(), sizeof(uint32_t) * N, hipMemcpyHostToDevice));
@@ -2933,6 +3098,7 @@ int helm_hip_ctx_destroy(helm_hip_ctx *ctx)
     }
     (void)hipFree(ctx->tw_fwd);
     (void)hipFree(ctx->tw_inv);
+    for (double *t : ctx->crt_tw) (void)hipFree(t);
     (void)hipFree(ctx->bsk);
     (void)hipFree(ctx->ksk);
     (void)hipFree(ctx->ksk_planes);
@@ -2980,6 +3146,7 @@ int helm_hip_sync(helm_hip_ctx *ctx)
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null ctx");
+    if (ctx->crt_path) return (int64_t)ctx->crt_per_cu * ctx->n_cus; // k_pbs_crt: one bootstrap per workgroup, all resident
     if (ctx->gen_path) return (int64_t)ctx->gen_per_cu * ctx->n_cus; // k_pbs_generic: one bootstrap per workgroup, all resident
     return 4 * (int64_t)ctx->n_cus; // PbsCfg::NB bootstraps per workgroup, one workgroup per CU
 }
@@ -2987,7 +3154,13 @@ int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx)
 int helm_hip_kernel_class(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->generic ? 1 : 0;
+    return ctx->crt_class ? 2 : ctx->generic ? 1 : 0;
+}
+
+int helm_hip_digit_batch(const helm_hip_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return ctx->crt_path ? ctx->crt_d : ctx->gen_path ? ctx->gen_d : 0;
 }
 
 int helm_hip_field_bits(const helm_hip_ctx *ctx)
@@ -3032,19 +3205,19 @@ int helm_hip_bound_violations(helm_hip_ctx *ctx, uint32_t counts[8], int reset, 
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    if (ctx->gen_path) return 0; // k_pbs_generic: plain radix-2 stages throughout
+    if (ctx->gen_path || ctx->crt_path) return 0; // k_pbs_generic, k_pbs_crt: plain radix-2 stages throughout
     return 2; // both fields of this engine (5072^4 + 1, 6432^4 + 1) have short eighth roots
 }
 
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4])
 {
     if (!ctx || !cost) return fail(HELM_ERR_INVALID, "null argument");
-    if (ctx->gen_path) {
-        // k_pbs_generic, from its occupancy W (workgroups per CU, one wave of each on every SIMD): a launch of at most q/4 of
+    if (ctx->gen_path || ctx->crt_path) {
+        // k_pbs_generic / k_pbs_crt, from its occupancy W (workgroups per CU, one wave of each on every SIMD): a launch of at most q/4 of
         // the quantum puts w = ceil(q W / 4) workgroups on a CU.  One wave per SIMD leaves the step's latencies (LDS round
         // trips, key loads, barriers) exposed; from two on, the SIMD's time grows with its waves.  Model: time ~ max(1, w / 2),
         // relative to the full round - non-decreasing, cost[3] = 1 (not measured; DESIGN.md "The generic kernel class")
-        const int W = ctx->gen_per_cu;
+        const int W = ctx->crt_path ? ctx->crt_per_cu : ctx->gen_per_cu;
         const double full = std::max(1.0, W / 2.0);
         for (int q = 1; q <= 4; q++) cost[q - 1] = std::max(1.0, ((q * W + 3) / 4) / 2.0) / full;
         return 0;
@@ -3080,7 +3253,7 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
     HIP_TRY(hipSetDevice(ctx->device));
-    if (P.N == 1024 && !ctx->gen_path) {
+    if (P.N == 1024 && !ctx->gen_path && !ctx->crt_path) {
         // Round 5: which field serves THIS key.  The exact sum an external product can reach is at most B/2 x the l1-norm of
         // the key coefficients that meet in one output coefficient: the (k+1) l polynomials of one key column of one step (a
         // negacyclic product's output coefficient is a signed sum over ALL coefficients of each factor).  Both groupings of
@@ -3125,9 +3298,20 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
     }
     Scratch<uint32_t> d_std;
     HIP_TRY(d_std.alloc(n_words));
-    if (!ctx->bsk) HIP_TRY(hipMalloc(&ctx->bsk, n_words * sizeof(double)));
+    // (a CRT context keeps every key word in both fields: 16 bytes per word)
+    if (!ctx->bsk) HIP_TRY(hipMalloc(&ctx->bsk, n_words * sizeof(double) * (ctx->crt_path ? 2 : 1)));
     HIP_TRY(hipMemcpyAsync(d_std.p, bsk_std, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->gen_path) {
+    if (ctx->crt_path) {
+        // the CRT class's layout: [i][r][c][lev][f][N], bit-reversed transform order (k_bsk_convert_crt)
+#define CRT_CONVERT(LN)                                                                                                     \
+    hipLaunchKernelGGL(k_bsk_convert_crt<LN>, dim3((unsigned)polys), dim3(CRT_THREADS), 0, ctx->stream, d_std.p, ctx->bsk,  \
+                       ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_n_inv[0], ctx->crt_n_inv[1], (int)K1, P.pbs_l)
+        if (P.N == 256) CRT_CONVERT(8);
+        else if (P.N == 512) CRT_CONVERT(9);
+        else if (P.N == 1024) CRT_CONVERT(10);
+        else CRT_CONVERT(11);
+#undef CRT_CONVERT
+    } else if (ctx->gen_path) {
         // the generic class's layout: [i][r][c][lev][N], bit-reversed transform order (k_bsk_convert_generic)
 #define GEN_CONVERT(LN)                                                                                                     \
     hipLaunchKernelGGL(k_bsk_convert_generic<LN>, dim3((unsigned)polys), dim3(GEN_THREADS), 0, ctx->stream, d_std.p, ctx->bsk, \
@@ -3937,7 +4121,17 @@ int helm_hip_ntt_roundtrip(helm_hip_ctx *ctx, const uint32_t *poly_in, uint32_t 
     HIP_TRY(d_in.alloc((size_t)count * N));
     HIP_TRY(d_out.alloc((size_t)count * N));
     HIP_TRY(hipMemcpyAsync(d_in.p, poly_in, (size_t)count * N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->gen_path) {
+    if (ctx->crt_path) {
+#define CRT_ROUNDTRIP(LN)                                                                                                     \
+    hipLaunchKernelGGL(k_ntt_roundtrip_crt<LN>, dim3((unsigned)count), dim3(CRT_THREADS), 0, ctx->stream, d_in.p, d_out.p,    \
+                       ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], ctx->crt_n_inv[0], ctx->crt_n_inv[1],  \
+                       ctx->crt_p0inv)
+        if (N == 256) CRT_ROUNDTRIP(8);
+        else if (N == 512) CRT_ROUNDTRIP(9);
+        else if (N == 1024) CRT_ROUNDTRIP(10);
+        else CRT_ROUNDTRIP(11);
+#undef CRT_ROUNDTRIP
+    } else if (ctx->gen_path) {
 #define GEN_ROUNDTRIP(LN)                                                                                                     \
     hipLaunchKernelGGL(k_ntt_roundtrip_generic<LN>, dim3((unsigned)count), dim3(GEN_THREADS), 0, ctx->stream, d_in.p, d_out.p, \
                        ctx->tw_fwd, ctx->tw_inv, ctx->n_inv)

@@ -14,7 +14,8 @@ from ._native import Params, HipTiming as Timing, hip, host, hip_check, client_c
 
 
 def named_params(name):
-    """-> (Params, lwe_noise_std, glwe_noise_std)"""
+    """-> (Params, lwe_noise_std, glwe_noise_std).  "boolean_tfhe_lib" and "toy_crt" lie beyond the single-prime capacity bound:
+    a server key for them needs ServerKey(..., crt="allow") (gen_keys(name, crt="allow"))."""
     p = Params()
     a, b = C.c_double(), C.c_double()
     client_check(host.helm_client_named_params(name.encode(), C.byref(p), C.byref(a), C.byref(b)))
@@ -96,14 +97,28 @@ class ClientKey:
         return out
 
 
+HIP_CREATE_ALLOW_CRT = 1  # include/helm_hip.h HELM_HIP_CREATE_*
+HIP_CREATE_FORCE_CRT = 2
+_CRT_FLAGS = {"allow": HIP_CREATE_ALLOW_CRT, "force": HIP_CREATE_FORCE_CRT}
+
+
 class ServerKey:
     """GPU engine context with the bootstrapping and keyswitching keys resident
-    in HBM.  Construction fails (HelmError) when no gfx950 device is usable."""
+    in HBM.  Construction fails (HelmError) when no gfx950 device is usable.
 
-    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0):
+    crt: None (helm_hip_ctx_create: shapes beyond the single-prime capacity bound are refused), "allow" (such shapes, inside
+    the CRT domain N <= 2048, (k+1) N <= 4096, run on the two-prime kernel; every other shape keeps its kernel) or "force"
+    (every launch on the two-prime kernel: tests and measurement) - helm_hip_ctx_create_ex."""
+
+    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, crt=None):
         self.params = client_key.params if client_key is not None else params
         h = nv.vp()
-        hip_check(hip.helm_hip_ctx_create(device, C.byref(self.params), C.byref(h)))
+        if crt is None:
+            hip_check(hip.helm_hip_ctx_create(device, C.byref(self.params), C.byref(h)))
+        else:
+            if crt not in _CRT_FLAGS:
+                raise ValueError('crt must be None, "allow" or "force"')
+            hip_check(hip.helm_hip_ctx_create_ex(device, C.byref(self.params), _CRT_FLAGS[crt], C.byref(h)))
         self._h = h
         self.device = device
         if client_key is not None:
@@ -140,11 +155,19 @@ class ServerKey:
 
     def kernel_class(self):
         """"tuned" when the parameter shape (N, k, pbs_l) has tuned blind-rotate builds, "generic" when the generic kernel
-        (k and pbs_l at run time) serves it (helm_hip_kernel_class; HELM_HIP_PBS_VARIANT=10 does not change it)."""
+        (k and pbs_l at run time) serves it, "crt" when the shape is beyond the single-prime capacity bound and runs on the
+        two-prime kernel (helm_hip_kernel_class; neither HELM_HIP_PBS_VARIANT=10 nor crt="force" changes it)."""
         v = int(hip.helm_hip_kernel_class(self._h))
         if v < 0:
             hip_check(v)
-        return "generic" if v == 1 else "tuned"
+        return {1: "generic", 2: "crt"}.get(v, "tuned")
+
+    def digit_batch(self):
+        """Digit polynomials the generic / two-prime kernel handles together (D; 0 on the tuned builds): helm_hip_digit_batch."""
+        v = int(hip.helm_hip_digit_batch(self._h))
+        if v < 0:
+            hip_check(v)
+        return v
 
     def wires(self, n_wires):
         return DeviceWires(self, n_wires)
@@ -185,7 +208,8 @@ class ServerKey:
     def field_bits(self):
         """49: the blind-rotate kernels compute in the lazy field p = 5072^4 + 1 (short eighth roots of unity: two forward
         stages on digits without modular reductions), 51: in the 51-bit field, 50: N = 1024 in the lazy field p = 5440^4 + 1,
-        chosen when the loaded key's own bound fits (helm_hip_field_bits)."""
+        chosen when the loaded key's own bound fits, 98: the CRT pair 5072^4 + 1, 5096^4 + 1 of the two-prime kernel
+        (helm_hip_field_bits)."""
         v = int(hip.helm_hip_field_bits(self._h))
         if v < 0:
             hip_check(v)

@@ -110,6 +110,31 @@ int helm_hip_runtime_copies(char *paths, size_t cap);
 /* -- context --------------------------------------------------------------- */
 /* Replaces ServerKey construction (reference src/bin/helm.rs:241, 187-192). */
 int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_ctx **out);
+
+/* Flags of helm_hip_ctx_create_ex. */
+enum {
+    HELM_HIP_CREATE_ALLOW_CRT = 1, /* admit shapes beyond the single-prime capacity bound: they run on the two-prime kernel */
+    HELM_HIP_CREATE_FORCE_CRT = 2  /* run every launch on the two-prime kernel (tests and measurement) */
+};
+/* helm_hip_ctx_create with flags; flags = 0 is helm_hip_ctx_create itself - the same checks in the same order, the same
+ * messages.  Every single-prime kernel admits a shape only while its exact products stay below half its prime,
+ * (k+1) pbs_l N 2^(pbs_logB-1) 2^31 < 2^49.6; shapes with few, wide decomposition levels lie beyond (tfhe's boolean
+ * TFHE_LIB_PARAMETERS: k = 2, N = 1024, one level of 23 bits; the later boolean default: k = 3, N = 512, two levels of
+ * 10 bits) and are refused with "... exceeds the single-prime NTT capacity".
+ * HELM_HIP_CREATE_ALLOW_CRT: a shape that passes every check of helm_hip_ctx_create keeps its kernel and class; a shape
+ * that fails ONLY the capacity check and lies in the CRT domain - N in {256, 512, 1024, 2048}, k >= 1, (k+1) N <= 4096
+ * (the kernel's LDS budget), pbs_l >= 1, pbs_logB pbs_l <= 31, n <= 1024, pbs_order 0, grouping_factor 1 - creates a
+ * context of kernel class 2: k_pbs_crt computes in the CRT pair of primes 5072^4 + 1 and 5096^4 + 1 (p0 p1 / 2 = 2^97.5,
+ * above every product of the domain: no capacity check) and lifts to the torus; bit-exact like every other kernel, slower
+ * than the single-prime ones, 16 bytes of device memory per bootstrapping-key word.  A shape beyond the bound with
+ * (k+1) N > 4096 is still refused, and the message names the CRT domain.
+ * HELM_HIP_CREATE_FORCE_CRT: every shape of the CRT domain runs every launch on k_pbs_crt, shapes a single-prime kernel
+ * could serve included (helm_hip_kernel_class keeps reporting such a shape's own class, helm_hip_field_bits reports 98); a
+ * shape outside the domain is HELM_ERR_INVALID.
+ * Any other bit, or both bits together, is HELM_ERR_INVALID.  A context whose launches run k_pbs_crt accepts
+ * HELM_HIP_PBS_VARIANT unset or 0 only (every other value names a single-prime build), and the bound-checking build
+ * (libhelm_hip_check.so) refuses it at creation with HELM_ERR_STATE. */
+int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_t flags, helm_hip_ctx **out);
 int helm_hip_ctx_destroy(helm_hip_ctx *ctx);
 /* The parameter set the context was created with. */
 int helm_hip_get_params(const helm_hip_ctx *ctx, helm_hip_params *out);
@@ -121,8 +146,9 @@ int helm_hip_sync(helm_hip_ctx *ctx);
 /* Bootstraps of one full round of the dominant (lockstep) build on this device: 4 per compute unit.
  * A launch of a whole number of rounds leaves no partial round behind; the host's launch packing
  * (helm_host_pack_levels) sizes launches with it.  When the generic kernel runs the context's launches (kernel class 1,
- * or HELM_HIP_PBS_VARIANT=10): its resident workgroups per compute unit (one bootstrap each, from the HIP occupancy
- * calculator at the context's LDS size) x compute units.  Negative on error. */
+ * or HELM_HIP_PBS_VARIANT=10) or the two-prime kernel does (kernel class 2, or HELM_HIP_CREATE_FORCE_CRT): its resident
+ * workgroups per compute unit (one bootstrap each, from the HIP occupancy calculator at the context's LDS size) x compute
+ * units.  Negative on error. */
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx);
 
 /* Which blind-rotate kernel class the context's shape (N, k, pbs_l) runs on: 0 = the tuned builds (k_pbs, k_pbs_wide,
@@ -131,15 +157,23 @@ int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx);
  * shape only: HELM_HIP_PBS_VARIANT=10, which runs a tuned shape on the generic kernel, does not change it (on a class-1
  * shape helm_hip_ctx_create refuses the variants that name tuned builds) - that variable is a debug switch.  The 64-bit
  * engine's helm_si_kernel_class (helm_shortint.h) differs: its forcing is an API flag, so it reports the kernel the launches
- * run on.  Negative on error. */
+ * run on.  2 = the two-prime kernel (k_pbs_crt): the shape is beyond the single-prime capacity bound and was admitted under
+ * HELM_HIP_CREATE_ALLOW_CRT (or FORCE_CRT); HELM_HIP_CREATE_FORCE_CRT on a shape of class 0 or 1 does not change the class,
+ * like HELM_HIP_PBS_VARIANT=10.  Negative on error. */
 int helm_hip_kernel_class(const helm_hip_ctx *ctx);
+/* Digit polynomials the generic or the two-prime kernel decomposes, transforms and multiplies together (D): the largest batch
+ * its LDS layout allows that still lets as many workgroups reside on a compute unit as D = 1; the last batch of a CMUX step
+ * is partial when D does not divide (k+1) pbs_l.  0 when the tuned builds run the context's launches.  Results do not depend
+ * on it; tests use it to know which path of those kernels a shape takes.  Negative on error. */
+int helm_hip_digit_batch(const helm_hip_ctx *ctx);
 
 /* What a launch of at most 1/4, 2/4, 3/4 and 4/4 of helm_hip_launch_quantum() bootstraps costs on this context, relative to
  * a full round (cost[3] = 1): the engine runs a different build of the blind-rotate kernel per width (k_pbs_wide: one
  * bootstrap per CU on four SIMDs, k_pbs_duo: two per CU on two SIMDs each, k_pbs_trio: three per CU on four waves each, full
  * lockstep rounds).  Measured on
  * MI355X (profiles/r04/microbench.jsonl); the host's launch packing (helm_host_pack_levels_costed) sizes launches that are
- * narrower than a round with it.  On the generic kernel: a model from its occupancy (non-decreasing, cost[3] = 1). */
+ * narrower than a round with it.  On the generic and the two-prime kernel: a model from its occupancy (non-decreasing,
+ * cost[3] = 1). */
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4]);
 
 /* The prime field the blind-rotate kernels of this context compute in, as its size class: 49 = the lazy field p = 5072^4 + 1
@@ -150,12 +184,13 @@ int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4]);
  * p/2 - an exact guarantee for that key and every input (a generated key under helm.rs:141-146's set does; the worst case
  * of the set does not, and a key that does not fit keeps 51), so the value may change when a key is loaded
  * (HELM_HIP_FIELD=51 in the environment keeps the 51-bit field).  Results do not depend on it (exact integer arithmetic
- * either way); reported by benchmarks because the operation count of the kernels does.  Negative on error. */
+ * either way); reported by benchmarks because the operation count of the kernels does.  98 = the CRT pair p0 = 5072^4 + 1,
+ * p1 = 5096^4 + 1 (2^49.23 x 2^49.26): k_pbs_crt runs the context's launches.  Negative on error. */
 int helm_hip_field_bits(const helm_hip_ctx *ctx);
 /* Number of leading stages of every forward transform on decomposition digits that run as plain multiplications by short
  * roots of unity (2 in both fields of this engine: one radix-4 butterfly of 10 operations per four values instead of two
  * stages of modular butterflies); 0 when the generic kernel runs the context's launches (kernel class 1, or
- * HELM_HIP_PBS_VARIANT=10: plain radix-2 stages).  For benchmarks that count the operations
+ * HELM_HIP_PBS_VARIANT=10: plain radix-2 stages) or the two-prime kernel does.  For benchmarks that count the operations
  * the kernels execute; results do not depend on it. */
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx);
 

@@ -60,6 +60,10 @@ pub const HELM_GATE_BUF: i32 = 10;
 pub const HELM_GATE_CONST_ONE: i32 = 11;
 pub const HELM_GATE_CONST_ZERO: i32 = 12;
 
+// include/helm_hip.h: flags of helm_hip_ctx_create_ex (an importer that meets a boolean key shape beyond the single-prime
+// capacity bound - few, wide decomposition levels - passes ALLOW_CRT)
+pub const HELM_HIP_CREATE_ALLOW_CRT: u32 = 1;
+pub const HELM_HIP_CREATE_FORCE_CRT: u32 = 2; // every launch on the two-prime kernel (tests and measurement)
 // include/helm_shortint.h: flags of helm_si_ctx_create_ex (an importer that meets an untuned key shape passes ALLOW_GENERIC)
 pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
 pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
@@ -104,11 +108,13 @@ extern "C" {
     pub fn helm_hip_device_count() -> c_int;
     pub fn helm_hip_runtime_copies(paths: *mut c_char, cap: usize) -> c_int;
     pub fn helm_hip_ctx_create(device_id: c_int, params: *const helm_hip_params, out: *mut *mut helm_hip_ctx) -> c_int;
+    pub fn helm_hip_ctx_create_ex(device_id: c_int, params: *const helm_hip_params, flags: u32, out: *mut *mut helm_hip_ctx) -> c_int;
     pub fn helm_hip_ctx_destroy(ctx: *mut helm_hip_ctx) -> c_int;
     pub fn helm_hip_set_stream(ctx: *mut helm_hip_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn helm_hip_sync(ctx: *mut helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_quantum(ctx: *const helm_hip_ctx) -> i64;
     pub fn helm_hip_kernel_class(ctx: *const helm_hip_ctx) -> c_int;
+    pub fn helm_hip_digit_batch(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_costs(ctx: *const helm_hip_ctx, cost: *mut f64) -> c_int;
     pub fn helm_hip_short_root_stages(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_field_bits(ctx: *const helm_hip_ctx) -> c_int;

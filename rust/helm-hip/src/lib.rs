@@ -97,9 +97,20 @@ impl<'a> HipGateCircuit<'a> {
     /// `GateCircuit::new(client_key, server_key, circuit)` (circuit.rs:383-391) with the server key
     /// replaced by an engine context holding the same key material.
     pub fn new(client_key: ClientKey, std_keys: &keys::StandardKeys, circuit: Circuit<'a>, device_id: i32) -> Self {
+        Self::new_with_crt(client_key, std_keys, circuit, device_id, None)
+    }
+
+    /// `new` with the two-prime kernel on request (`helm_hip_ctx_create_ex`): `Some(sys::HELM_HIP_CREATE_ALLOW_CRT)` admits a
+    /// key shape beyond the single-prime capacity bound (tfhe's boolean TFHE_LIB_PARAMETERS: one level of 23 bits) inside the
+    /// CRT domain, `Some(sys::HELM_HIP_CREATE_FORCE_CRT)` runs every launch on that kernel; `None` is `new`.
+    pub fn new_with_crt(client_key: ClientKey, std_keys: &keys::StandardKeys, circuit: Circuit<'a>, device_id: i32,
+                        crt: Option<u32>) -> Self {
         assert_one_hip_runtime();
         let mut ctx = std::ptr::null_mut();
-        check(unsafe { sys::helm_hip_ctx_create(device_id, &std_keys.params, &mut ctx) });
+        match crt {
+            None => check(unsafe { sys::helm_hip_ctx_create(device_id, &std_keys.params, &mut ctx) }),
+            Some(flags) => check(unsafe { sys::helm_hip_ctx_create_ex(device_id, &std_keys.params, flags, &mut ctx) }),
+        }
         check(unsafe { sys::helm_hip_load_bootstrap_key(ctx, std_keys.bsk.as_ptr(), std_keys.bsk.len()) });
         check(unsafe { sys::helm_hip_load_keyswitch_key(ctx, std_keys.ksk.as_ptr(), std_keys.ksk.len()) });
         HipGateCircuit {
