@@ -2022,7 +2022,9 @@ __global__ __launch_bounds__(64) void k_ntt_roundtrip(const uint32_t *__restrict
 
 // k_pbs_generic: k and pbs_l at run time, every admitted shape the tuned builds do not cover (and HELM_HIP_PBS_VARIANT=10)
 #include "helm_pbs_generic.inc"
-// k_pbs_crt: the same in the CRT pair FpG x FpG2, for shapes beyond the single-prime capacity bound (helm_hip_ctx_create_ex)
+// k_pbs_crt: the same in the CRT pair FpG x FpG2, for shapes beyond the single-prime capacity bound (helm_hip_ctx_create_ex);
+// pbs_twoprime.h: what it shares with the 64-bit engine's k_pbs64_generic
+#include "pbs_twoprime.h"
 #include "helm_pbs_crt.inc"
 
 #endif // HELM_HIP_TU == 0
@@ -2031,29 +2033,6 @@ __global__ __launch_bounds__(64) void k_ntt_roundtrip(const uint32_t *__restrict
 // host side
 // ------------------------------------------------------------------------------------
 namespace {
-
-typedef unsigned __int128 u128;
-uint64_t mulmod_u64(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((u128)a * b % p); }
-uint64_t powmod_u64(uint64_t a, uint64_t e, uint64_t p)
-{
-    uint64_t r = 1;
-    while (e) {
-        if (e & 1) r = mulmod_u64(r, a, p);
-        a = mulmod_u64(a, a, p);
-        e >>= 1;
-    }
-    return r;
-}
-double centred(uint64_t v, uint64_t p) { return v > p / 2 ? (double)((int64_t)v - (int64_t)p) : (double)(int64_t)v; }
-int bitrev(int x, int bits)
-{
-    int r = 0;
-    for (int i = 0; i < bits; i++) {
-        r = (r << 1) | (x & 1);
-        x >>= 1;
-    }
-    return r;
-}
 
 template <typename T> struct DevBuf {
     T *p = nullptr;
@@ -2140,8 +2119,8 @@ struct helm_hip_ctx {
     int gen_per_cu = 1;      // k_pbs_generic: resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
     bool crt_class = false;  // the shape is beyond the single-prime capacity bound: only k_pbs_crt serves it (kernel class 2)
     bool crt_path = false;   // k_pbs_crt runs every launch (a class-2 shape, or HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout
-    int crt_d = 1;           // k_pbs_crt: digit polynomials per batch (crt_batch)
-    size_t crt_lds = 0;      // k_pbs_crt: LDS bytes per workgroup (CrtLds)
+    int crt_d = 1;           // k_pbs_crt: digit polynomials per batch (tp_batch, tp_fit)
+    size_t crt_lds = 0;      // k_pbs_crt: LDS bytes per workgroup (TwoPrimeLds<uint32_t>)
     int crt_per_cu = 1;      // k_pbs_crt: resident workgroups per CU at crt_lds
     double *crt_tw[4] = {nullptr, nullptr, nullptr, nullptr}; // k_pbs_crt: forward tables of FpG, FpG2, then the inverse ones
     double crt_n_inv[2] = {0, 0}, crt_p0inv = 0;              // 1/N in each field, p0^-1 mod p1
@@ -2643,7 +2622,7 @@ static hipError_t launch_pbs_generic(helm_hip_ctx *ctx, const PbsJob *jobs, int6
 
 // the CRT domain, whole (helm_hip_ctx_create_ex under HELM_HIP_CREATE_ALLOW_CRT / FORCE_CRT, as include/helm_hip.h states
 // it): N stops at 2048 because FpG2 has 2-adicity 2^12; (k+1) N <= 4096 is the kernel's LDS budget (helm_pbs_crt.inc);
-// n <= 1024 is what setup_crt sizes the kernel's LDS attribute for; pbs_logB pbs_l <= 31 is what gen_decompose_step's 32-bit
+// n <= 1024 is what tp_fit sizes the kernel's LDS attribute for; pbs_logB pbs_l <= 31 is what gen_decompose_step's 32-bit
 // recurrence and the static_assert below rest on.  helm_hip_ctx_create_ex checks n, the decomposition, pbs_order and
 // grouping_factor on their own as well (with helm_hip_ctx_create's messages, before this function is asked): they are
 // repeated here so that this function alone is the domain.
@@ -2656,7 +2635,7 @@ static bool crt_admitted(const helm_hip_params &P)
 // The CRT domain needs no capacity check: the largest exact product over it, (k+1) N <= 4096 times l 2^(logB-1) <= 31 x 2^30
 // (logB l <= 31) times 2^31, is 4096 x 31 x 2^61 = 2^77.96 < 2^78, and p0 p1 / 2 = 2^97.5.
 static_assert(((unsigned __int128)4096 * 31 << 61) < ((unsigned __int128)1 << 78) &&
-                  ((unsigned __int128)1 << 78) < (unsigned __int128)CrtF0::P_U64 * CrtF1::P_U64 / 2,
+                  ((unsigned __int128)1 << 78) < (unsigned __int128)FpG::P_U64 * FpG2::P_U64 / 2,
               "the CRT domain's largest exact product is below p0 p1 / 2");
 
 [[maybe_unused]] static const void *crt_kernel(int logN)
@@ -2672,7 +2651,7 @@ static hipError_t launch_pbs_crt_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_
                                    const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     // (the dynamic LDS attribute is set by setup_crt, at the largest layout of this N)
-    hipLaunchKernelGGL(k_pbs_crt<LOGN>, dim3((unsigned)count), dim3(CRT_THREADS), ctx->crt_lds, ctx->stream, jobs, wires, raw, tvs,
+    hipLaunchKernelGGL(k_pbs_crt<LOGN>, dim3((unsigned)count), dim3(TP_THREADS), ctx->crt_lds, ctx->stream, jobs, wires, raw, tvs,
                        ctx->bsk, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], out_big, ctx->P.n, ctx->P.k,
                        ctx->P.pbs_l, ctx->P.pbs_logB, ctx->crt_d, ctx->crt_p0inv);
     return hipGetLastError();
@@ -2821,15 +2800,9 @@ static int setup_field_tables(helm_hip_ctx *ctx)
         if (!pick) return fail(HELM_ERR_STATE, "internal: no 2N-th root of unity with psi^(N/4) = b");
         psi = powmod_u64(psi, pick, pm);
     }
-    const uint64_t psi_inv = powmod_u64(psi, pm - 2, pm);
     std::vector<double> tf(N), ti(N);
-    uint64_t a = 1, b = 1;
-    for (int i = 0; i < N; i++) {
-        tf[bitrev(i, logN)] = centred(a, pm);
-        ti[bitrev(i, logN)] = centred(b, pm);
-        a = mulmod_u64(a, psi, pm);
-        b = mulmod_u64(b, psi_inv, pm);
-    }
+    power_table(tf.data(), psi, pm, N, logN);
+    power_table(ti.data(), powmod_u64(psi, pm - 2, pm), pm, N, logN);
     if (tf[1] != b2 || tf[2] != b1 || tf[3] != b3)
         return fail(HELM_ERR_STATE, "internal: the first twiddles are not the constants the kernels assume");
     ctx->n_inv = centred(powmod_u64((uint64_t)N, pm - 2, pm), pm);
@@ -2854,19 +2827,13 @@ static int setup_crt(helm_hip_ctx *ctx)
 #else
     const helm_hip_params &P = ctx->P;
     const int N = P.N, logN = ctx->logN;
-    const uint64_t pm[2] = {CrtF0::P_U64, CrtF1::P_U64}, gen[2] = {CrtF0::GEN, CrtF1::GEN};
+    const uint64_t pm[2] = {FpG::P_U64, FpG2::P_U64}, gen[2] = {FpG::GEN, FpG2::GEN};
     for (int f = 0; f < 2; f++) {
         const uint64_t psi = powmod_u64(gen[f], (pm[f] - 1) / (2 * (uint64_t)N), pm[f]);
         if (powmod_u64(psi, (uint64_t)N, pm[f]) != pm[f] - 1) return fail(HELM_ERR_STATE, "internal: no primitive 2N-th root of unity");
-        const uint64_t psi_inv = powmod_u64(psi, pm[f] - 2, pm[f]);
         std::vector<double> tf(N), ti(N);
-        uint64_t a = 1, b = 1;
-        for (int i = 0; i < N; i++) {
-            tf[bitrev(i, logN)] = centred(a, pm[f]);
-            ti[bitrev(i, logN)] = centred(b, pm[f]);
-            a = mulmod_u64(a, psi, pm[f]);
-            b = mulmod_u64(b, psi_inv, pm[f]);
-        }
+        power_table(tf.data(), psi, pm[f], N, logN);
+        power_table(ti.data(), powmod_u64(psi, pm[f] - 2, pm[f]), pm[f], N, logN);
         ctx->crt_n_inv[f] = centred(powmod_u64((uint64_t)N, pm[f] - 2, pm[f]), pm[f]);
         HIP_TRY(hipMalloc(&ctx->crt_tw[f], sizeof(double) * N));
         HIP_TRY(hipMalloc(&ctx->crt_tw[2 + f], sizeof(double) * N));
@@ -2875,32 +2842,12 @@ static int setup_crt(helm_hip_ctx *ctx)
     }
     ctx->crt_p0inv = centred(powmod_u64(pm[0] % pm[1], pm[1] - 2, pm[1]), pm[1]);
     const void *kern = crt_kernel(logN);
-    // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a context
-    // created later with a smaller one cannot lower it under an earlier context's launches
-    const int K1max = 4096 / N;
-    const size_t lds_max = CrtLds(N, K1max, crt_batch(N, K1max - 1, 31), 1024).bytes;
-    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-    auto occupancy = [&](int d, int &nb) -> int {
-        nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CRT_THREADS, CrtLds(N, P.k + 1, d, P.n).bytes));
-        return 0;
-    };
-    int nb1 = 0;
-    if (int rc = occupancy(1, nb1)) return rc;
-    if (nb1 < 1)
-        return fail(HELM_ERR_STATE, "k_pbs_crt: no workgroup of " + std::to_string(CrtLds(N, P.k + 1, 1, P.n).bytes) + " B LDS fits a CU");
-    // digit polynomials per batch: the most (<= crt_batch) that cost no resident workgroup against one per batch
-    ctx->crt_d = 1;
-    for (int d = crt_batch(N, P.k, P.pbs_l); d > 1; d--) {
-        int nb = 0;
-        if (int rc = occupancy(d, nb)) return rc;
-        if (nb == nb1) {
-            ctx->crt_d = d;
-            break;
-        }
-    }
-    ctx->crt_lds = CrtLds(N, P.k + 1, ctx->crt_d, P.n).bytes;
-    ctx->crt_per_cu = nb1;
+    TwoPrimeFit fit;
+    HIP_TRY(tp_fit<uint32_t>(kern, N, P.k, P.pbs_l, P.n, fit));
+    if (fit.per_cu < 1) return fail(HELM_ERR_STATE, "k_pbs_crt: no workgroup of " + std::to_string(fit.lds) + " B LDS fits a CU");
+    ctx->crt_d = fit.d;
+    ctx->crt_lds = fit.lds;
+    ctx->crt_per_cu = fit.per_cu;
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
@@ -3304,7 +3251,7 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
     if (ctx->crt_path) {
         // the CRT class's layout: [i][r][c][lev][f][N], bit-reversed transform order (k_bsk_convert_crt)
 #define CRT_CONVERT(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_bsk_convert_crt<LN>, dim3((unsigned)polys), dim3(CRT_THREADS), 0, ctx->stream, d_std.p, ctx->bsk,  \
+    hipLaunchKernelGGL(k_bsk_convert_crt<LN>, dim3((unsigned)polys), dim3(TP_THREADS), 0, ctx->stream, d_std.p, ctx->bsk,   \
                        ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_n_inv[0], ctx->crt_n_inv[1], (int)K1, P.pbs_l)
         if (P.N == 256) CRT_CONVERT(8);
         else if (P.N == 512) CRT_CONVERT(9);
@@ -4123,7 +4070,7 @@ int helm_hip_ntt_roundtrip(helm_hip_ctx *ctx, const uint32_t *poly_in, uint32_t 
     HIP_TRY(hipMemcpyAsync(d_in.p, poly_in, (size_t)count * N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     if (ctx->crt_path) {
 #define CRT_ROUNDTRIP(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_ntt_roundtrip_crt<LN>, dim3((unsigned)count), dim3(CRT_THREADS), 0, ctx->stream, d_in.p, d_out.p,    \
+    hipLaunchKernelGGL(k_ntt_roundtrip_crt<LN>, dim3((unsigned)count), dim3(TP_THREADS), 0, ctx->stream, d_in.p, d_out.p,     \
                        ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], ctx->crt_n_inv[0], ctx->crt_n_inv[1],  \
                        ctx->crt_p0inv)
         if (N == 256) CRT_ROUNDTRIP(8);

@@ -6,8 +6,8 @@
 //
 // Why it is its own kernel.  (1) The field: FpG2 (5096^4 + 1) has 2-adicity 2^12, so it holds no 8192-th root of unity; the
 // pair here is L0 = FpG (5072^4 + 1, 2^16 | p - 1) and L1 = FpI (5440^4 + 1, 2^24 | p - 1), p0 p1 / 2 = 2^97.87.  (2) LDS:
-// Gen64Lds at k = 1, N = 4096 would be 64 (acc) + 128 (col, both fields) + 64 (dig) KiB.  (3) One workgroup per CU is all
-// that fits, so the workgroup is wide.
+// TwoPrimeLds<uint64_t> at k = 1, N = 4096 would be 64 (acc) + 128 (col, both fields) + 64 (dig) KiB.  (3) One workgroup per
+// CU is all that fits, so the workgroup is wide.
 //
 // One workgroup of 1024 threads (16 waves, four per SIMD, <= 128 VGPRs per lane) per bootstrap.  LDS (Large64Lds):
 //   acc   u64    [2][N]    the accumulator GLWE                                                      64 KiB
@@ -83,8 +83,8 @@ __device__ __forceinline__ void l64_ntt_forward(double *x, const double *__restr
         for (int b0 = 0; b0 < 2 * H; b0 += L64_THREADS) {
             const int b = b0 + (int)threadIdx.x, k = b & (H - 1), i = k >> logt;
             double *y = x + (b0 >= H ? N : 0) + (i << (logt + 1)) + (k & (t - 1));
-            if (b0 < H) g64_fwd_bfly<L0>(y, t, tw0[m + i]);
-            else g64_fwd_bfly<L1>(y, t, tw1[m + i]);
+            if (b0 < H) tp_fwd_bfly<L0>(y, t, tw0[m + i]);
+            else tp_fwd_bfly<L1>(y, t, tw1[m + i]);
         }
         __syncthreads();
     }
@@ -102,8 +102,8 @@ __device__ __forceinline__ void l64_ntt_inverse(double *x, const double *__restr
         for (int b0 = 0; b0 < 2 * H; b0 += L64_THREADS) {
             const int b = b0 + (int)threadIdx.x, k = b & (H - 1), i = k >> logt;
             double *y = x + (b0 >= H ? N : 0) + (i << (logt + 1)) + (k & (t - 1));
-            if (b0 < H) g64_inv_bfly<L0>(y, t, twi0[h + i]);
-            else g64_inv_bfly<L1>(y, t, twi1[h + i]);
+            if (b0 < H) tp_inv_bfly<L0>(y, t, twi0[h + i]);
+            else tp_inv_bfly<L1>(y, t, twi1[h + i]);
         }
         __syncthreads();
     }

@@ -1494,29 +1494,6 @@ __global__ __launch_bounds__(64) void k_bsk_convert64(const uint64_t *__restrict
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-typedef unsigned __int128 u128;
-uint64_t mulmod_u64(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((u128)a * b % p); }
-uint64_t powmod_u64(uint64_t a, uint64_t e, uint64_t p)
-{
-    uint64_t r = 1;
-    while (e) {
-        if (e & 1) r = mulmod_u64(r, a, p);
-        a = mulmod_u64(a, a, p);
-        e >>= 1;
-    }
-    return r;
-}
-double centred(uint64_t v, uint64_t p) { return v > p / 2 ? (double)((int64_t)v - (int64_t)p) : (double)(int64_t)v; }
-int bitrev(int x, int bits)
-{
-    int r = 0;
-    for (int i = 0; i < bits; i++) {
-        r = (r << 1) | (x & 1);
-        x >>= 1;
-    }
-    return r;
-}
-
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
@@ -1567,8 +1544,8 @@ struct SiKeyState {
     // HELM_SI_CREATE_ALLOW_GENERIC, or any shape under HELM_SI_CREATE_FORCE_GENERIC): always the 49-bit pair, its own key
     // layout (k_bsk_convert64_generic), no split key
     bool gen = false;
-    int gen_d = 1;                        // digit polynomials per batch (gen64_batch)
-    size_t gen_lds = 0;                   // LDS bytes per workgroup (Gen64Lds)
+    int gen_d = 1;                        // digit polynomials per batch (tp_batch, tp_fit)
+    size_t gen_lds = 0;                   // LDS bytes per workgroup (TwoPrimeLds<uint64_t>)
     int gen_per_cu = 1;                   // resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
     double *twi[2] = {nullptr, nullptr};  // bit-reversed powers of psi^-1 per field (the generic kernel's inverse transforms)
     // helm_si_ctx_create_ex under HELM_SI_CREATE_LARGE_N at N = 4096: k_pbs64_large runs every bootstrap launch, in the pair
@@ -1834,6 +1811,7 @@ hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_
 }
 #endif
 #if HELM_SI_TU == 0 // ==== everything below: the main unit only ===============================================
+#include "pbs_twoprime.h" // what k_pbs64_generic shares with the boolean engine's k_pbs_crt
 namespace {
 
 // k_pbs64_generic: k, pbs_l and pbs_logB at run time (helm_si_ctx_create_ex)
@@ -1863,7 +1841,7 @@ hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_
                                   const uint64_t *luts, uint64_t *out)
 {
     const SiKeyState &K = *ctx->keys;
-    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(G64_THREADS), K.gen_lds, ctx->stream, jobs,
+    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(TP_THREADS), K.gen_lds, ctx->stream, jobs,
                        small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.k,
                        ctx->P.pbs_l, ctx->P.pbs_logB, K.gen_d, K.p0inv_mod_p1);
     return hipGetLastError();
@@ -2395,16 +2373,6 @@ uint64_t si_psi(int N, int pair, int f)
     return 0;
 }
 
-// out[i] = root^i mod p (centred), i < count; rev_bits > 0: power i goes to the bit-reversed index
-void power_table(double *out, uint64_t root, uint64_t p, int count, int rev_bits)
-{
-    uint64_t a = 1;
-    for (int i = 0; i < count; i++) {
-        out[rev_bits ? bitrev(i, rev_bits) : i] = centred(a, p);
-        a = mulmod_u64(a, root, p);
-    }
-}
-
 // The forward twiddle tables (bit-reversed powers of psi), 1/N, 2^32 and the CRT constant of one pair of fields.  pair 1: with
 // psi^(N/4) = b the first three table entries are b^2, b, b^3 - what the plain radix-4 top of a forward transform on digits
 // multiplies by (fwd_top2_digits).
@@ -2455,33 +2423,13 @@ int setup_generic(helm_si_ctx *ctx)
     }
     const int group = P.grouping_factor > 1 ? P.grouping_factor : 1;
     const void *kern = pbs64_generic_kernel(logN, group);
-    // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a context
-    // created later with a smaller one cannot lower it under an earlier context's launches
-    const int K1max = 4096 / N;
-    const size_t lds_max = Gen64Lds(N, K1max, gen64_batch(N, K1max - 1, 31), 1024).bytes;
-    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-    auto occupancy = [&](int d, int &nb) -> int {
-        nb = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, G64_THREADS, Gen64Lds(N, P.k + 1, d, P.n).bytes));
-        return 0;
-    };
-    int nb1 = 0;
-    if (int rc = occupancy(1, nb1)) return rc;
-    if (nb1 < 1)
-        return fail(HELM_ERR_INVALID, "k_pbs64_generic: no workgroup of " + std::to_string(Gen64Lds(N, P.k + 1, 1, P.n).bytes) +
-                                          " B LDS fits a CU for this shape");
-    // digit polynomials per batch: the most (<= gen64_batch) that cost no resident workgroup against one per batch
-    K.gen_d = 1;
-    for (int d = gen64_batch(N, P.k, P.pbs_l); d > 1; d--) {
-        int nb = 0;
-        if (int rc = occupancy(d, nb)) return rc;
-        if (nb == nb1) {
-            K.gen_d = d;
-            break;
-        }
-    }
-    K.gen_lds = Gen64Lds(N, P.k + 1, K.gen_d, P.n).bytes;
-    K.gen_per_cu = nb1;
+    TwoPrimeFit fit;
+    HIP_TRY(tp_fit<uint64_t>(kern, N, P.k, P.pbs_l, P.n, fit));
+    if (fit.per_cu < 1)
+        return fail(HELM_ERR_INVALID, "k_pbs64_generic: no workgroup of " + std::to_string(fit.lds) + " B LDS fits a CU for this shape");
+    K.gen_d = fit.d;
+    K.gen_lds = fit.lds;
+    K.gen_per_cu = fit.per_cu;
     K.gen = true;
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
@@ -2913,7 +2861,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     } else if (K.gen) {
         // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
 #define GEN64_CONVERT(LN)                                                                                                 \
-    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(G64_THREADS), 0, ctx->stream, d_std, K.bsk,   \
+    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(TP_THREADS), 0, ctx->stream, d_std, K.bsk,   \
                        K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l)
         if (ctx->logN == 8) GEN64_CONVERT(8);
         else if (ctx->logN == 9) GEN64_CONVERT(9);

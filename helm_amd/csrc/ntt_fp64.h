@@ -871,4 +871,36 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[Geo<LOGN>::E], double *x
     }
 }
 
+// ---- host side: the integers behind the tables of a field (both engines' context set-up) ----
+inline uint64_t mulmod_u64(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((unsigned __int128)a * b % p); }
+inline uint64_t powmod_u64(uint64_t a, uint64_t e, uint64_t p)
+{
+    uint64_t r = 1;
+    while (e) {
+        if (e & 1) r = mulmod_u64(r, a, p);
+        a = mulmod_u64(a, a, p);
+        e >>= 1;
+    }
+    return r;
+}
+inline double centred(uint64_t v, uint64_t p) { return v > p / 2 ? (double)((int64_t)v - (int64_t)p) : (double)(int64_t)v; }
+inline int bitrev(int x, int bits)
+{
+    int r = 0;
+    for (int i = 0; i < bits; i++) {
+        r = (r << 1) | (x & 1);
+        x >>= 1;
+    }
+    return r;
+}
+// out[i] = root^i mod p (centred), i < count; rev_bits > 0: power i goes to the bit-reversed index
+inline void power_table(double *out, uint64_t root, uint64_t p, int count, int rev_bits)
+{
+    uint64_t a = 1;
+    for (int i = 0; i < count; i++) {
+        out[rev_bits ? bitrev(i, rev_bits) : i] = centred(a, p);
+        a = mulmod_u64(a, root, p);
+    }
+}
+
 } // namespace helm

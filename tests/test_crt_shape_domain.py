@@ -127,13 +127,14 @@ def _centred(v, p):
 
 
 def _lift32(r0, r1):
-    """(uint32_t)r0 + (uint32_t)p0 (uint32_t)t with t = reduce<F1>(mulmod<F1>(reduce<F1>(r1 - r0), p0^-1 mod p1)); every value
-    the kernel forms is checked to stay below 2^63 in magnitude (the modular products are fused in mulmod: their operands and
-    results are what is formed), r0 and t below 2^51 (to_torus32's range)."""
-    d = _centred(r1 - r0, P1)
-    t = _centred(d * _centred(P0INV, P1), P1)
-    for v in (r0, r1, r1 - r0, d, t):
+    """(uint32_t)r0 + (uint32_t)p0 (uint32_t)t with t = reduce<F1>(mulmod<F1>(r1 - r0, p0^-1 mod p1)) (tp_quotient,
+    pbs_twoprime.h: r1 - r0 goes into the multiplication unreduced, below mulmod's 2^53); every value the kernel forms is
+    checked to stay below 2^63 in magnitude (the modular products are fused in mulmod: their operands and results are what
+    is formed), r0 and t below 2^51 (to_torus32's range)."""
+    t = _centred((r1 - r0) * _centred(P0INV, P1), P1)
+    for v in (r0, r1, r1 - r0, t):
         assert abs(v) < LIM
+    assert abs(r1 - r0) < 1 << 53
     assert abs(r0) < 1 << 51 and abs(t) < 1 << 51
     word = (r0 % M32) + (P0 % M32) * (t % M32)
     assert word < 1 << 64
@@ -187,7 +188,7 @@ def test_the_creation_time_arithmetic():
     assert 97.4 < np.log2(float(P0 * P1 // 2)) < 97.6
     assert P0 == 5072 ** 4 + 1 and P1 == 5096 ** 4 + 1 and (P1 - 1) % 4096 == 0 and (P1 - 1) % 8192 != 0   # N <= 2048
     assert P0INV * P0 % P1 == 1
-    # the LDS layout at the domain's edge (CrtLds): acc u32, col 2 doubles, dig 2 D doubles, ms u16
+    # the LDS layout at the domain's edge (TwoPrimeLds<uint32_t>): acc u32, col 2 doubles, dig 2 D doubles, ms u16
     for N, D in ((1024, 1), (2048, 1), (256, 4)):
         assert 4 * 4096 + 16 * 4096 + 16 * D * N + 2 * 1025 <= 160 * 1024
 

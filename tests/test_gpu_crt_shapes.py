@@ -49,7 +49,7 @@ def test_crt_shape_end_to_end(shape):
     sk = helm_amd.ServerKey(ck, crt="allow")   # "capacity" without the flag; no such entry point before this kernel
     assert sk.kernel_class() == "crt" and sk.field_bits() == 98 and sk.short_root_stages() == 0
     qn, d = (p.k + 1) * p.pbs_l, sk.digit_batch()
-    assert 1 <= d <= min(4, max(1, 1024 // p.N), qn)                     # crt_batch's cap
+    assert 1 <= d <= min(4, max(1, 1024 // p.N), qn)                     # tp_batch's cap
     if shape in X.PARTIAL_BATCH:
         assert d > 1 and qn % d != 0, (d, qn)                            # the partial last batch runs here
     rng = np.random.default_rng(1)

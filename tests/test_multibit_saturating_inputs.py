@@ -1,6 +1,7 @@
 """tests/saturation_mb.py pinned on the CPU: the construction against both oracle routes, the peak it reaches as an exact
 fraction of the loader's bound, the loader's rule and the figure of its refusal text, the list of shapes, and a model of every
-CRT lift of the 64-bit engine that says up to which fraction of the half-modulus the lift is the exact integer.
+CRT lift of the 64-bit engine (and of the boolean engine's k_pbs_crt, which shares the generic kernel's quotient) that says up
+to which fraction of the half-modulus the lift is the exact integer.
 
 The lift.  Every 64-bit bootstrap kernel ends a step with x = r0 + p0 t, t = (r1 - r0) p0^-1 mod p1, where r0, r1 are the
 residues of the exact integer column coefficient x.  With t* = (x - r0) / p0 the true quotient, |t*| <= (|x| + |r0|) / p0, and
@@ -232,10 +233,21 @@ def lift_sites():
     mb = re.search(r"const double t = ADD \? tq : reduce<F1>\(tq\);", body) is not None
     sites["lift_pairs, classical (ADD)"] = (P0, P1, cent(P0) + cent(P1), cent(P0), False)
     sites["lift_pairs, multi-bit"] = (P0, P1, cent(P0) + cent(P1), cent(P0), mb)
+    # the two-prime generic kernels of both engines share one quotient (pbs_twoprime.h): the recentred statement once there,
+    # and each kernel's lifts go through it
+    shared = "mulmod<FpG2>(r1 - r0, p0inv_mod_p1)"
+    body = _function_text("pbs_twoprime.h", "double tp_quotient(", "\n}\n")
+    assert body.count("reduce<FpG2>(" + shared + ")") == 1 and body.count(shared) == 1 and body.count("mulmod") == 1
+    call = "tp_quotient(r0, r1, p0inv_mod_p1)"
     body = _function_text("helm_pbs64_generic.inc", "void k_pbs64_generic(", "\n}\n")
-    assert body.count("reduce<F1>(" + plain + ")") == 2 and body.count(plain) == 2
+    assert body.count(call) == 2 and "mulmod<F1>(r1" not in body
     sites["k_pbs64_generic, classical"] = (P0, P1, cent(P0) + cent(P1), cent(P0), True)
     sites["k_pbs64_generic, multi-bit"] = (P0, P1, cent(P0) + cent(P1), cent(P0), True)
+    body = _function_text("helm_pbs_crt.inc", "uint32_t crt_lift32(", "\n}\n")
+    assert body.count(call) == 1 and "mulmod" not in body
+    body = _function_text("helm_pbs_crt.inc", "void k_pbs_crt(", "\n}\n")
+    assert body.count("crt_lift32(") == 1 and "mulmod<FpG2>(r1" not in body and "tp_quotient" not in body
+    sites["k_pbs_crt"] = (P0, P1, cent(P0) + cent(P1), cent(P0), True)
     return sites
 
 
@@ -263,6 +275,9 @@ def admitted_fractions():
         "lift_pairs, multi-bit": 1 / 1.001,                             # ... bound x 1.001 < p0 p1 / 2, group sums
         "k_pbs64_generic, classical": S.nearest_capacity_shape(64, 12)[1],
         "k_pbs64_generic, multi-bit": 1 / 1.001,
+        # the boolean engine's CRT domain has no capacity check: its largest exact product is below 2^78 whatever the
+        # shape (test_crt_shape_domain.py::test_the_creation_time_arithmetic, the static_assert beside crt_admitted)
+        "k_pbs_crt": 2.0 ** 78 / S.HALF_49,
     }
 
 
