@@ -170,6 +170,7 @@ HIP_API = {
     "helm_hip_set_stream": (C.c_int, [vp, vp]),
     "helm_hip_sync": (C.c_int, [vp]),
     "helm_hip_launch_quantum": (C.c_int64, [vp]),
+    "helm_hip_wire_words": (C.c_int64, [vp]),
     "helm_hip_kernel_class": (C.c_int, [vp]),
     "helm_hip_digit_batch": (C.c_int, [vp]),
     "helm_hip_launch_costs": (C.c_int, [vp, C.POINTER(C.c_double)]),
@@ -323,6 +324,7 @@ CLIENT_API = {
     "helm_client_keygen": (C.c_int, [C.POINTER(Params), C.c_double, C.c_double, C.c_uint64, C.POINTER(vp)]),
     "helm_client_key_free": (None, [vp]),
     "helm_client_params": (C.c_int, [vp, C.POINTER(Params)]),
+    "helm_client_ct_words": (C.c_int64, [vp]),
     "helm_client_bsk_words": (C.c_size_t, [vp]),
     "helm_client_ksk_words": (C.c_size_t, [vp]),
     "helm_client_bsk": (u32p, [vp]),

@@ -55,7 +55,7 @@ class EncWireMap:
         if _handle is None:
             h = H.vp()
             H.check(H.host.helm_host_enc_map_new(server_key._h, C.byref(h)))
-            _handle, _n = h, server_key.params.n
+            _handle, _n = h, server_key.wire_words() - 1
         self._h, self._n = _handle, _n
 
     def __del__(self):
@@ -111,7 +111,7 @@ class GateCircuit(EvalCircuit):
         H.check(H.host.helm_host_gate_circuit_new(client_key._h, server_key._h, circuit._h, C.byref(h)))
         self._h = h
         self._ck, self._sk, self.circuit = client_key, server_key, circuit  # keep alive
-        self._n = server_key.params.n
+        self._n = server_key.wire_words() - 1
 
     def __del__(self):
         if getattr(self, "_h", None):

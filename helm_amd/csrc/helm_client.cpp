@@ -87,6 +87,19 @@ int helm_client_named_params(const char *name, helm_hip_params *p, double *lwe_s
         p->n = 16; p->k = 2; p->N = 1024; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 4; p->ks_logB = 4;
         *lwe_std = 1e-7;
         *glwe_std = 3e-16;
+    } else if (s == "boolean_default_ks_pbs") {
+        // tfhe 0.4.1 boolean::DEFAULT_PARAMETERS_KS_PBS [recalled from memory, in the sense of SURVEY.md App. B, with
+        // low-to-medium confidence: check against the tfhe release at hand before relying on its security or failure
+        // probability].  boolean_default's GLWE shape and decompositions (the tuned kernels), a smaller n and a larger LWE
+        // noise; ciphertexts live under the GLWE key (pbs_order = 1: helm_hip_ctx_create_ex with HELM_HIP_CREATE_KS_PBS)
+        p->n = 664; p->k = 2; p->N = 512; p->pbs_l = 3; p->pbs_logB = 6; p->ks_l = 4; p->ks_logB = 3;
+        p->pbs_order = 1;
+        *lwe_std = 0.0000380828277062;
+        *glwe_std = 0.00000004990272175010415;
+    } else if (s == "toy_ks_pbs" || s == "toy_k2_ks_pbs" || s == "toy_1024_ks_pbs") {
+        // the toy sets with keyswitch-first order: same shape and noise values, pbs_order = 1
+        if (int rc = helm_client_named_params(s.substr(0, s.size() - 7).c_str(), p, lwe_std, glwe_std)) return rc;
+        p->pbs_order = 1;
     } else
         return fail(HELM_ERR_INVALID, "unknown parameter set '" + s + "'");
     return 0;
@@ -99,6 +112,7 @@ int helm_client_keygen(const helm_hip_params *params, double lwe_std, double glw
     *out = nullptr;
     const helm_hip_params &P = *params;
     if (P.torus_bits != 32) return fail(HELM_ERR_INVALID, "only torus_bits = 32");
+    if (P.pbs_order != 0 && P.pbs_order != 1) return fail(HELM_ERR_INVALID, "pbs_order must be 0 or 1");
     if (P.n < 1 || P.k < 1 || P.N < 2 || (P.N & (P.N - 1)) || P.pbs_l < 1 || P.ks_l < 1 ||
         P.pbs_logB * P.pbs_l > 32 || P.ks_logB * P.ks_l > 32 || P.pbs_logB < 1 || P.ks_logB < 1)
         return fail(HELM_ERR_INVALID, "bad parameter set");
@@ -185,6 +199,11 @@ int helm_client_params(const helm_client_key *key, helm_hip_params *out)
     *out = key->P;
     return 0;
 }
+int64_t helm_client_ct_words(const helm_client_key *key)
+{
+    if (!key) return fail(HELM_ERR_INVALID, "null argument");
+    return (key->P.pbs_order == 1 ? (int64_t)key->P.k * key->P.N : (int64_t)key->P.n) + 1;
+}
 size_t helm_client_bsk_words(const helm_client_key *key) { return key ? key->bsk.size() : 0; }
 size_t helm_client_ksk_words(const helm_client_key *key) { return key ? key->ksk.size() : 0; }
 const uint32_t *helm_client_bsk(const helm_client_key *key) { return key ? key->bsk.data() : nullptr; }
@@ -195,13 +214,18 @@ const uint32_t *helm_client_glwe_secret(const helm_client_key *key) { return key
 int helm_client_encrypt_bool(helm_client_key *key, const uint8_t *bits, int64_t count, uint32_t *out)
 {
     if (!key || !bits || !out || count < 0) return fail(HELM_ERR_INVALID, "bad argument");
-    const int n = key->P.n;
+    // pbs_order = 1: under the GLWE key read as an LWE key of k*N bits, with the GLWE noise (the same draws in the same
+    // order over the other key: an order-0 key's words are what they always were)
+    const bool big = key->P.pbs_order == 1;
+    const int n = big ? key->P.k * key->P.N : key->P.n;
+    const uint32_t *sk = big ? key->glwe_sk.data() : key->lwe_sk.data();
+    const double std_dev = big ? key->glwe_std : key->lwe_std;
     for (int64_t g = 0; g < count; g++) {
         uint32_t *ct = out + (size_t)g * (n + 1);
-        uint32_t b = key->enc_rng.noise32(key->lwe_std);
+        uint32_t b = key->enc_rng.noise32(std_dev);
         for (int i = 0; i < n; i++) {
             ct[i] = key->enc_rng.u32();
-            if (key->lwe_sk[i]) b += ct[i];
+            if (sk[i]) b += ct[i];
         }
         ct[n] = b + (bits[g] ? 0x20000000u : 0xE0000000u);
     }
@@ -227,7 +251,7 @@ int helm_client_decrypt_bool(const helm_client_key *key, const uint32_t *lwe, in
 {
     if (!key || !lwe || !bits || count < 0) return fail(HELM_ERR_INVALID, "bad argument");
     std::vector<uint32_t> ph((size_t)count);
-    if (int rc = helm_client_phase(key, lwe, count, 0, ph.data())) return rc;
+    if (int rc = helm_client_phase(key, lwe, count, key->P.pbs_order == 1, ph.data())) return rc;
     for (int64_t g = 0; g < count; g++) bits[g] = ph[(size_t)g] < 0x80000000u; // circuit.rs:948
     return 0;
 }

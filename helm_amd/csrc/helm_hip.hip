@@ -1907,6 +1907,154 @@ __global__ __launch_bounds__(256) void k_ks_zero(const KsJob *__restrict__ jobs,
 }
 
 // ------------------------------------------------------------------------------------
+// Keyswitch-first levels (pbs_order = 1: wires are big LWE rows of k*N + 1 words under the GLWE key).  A gate is linear
+// combination -> keyswitch -> bootstrap, so the keyswitch is the front of the level: k_keyswitch_gate and k_ks_gate_digits
+// are k_keyswitch and k_ks_digits fed by the level's PbsJob list - they form gate_lincomb() of up to three wire rows as they
+// read them (the +-1/8 on the body word, index k*N) - with the same decompose<>, the same packed-byte LDS layout and row
+// split, the same A-fragment order, dsum and body arrays (k_ks_mfma runs unchanged behind k_ks_gate_digits).  The small row
+// of job i is row i of the context's staging buffer (`out`); the blind-rotate kernels then take those rows as raw LWEs.
+// ------------------------------------------------------------------------------------
+struct GateRows {
+    const uint32_t *a0, *a1, *a2;
+    __device__ __forceinline__ GateRows(const PbsJob &job, const uint32_t *wires, size_t row)
+        : a0(job.in0 >= 0 ? wires + row * (size_t)job.in0 : nullptr), a1(job.in1 >= 0 ? wires + row * (size_t)job.in1 : nullptr),
+          a2(job.in2 >= 0 ? wires + row * (size_t)job.in2 : nullptr)
+    {
+    }
+    __device__ __forceinline__ uint32_t word(const PbsJob &job, int i, bool body) const
+    {
+        return gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, body);
+    }
+};
+
+template <int KSL>
+__global__ __launch_bounds__(256) void k_keyswitch_gate(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
+                                                        const uint32_t *__restrict__ ksk, uint32_t *__restrict__ out,
+                                                        int n, int kN, int logB, int count, int t_chunk)
+{
+    // grid, LDS layout and row split of k_keyswitch; gate g0 + g writes row g0 + g of `out`
+    constexpr int G = 4;
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint32_t *DIG = reinterpret_cast<uint32_t *>(smem); // [t_chunk * KSL] words, byte g = digit of gate g
+    const int g0 = blockIdx.x * G;
+    const int ng = min(G, count - g0);
+    const int t0 = blockIdx.z * t_chunk, t1 = min(kN, t0 + t_chunk);
+    const size_t brow = (size_t)kN + 1;
+    PbsJob job[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) job[g] = jobs[g0 + (g < ng ? g : 0)];
+    for (int t = t0 + threadIdx.x; t < t1; t += 256) {
+        uint32_t packed[KSL];
+#pragma unroll
+        for (int j = 0; j < KSL; j++) packed[j] = 0;
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g < ng) {
+                const uint32_t v = GateRows(job[g], wires, brow).word(job[g], t, false);
+                int dig[KSL];
+                decompose<KSL>(v, logB, dig);
+#pragma unroll
+                for (int j = 0; j < KSL; j++) packed[j] |= ((uint32_t)dig[j] & 0xFFu) << (8 * g);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KSL; j++) DIG[(t - t0) * KSL + j] = packed[j];
+    }
+    __syncthreads();
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c > n) return;
+    const size_t krow = (size_t)n + 1;
+    uint32_t acc[G] = {0, 0, 0, 0};
+    const uint32_t *kp = ksk + (size_t)t0 * KSL * krow + c;
+    const int rows = (t1 - t0) * KSL;
+#pragma unroll 8
+    for (int r = 0; r < rows; r++) {
+        const uint32_t w = kp[(size_t)r * krow];
+        const uint32_t pk = DIG[r];
+#pragma unroll
+        for (int g = 0; g < G; g++) acc[g] += (uint32_t)__builtin_amdgcn_sbfe(pk, 8 * g, 8) * w;
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        if (g < ng) {
+            uint32_t body = 0;
+            if (c == n && blockIdx.z == 0) body = GateRows(job[g], wires, brow).word(job[g], kN, true);
+            uint32_t *dst = out + krow * (size_t)(g0 + g) + c;
+            if (gridDim.z == 1) *dst = body - acc[g];
+            else atomicAdd(dst, body - acc[g]);
+        }
+    }
+}
+
+template <int KSL>
+__global__ __launch_bounds__(256) void k_ks_gate_digits(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
+                                                        int8_t *__restrict__ dig, int32_t *__restrict__ dsum,
+                                                        uint32_t *__restrict__ body, int kN, int logB, int count, int kchunks)
+{
+    const int g = blockIdx.x; // padded gate index; g >= count: an all-zero row
+    __shared__ int red[256];
+    int local = 0;
+    const bool live = g < count;
+    PbsJob job{};
+    if (live) job = jobs[g];
+    const GateRows rows(job, wires, (size_t)kN + 1);
+    int8_t *tile = dig + (size_t)(g >> 4) * kchunks * 1024;
+    for (int t = threadIdx.x; t < kN; t += 256) {
+        int d[KSL];
+        if (live) {
+            decompose<KSL>(rows.word(job, t, false), logB, d);
+        } else {
+#pragma unroll
+            for (int j = 0; j < KSL; j++) d[j] = 0;
+        }
+        const int r0 = t * KSL, kc = r0 >> 6, kq = (r0 & 63) >> 4, j0 = r0 & 15;
+        int8_t *dst = tile + ((size_t)kc * 64 + (kq << 4 | (g & 15))) * 16 + j0;
+#pragma unroll
+        for (int j = 0; j < KSL; j++) {
+            dst[j] = (int8_t)d[j];
+            local += d[j];
+        }
+    }
+    red[threadIdx.x] = local;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        dsum[g] = red[0];
+        body[g] = live ? rows.word(job, kN, true) : 0u;
+    }
+}
+
+// raw[i] = {op -1, in0 = i, tv 0} (the bootstrap of staging row i), ident[i] = {out = i} (k_ks_mfma's and k_ks_zero's
+// destination of job i): the two job lists of a keyswitch-first level that do not depend on the level
+__global__ __launch_bounds__(256) void k_iota_jobs(PbsJob *__restrict__ raw, KsJob *__restrict__ ident, int count)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    raw[i] = PbsJob{-1, 0, i, -1, -1, 0};
+    ident[i] = KsJob{i, -1, i, 0u};
+}
+
+// k_big_out: dst[out] = big[big0] (+ big[big1]) over k*N + 1 words, add_body on the body word - the scatter of the extracted
+// rows into the wire table (or a shard's staging chunk) and the MUX recombination of a keyswitch-first level.
+__global__ __launch_bounds__(256) void k_big_out(const KsJob *__restrict__ jobs, const uint32_t *__restrict__ big,
+                                                 uint32_t *__restrict__ dst, int kN)
+{
+    const KsJob job = jobs[blockIdx.x];
+    const size_t row = (size_t)kN + 1;
+    const uint32_t *b0 = big + row * (size_t)job.big0, *b1 = job.big1 >= 0 ? big + row * (size_t)job.big1 : nullptr;
+    uint32_t *d = dst + row * (size_t)job.out;
+    for (int i = threadIdx.x; i <= kN; i += 256) {
+        uint32_t v = b0[i];
+        if (b1) v += b1[i];
+        if (i == kN) v += job.add_body;
+        d[i] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // k_linear: NOT / BUF / DFF / constants.  One workgroup per gate.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_linear(const LinJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
@@ -2129,6 +2277,12 @@ struct helm_hip_ctx {
     DevBuf<KsJob> d_ks;
     DevBuf<LinJob> d_lin;
     DevBuf<uint32_t> d_big;
+    // keyswitch-first levels (pbs_order = 1): the small rows between the gate keyswitch and the bootstrap, and the two job
+    // lists that do not depend on the level (k_iota_jobs), filled up to iota_filled
+    DevBuf<uint32_t> d_small;
+    DevBuf<PbsJob> d_raw;
+    DevBuf<KsJob> d_ident;
+    size_t iota_filled = 0;
     // timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pbs, ev_pbs_main, ev_ks, ev_lin, ev_xchg;
@@ -2180,6 +2334,9 @@ static void release_overlap(helm_hip_program *pr)
         v->clear();
     }
 }
+
+// Words of the mask of a wire row: n in order 0 (wires under the small key), k N in order 1 (under the GLWE key)
+static int wire_dim(const helm_hip_ctx *ctx) { return ctx->P.pbs_order == 1 ? ctx->P.k * ctx->P.N : ctx->P.n; }
 
 static bool needs_pbs(int op)
 {
@@ -2630,7 +2787,8 @@ static bool crt_admitted(const helm_hip_params &P)
 {
     return (P.N == 256 || P.N == 512 || P.N == 1024 || P.N == 2048) && P.k >= 1 && (int64_t)(P.k + 1) * P.N <= 4096 &&
            P.pbs_l >= 1 && P.pbs_logB >= 1 && (int64_t)P.pbs_logB * P.pbs_l <= 31 && P.n >= 1 && P.n <= 1024 &&
-           P.pbs_order == 0 && P.grouping_factor == 1;
+           (P.pbs_order == 0 || P.pbs_order == 1) && P.grouping_factor == 1; // (order 1: only under HELM_HIP_CREATE_KS_PBS,
+                                                                              // which helm_hip_ctx_create_ex has checked)
 }
 // The CRT domain needs no capacity check: the largest exact product over it, (k+1) N <= 4096 times l 2^(logB-1) <= 31 x 2^30
 // (logB l <= 31) times 2^31, is 4096 x 31 x 2^61 = 2^77.96 < 2^78, and p0 p1 / 2 = 2^97.5.
@@ -2734,12 +2892,120 @@ static hipError_t launch_ks(helm_hip_ctx *ctx, const KsJob *jobs, int64_t count,
     return hipGetLastError();
 }
 
+// pbs_order = 1: the level-independent job lists of `count` rows (grown on demand, filled on the context's stream)
+static hipError_t ensure_iota_jobs(helm_hip_ctx *ctx, int64_t count)
+{
+    if ((size_t)count <= ctx->iota_filled) return hipSuccess;
+    ctx->iota_filled = 0;
+    if (ctx->d_raw.ensure((size_t)count) || ctx->d_ident.ensure((size_t)count)) return hipErrorOutOfMemory;
+    const size_t fill = std::min(ctx->d_raw.cap, ctx->d_ident.cap);
+    hipLaunchKernelGGL(k_iota_jobs, dim3((unsigned)((fill + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_raw.p, ctx->d_ident.p,
+                       (int)fill);
+    hipError_t e = hipGetLastError();
+    // the lists outlive this launch and helm_hip_set_stream may move the context to another stream before the next one:
+    // wait once, where the buffers grew (the allocation above has synchronised the device already) - never in a round
+    // that finds them large enough
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) ctx->iota_filled = fill;
+    return e;
+}
+
+// The front of a keyswitch-first level: launch_ks with the gate's linear combination folded into the read - job i of the
+// level's PbsJob list, over the big wire rows, to row i of `out`.  Same path choice, padding, slices and LDS size.
+static hipError_t launch_ks_gate(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires, uint32_t *out)
+{
+    const helm_hip_params &P = ctx->P;
+    const int kN = P.k * P.N;
+    if (ctx->ksk_planes && ctx->ks_mfma) {
+        const int64_t padded = (count + 63) / 64 * 64;
+        if (ctx->d_dig.ensure((size_t)padded * kN * P.ks_l) || ctx->d_dsum.ensure((size_t)padded) || ctx->d_body.ensure((size_t)padded))
+            return hipErrorOutOfMemory;
+#define KSD_CASE(LV)                                                                                                        \
+    case LV:                                                                                                                \
+        hipLaunchKernelGGL(k_ks_gate_digits<LV>, dim3((unsigned)padded), dim3(256), 0, ctx->stream, jobs, wires, ctx->d_dig.p, \
+                           ctx->d_dsum.p, ctx->d_body.p, kN, P.ks_logB, (int)count, ctx->ks_kchunks);                      \
+        break;
+        switch (P.ks_l) {
+            KSD_CASE(1) KSD_CASE(2) KSD_CASE(4) KSD_CASE(8)
+        default: return hipErrorInvalidValue;
+        }
+#undef KSD_CASE
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ks_mfma, dim3((unsigned)(padded / 64), (unsigned)((ctx->ks_ctiles + 1) / 2)), dim3(64), 0, ctx->stream,
+                           ctx->d_ident.p, ctx->d_dig.p, ctx->d_dsum.p, ctx->d_body.p, ctx->ksk_planes, out, P.n, (int)count,
+                           ctx->ks_kchunks, ctx->ks_ctiles);
+        return hipGetLastError();
+    }
+    const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((P.n + 1 + 255) / 256);
+    int slices = 1;
+    while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)ctx->n_cus && kN / (slices * 2) >= 64) slices *= 2;
+    const int t_chunk = (kN + slices - 1) / slices;
+    dim3 grid(gx, gy, (unsigned)slices);
+    const size_t lds = (size_t)t_chunk * P.ks_l * sizeof(uint32_t);
+    if (slices > 1) {
+        hipLaunchKernelGGL(k_ks_zero, dim3((unsigned)count), dim3(256), 0, ctx->stream, ctx->d_ident.p, out, P.n);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+#define KS_CASE(LV)                                                                                                  \
+    case LV:                                                                                                         \
+        hipLaunchKernelGGL(k_keyswitch_gate<LV>, grid, dim3(256), lds, ctx->stream, jobs, wires, ctx->ksk, out, P.n, kN, \
+                           P.ks_logB, (int)count, t_chunk);                                                          \
+        break;
+    switch (P.ks_l) {
+        KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) KS_CASE(5) KS_CASE(6) KS_CASE(8)
+    default: return hipErrorInvalidValue;
+    }
+#undef KS_CASE
+    return hipGetLastError();
+}
+
+// A keyswitch-first level (pbs_order = 1): gate keyswitch from the big wire rows to the small staging, bootstrap of the
+// staging rows as raw LWEs, k_big_out from the extracted rows to `dst` (MUX: the sum of its two halves + 1/8), k_linear at
+// dimension k N.  k_big_out writes only after every keyswitch of the level has read, so a gate may update its row in place.
+static int run_level_device_ks_first(helm_hip_ctx *ctx, const PbsJob *d_pbs, int64_t n_pbs, const KsJob *d_ks, int64_t n_ks,
+                                     const LinJob *d_lin, int64_t n_lin, const uint32_t *wires_in, uint32_t *dst)
+{
+    const helm_hip_params &P = ctx->P;
+    const int kN = P.k * P.N;
+    if (n_pbs > 0) {
+        if (!ctx->have_bsk || !ctx->have_ksk) return fail(HELM_ERR_STATE, "bootstrapping / keyswitching key not loaded");
+        if (ctx->d_big.ensure((size_t)n_pbs * ((size_t)kN + 1))) return fail(HELM_ERR_OOM, "big-LWE scratch");
+        if (ctx->d_small.ensure((size_t)n_pbs * ((size_t)P.n + 1))) return fail(HELM_ERR_OOM, "small-LWE staging");
+        HIP_TRY(ensure_iota_jobs(ctx, n_pbs));
+        {
+            TimedScope t(ctx, &ctx->ev_ks);
+            HIP_TRY(launch_ks_gate(ctx, d_pbs, n_pbs, wires_in, ctx->d_small.p));
+        }
+        ctx->tacc.ks_launches++;
+        ctx->tacc.ks_count += n_pbs;
+        {
+            TimedScope t(ctx, &ctx->ev_pbs);
+            HIP_TRY(launch_pbs(ctx, ctx->d_raw.p, n_pbs, nullptr, ctx->d_small.p, ctx->tv_bool, ctx->d_big.p));
+        }
+        ctx->tacc.pbs_launches++;
+        ctx->tacc.pbs_count += n_pbs;
+        {
+            TimedScope t(ctx, &ctx->ev_ks);
+            hipLaunchKernelGGL(k_big_out, dim3((unsigned)n_ks), dim3(256), 0, ctx->stream, d_ks, ctx->d_big.p, dst, kN);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (n_lin > 0) {
+        TimedScope t(ctx, &ctx->ev_lin);
+        hipLaunchKernelGGL(k_linear, dim3((unsigned)n_lin), dim3(256), 0, ctx->stream, d_lin, wires_in, dst, kN);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
 
 // Run one planned level whose job arrays are already on the device.
 static int run_level_device(helm_hip_ctx *ctx, const PbsJob *d_pbs, int64_t n_pbs, const KsJob *d_ks, int64_t n_ks,
                             const LinJob *d_lin, int64_t n_lin, const uint32_t *wires_in, uint32_t *dst)
 {
     const helm_hip_params &P = ctx->P;
+    if (P.pbs_order == 1) return run_level_device_ks_first(ctx, d_pbs, n_pbs, d_ks, n_ks, d_lin, n_lin, wires_in, dst);
     if (n_pbs > 0) {
         if (!ctx->have_bsk || !ctx->have_ksk) return fail(HELM_ERR_STATE, "bootstrapping / keyswitching key not loaded");
         if (ctx->d_big.ensure((size_t)n_pbs * ((size_t)P.k * P.N + 1))) return fail(HELM_ERR_OOM, "big-LWE scratch");
@@ -2867,18 +3133,25 @@ int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_
 {
     if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (flags & ~(uint32_t)(HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
+    // HELM_HIP_CREATE_KS_PBS admits pbs_order = 1 and changes nothing else: the CRT flags are judged on the remaining bits
+    const bool ks_pbs = (flags & HELM_HIP_CREATE_KS_PBS) != 0;
+    const uint32_t crt_flags = flags & ~(uint32_t)HELM_HIP_CREATE_KS_PBS;
+    if (crt_flags & ~(uint32_t)(HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
-                                          " (HELM_HIP_CREATE_ALLOW_CRT = 1, HELM_HIP_CREATE_FORCE_CRT = 2)");
-    if (flags == (HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
-        return fail(HELM_ERR_INVALID, "flags 3: HELM_HIP_CREATE_ALLOW_CRT and HELM_HIP_CREATE_FORCE_CRT exclude each other");
-    const bool allow_crt = flags == HELM_HIP_CREATE_ALLOW_CRT, force_crt = flags == HELM_HIP_CREATE_FORCE_CRT;
+                                          " (HELM_HIP_CREATE_ALLOW_CRT = 1, HELM_HIP_CREATE_FORCE_CRT = 2" +
+                                          (ks_pbs ? ", HELM_HIP_CREATE_KS_PBS = 16)" : ")"));
+    if (crt_flags == (HELM_HIP_CREATE_ALLOW_CRT | HELM_HIP_CREATE_FORCE_CRT))
+        return fail(HELM_ERR_INVALID, "flags " + std::to_string(flags) +
+                                          ": HELM_HIP_CREATE_ALLOW_CRT and HELM_HIP_CREATE_FORCE_CRT exclude each other");
+    const bool allow_crt = crt_flags == HELM_HIP_CREATE_ALLOW_CRT, force_crt = crt_flags == HELM_HIP_CREATE_FORCE_CRT;
     static const char *const crt_domain = "the CRT domain (HELM_HIP_CREATE_ALLOW_CRT / HELM_HIP_CREATE_FORCE_CRT) is N in {256, 512, 1024, "
                                           "2048}, k >= 1 with (k+1) N <= 4096, pbs_l >= 1 with pbs_logB pbs_l <= 31, n in [1,1024], "
                                           "pbs_order 0, grouping_factor 1";
     const helm_hip_params &P = *params;
     if (P.torus_bits != 32) return fail(HELM_ERR_INVALID, "only torus_bits = 32 is implemented");
-    if (P.pbs_order != 0) return fail(HELM_ERR_INVALID, "only pbs_order = 0 (bootstrap then keyswitch)");
+    if (P.pbs_order != 0 && !ks_pbs) return fail(HELM_ERR_INVALID, "only pbs_order = 0 (bootstrap then keyswitch)");
+    if (P.pbs_order != 0 && P.pbs_order != 1)
+        return fail(HELM_ERR_INVALID, "pbs_order must be 0 (bootstrap then keyswitch) or 1 (keyswitch then bootstrap)");
     if (P.grouping_factor != 1) return fail(HELM_ERR_INVALID, "multi-bit PBS (grouping_factor > 1) not implemented");
     if (force_crt && !crt_admitted(P))
         return fail(HELM_ERR_INVALID, std::string("HELM_HIP_CREATE_FORCE_CRT: unsupported (N,k,pbs_l): ") + crt_domain);
@@ -3057,6 +3330,9 @@ int helm_hip_ctx_destroy(helm_hip_ctx *ctx)
     ctx->d_ks.release();
     ctx->d_lin.release();
     ctx->d_big.release();
+    ctx->d_small.release();
+    ctx->d_raw.release();
+    ctx->d_ident.release();
     if (ctx->xchg_stream) (void)hipStreamDestroy(ctx->xchg_stream);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -3102,6 +3378,12 @@ int helm_hip_kernel_class(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
     return ctx->crt_class ? 2 : ctx->generic ? 1 : 0;
+}
+
+int64_t helm_hip_wire_words(const helm_hip_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return (int64_t)wire_dim(ctx) + 1;
 }
 
 int helm_hip_digit_batch(const helm_hip_ctx *ctx)
@@ -3335,7 +3617,7 @@ int helm_hip_wires_alloc(helm_hip_ctx *ctx, int64_t n_wires, helm_hip_wires **ou
     if (!w) return fail(HELM_ERR_OOM, "wires");
     w->owner = ctx;
     w->n_wires = n_wires;
-    const size_t bytes = (size_t)n_wires * ((size_t)ctx->P.n + 1) * sizeof(uint32_t);
+    const size_t bytes = (size_t)n_wires * ((size_t)wire_dim(ctx) + 1) * sizeof(uint32_t);
     if (hipMalloc(&w->d, bytes) != hipSuccess) {
         delete w;
         return fail(HELM_ERR_OOM, "wire table of " + std::to_string(bytes) + " bytes");
@@ -3385,14 +3667,14 @@ int helm_hip_wires_upload(helm_hip_ctx *ctx, helm_hip_wires *w, const int32_t *i
             return fail(HELM_ERR_INVALID, "upload names the same wire twice");
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = (size_t)ctx->P.n + 1;
+    const size_t row = (size_t)wire_dim(ctx) + 1;
     Scratch<uint32_t> d_rows;
     Scratch<int32_t> d_idx;
     HIP_TRY(d_rows.alloc((size_t)count * row));
     HIP_TRY(d_idx.alloc((size_t)count));
     HIP_TRY(hipMemcpyAsync(d_rows.p, lwe_host, (size_t)count * row * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_idx.p, idx, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, d_rows.p, d_idx.p, w->d, ctx->P.n);
+    hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, d_rows.p, d_idx.p, w->d, wire_dim(ctx));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3405,13 +3687,13 @@ int helm_hip_wires_download(helm_hip_ctx *ctx, helm_hip_wires *w, const int32_t 
     if (count == 0) return 0;
     if (int rc = check_idx(w, idx, count, false)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = (size_t)ctx->P.n + 1;
+    const size_t row = (size_t)wire_dim(ctx) + 1;
     Scratch<uint32_t> d_rows;
     Scratch<int32_t> d_idx;
     HIP_TRY(d_rows.alloc((size_t)count * row));
     HIP_TRY(d_idx.alloc((size_t)count));
     HIP_TRY(hipMemcpyAsync(d_idx.p, idx, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, w->d, d_idx.p, d_rows.p, ctx->P.n);
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, w->d, d_idx.p, d_rows.p, wire_dim(ctx));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(lwe_host, d_rows.p, (size_t)count * row * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -3442,7 +3724,7 @@ int helm_hip_wires_copy(helm_hip_ctx *ctx, helm_hip_wires *src, const int32_t *s
     HIP_TRY(d_dst.alloc((size_t)count));
     HIP_TRY(hipMemcpyAsync(d_src.p, src_idx, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_dst.p, dst_idx, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, src->d, d_src.p, dst->d, d_dst.p, ctx->P.n);
+    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)count), dim3(256), 0, ctx->stream, src->d, d_src.p, dst->d, d_dst.p, wire_dim(ctx));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3462,7 +3744,7 @@ int helm_hip_wires_set_trivial(helm_hip_ctx *ctx, helm_hip_wires *w, const int32
     HIP_TRY(d_val.alloc((size_t)count));
     HIP_TRY(hipMemcpyAsync(d_idx.p, idx, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_val.p, value, (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_set_trivial, dim3((unsigned)count), dim3(256), 0, ctx->stream, d_idx.p, d_val.p, w->d, ctx->P.n);
+    hipLaunchKernelGGL(k_set_trivial, dim3((unsigned)count), dim3(256), 0, ctx->stream, d_idx.p, d_val.p, w->d, wire_dim(ctx));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3784,7 +4066,7 @@ int helm_hip_program_run_level_shard(helm_hip_ctx *ctx, helm_hip_program *prog, 
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t *bd = prog->sh_bounds.data() + (size_t)level * (world + 1);
     const int64_t chunk = prog->sh_rows[(size_t)level], mine = bd[rank + 1] - bd[rank];
-    const size_t row = (size_t)ctx->P.n + 1;
+    const size_t row = (size_t)wire_dim(ctx) + 1;
     // padding rows of the staging chunk must be defined (they travel through the all-gather)
     if (mine < chunk)
         HIP_TRY(hipMemsetAsync(static_cast<uint32_t *>(staging_dev) + row * (size_t)mine, 0,
@@ -3802,7 +4084,7 @@ static int scatter_level_on(helm_hip_ctx *ctx, helm_hip_program *prog, helm_hip_
     const int64_t rb = prog->sh_rows_off[level], rows = prog->sh_rows_off[level + 1] - rb;
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)rows), dim3(256), 0, stream, static_cast<const uint32_t *>(gathered_dev),
-                       prog->s_rows.p + rb, w->d, ctx->P.n);
+                       prog->s_rows.p + rb, w->d, wire_dim(ctx));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3890,7 +4172,7 @@ int helm_hip_program_overlap_applies(helm_hip_program *prog)
 static int run_sharded_comm_overlapped(helm_hip_ctx *ctx, helm_hip_program *prog, helm_hip_wires *w, helm_comm *comm, int rank,
                                        int world, int64_t replicate_below, int64_t cap)
 {
-    const size_t row = (size_t)ctx->P.n + 1;
+    const size_t row = (size_t)wire_dim(ctx) + 1;
     if (!ctx->xchg_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->xchg_stream, hipStreamNonBlocking));
     for (auto &b : prog->x_ring)
         if (b.ensure((size_t)cap * world * row)) return fail(HELM_ERR_OOM, "gather ring");
@@ -3965,7 +4247,7 @@ int helm_hip_program_run_sharded_comm(helm_hip_ctx *ctx, helm_hip_program *prog,
     if (dev != ctx->device) return fail(HELM_ERR_STATE, "run_sharded_comm: the communicator lives on another device than the context");
     HIP_TRY(hipSetDevice(ctx->device)); // the gather buffers and the exchange stream below belong to the context's device
     if (int rc = shard_prepare(ctx, prog, rank, world)) return rc;
-    const size_t row = (size_t)ctx->P.n + 1;
+    const size_t row = (size_t)wire_dim(ctx) + 1;
     int64_t cap = 0;
     for (int64_t l = 0; l < prog->n_levels; l++)
         if (helm_hip_program_level_pbs(prog, l) > replicate_below) cap = std::max(cap, prog->sh_rows[(size_t)l]);

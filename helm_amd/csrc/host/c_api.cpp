@@ -272,9 +272,8 @@ int64_t helm_host_shard_bounds(const int32_t *opcode, int64_t count, int world, 
 int helm_host_enc_map_new(helm_hip_ctx *server_key, helm_enc_map **out)
 {
     return guard([&] {
-        helm_hip_params P;
-        if (!server_key || helm_hip_get_params(server_key, &P)) throw Panic("null server key");
-        *out = new helm_enc_map{std::make_unique<EncWireMap>(server_key, P.n)};
+        if (!server_key || helm_hip_wire_words(server_key) <= 0) throw Panic("null server key");
+        *out = new helm_enc_map{std::make_unique<EncWireMap>(server_key, (int)helm_hip_wire_words(server_key) - 1)};
     });
 }
 

@@ -137,9 +137,14 @@ std::unique_ptr<EncWireMap> EncWireMap::clone() const
 GateCircuit::GateCircuit(helm_client_key *client_key, helm_hip_ctx *server_key, Circuit circuit)
     : client_key_(client_key), server_key_(server_key), circuit_(std::move(circuit))
 {
-    helm_hip_params P;
-    client_ok(helm_client_params(client_key, &P), "client_params");
-    n_ = P.n;
+    // the row width comes from the context (n + 1 words, or k N + 1 under a keyswitch-first key); the client key must
+    // encrypt rows of that width
+    const int64_t words = helm_hip_wire_words(server_key);
+    if (words <= 0) throw Panic("GateCircuit: null server key");
+    if (helm_client_ct_words(client_key) != words)
+        throw Panic("GateCircuit: the client key encrypts rows of " + std::to_string(helm_client_ct_words(client_key)) +
+                    " words, the server key's wires have " + std::to_string(words) + " (pbs_order differs)");
+    n_ = (int)words - 1;
 }
 
 GateCircuit::~GateCircuit()

@@ -24,7 +24,7 @@ class GpuLevelExecutor:
         self.torch = torch
         self.program, self.wires = program, wires
         self.n_levels = program.n_levels
-        self.row_words = program.sk.params.n + 1
+        self.row_words = program.sk.wire_words()
         self.device = torch.device("cuda", program.sk.device)
 
     def bind_stream(self):

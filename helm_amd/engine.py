@@ -15,7 +15,8 @@ from ._native import Params, HipTiming as Timing, hip, host, hip_check, client_c
 
 def named_params(name):
     """-> (Params, lwe_noise_std, glwe_noise_std).  "boolean_tfhe_lib" and "toy_crt" lie beyond the single-prime capacity bound:
-    a server key for them needs ServerKey(..., crt="allow") (gen_keys(name, crt="allow"))."""
+    a server key for them needs ServerKey(..., crt="allow") (gen_keys(name, crt="allow")).  The "*_ks_pbs" sets carry
+    pbs_order = 1 (keyswitch then bootstrap, ciphertexts under the GLWE key): ClientKey and ServerKey follow the field."""
     p = Params()
     a, b = C.c_double(), C.c_double()
     client_check(host.helm_client_named_params(name.encode(), C.byref(p), C.byref(a), C.byref(b)))
@@ -72,11 +73,18 @@ class ClientKey:
     def glwe_secret(self):
         return self._view(host.helm_client_glwe_secret, self.params.k * self.params.N)
 
+    def ct_words(self):
+        """Words of one ciphertext: n + 1, or k N + 1 for a key generated with pbs_order = 1 (helm_client_ct_words)."""
+        v = int(host.helm_client_ct_words(self._h))
+        if v <= 0:
+            client_check(v or -1)
+        return v
+
     def encrypt(self, bits):
-        """bool or sequence of bools -> [count, n+1] uint32 (ClientKey::encrypt)."""
+        """bool or sequence of bools -> [count, ct_words()] uint32 (ClientKey::encrypt)."""
         scalar = np.isscalar(bits) or isinstance(bits, (bool, np.bool_))
         b = np.ascontiguousarray(np.atleast_1d(np.asarray(bits)).astype(np.uint8))
-        out = np.zeros((len(b), self.params.n + 1), dtype=np.uint32)
+        out = np.zeros((len(b), self.ct_words()), dtype=np.uint32)
         client_check(host.helm_client_encrypt_bool(self._h, nv.as_u8p(b), len(b), nv.as_u32p(out)))
         return out[0] if scalar else out
 
@@ -84,7 +92,7 @@ class ClientKey:
         """[count, n+1] (or one row) -> bool array (ClientKey::decrypt)."""
         a = np.ascontiguousarray(lwe, dtype=np.uint32)
         one = a.ndim == 1
-        a2 = a.reshape(-1, self.params.n + 1)
+        a2 = a.reshape(-1, self.ct_words())
         out = np.zeros(len(a2), dtype=np.uint8)
         client_check(host.helm_client_decrypt_bool(self._h, nv.as_u32p(a2), len(a2), nv.as_u8p(out)))
         return bool(out[0]) if one else out.astype(bool)
@@ -99,6 +107,7 @@ class ClientKey:
 
 HIP_CREATE_ALLOW_CRT = 1  # include/helm_hip.h HELM_HIP_CREATE_*
 HIP_CREATE_FORCE_CRT = 2
+HIP_CREATE_KS_PBS = 16
 _CRT_FLAGS = {"allow": HIP_CREATE_ALLOW_CRT, "force": HIP_CREATE_FORCE_CRT}
 
 
@@ -113,12 +122,14 @@ class ServerKey:
     def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, crt=None):
         self.params = client_key.params if client_key is not None else params
         h = nv.vp()
-        if crt is None:
+        if crt is not None and crt not in _CRT_FLAGS:
+            raise ValueError('crt must be None, "allow" or "force"')
+        # HELM_HIP_CREATE_KS_PBS exactly when the parameters say keyswitch-first
+        flags = (_CRT_FLAGS[crt] if crt is not None else 0) | (HIP_CREATE_KS_PBS if self.params.pbs_order == 1 else 0)
+        if flags == 0:
             hip_check(hip.helm_hip_ctx_create(device, C.byref(self.params), C.byref(h)))
         else:
-            if crt not in _CRT_FLAGS:
-                raise ValueError('crt must be None, "allow" or "force"')
-            hip_check(hip.helm_hip_ctx_create_ex(device, C.byref(self.params), _CRT_FLAGS[crt], C.byref(h)))
+            hip_check(hip.helm_hip_ctx_create_ex(device, C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self.device = device
         if client_key is not None:
@@ -152,6 +163,13 @@ class ServerKey:
         if q <= 0:
             hip_check(q or -1)
         return q
+
+    def wire_words(self):
+        """Words of one wire row: n + 1, or k N + 1 when the parameters say pbs_order = 1 (helm_hip_wire_words)."""
+        v = int(hip.helm_hip_wire_words(self._h))
+        if v <= 0:
+            hip_check(v or -1)
+        return v
 
     def kernel_class(self):
         """"tuned" when the parameter shape (N, k, pbs_l) has tuned blind-rotate builds, "generic" when the generic kernel
@@ -246,7 +264,7 @@ class ServerKey:
 
 
 class DeviceWires:
-    """HBM-resident wire table: n_wires rows of n+1 words."""
+    """HBM-resident wire table: n_wires rows of ServerKey.wire_words() words."""
 
     def __init__(self, server_key, n_wires):
         self.sk = server_key
@@ -267,14 +285,14 @@ class DeviceWires:
 
     def upload(self, idx, lwe):
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        lwe = np.ascontiguousarray(lwe, dtype=np.uint32).reshape(len(idx), self.sk.params.n + 1)
+        lwe = np.ascontiguousarray(lwe, dtype=np.uint32).reshape(len(idx), self.sk.wire_words())
         hip_check(hip.helm_hip_wires_upload(self.sk._h, self._h, nv.as_i32p(idx), nv.as_u32p(lwe), len(idx)))
 
     def download(self, idx=None):
         if idx is None:
             idx = np.arange(self.n_wires)
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        out = np.zeros((len(idx), self.sk.params.n + 1), dtype=np.uint32)
+        out = np.zeros((len(idx), self.sk.wire_words()), dtype=np.uint32)
         hip_check(hip.helm_hip_wires_download(self.sk._h, self._h, nv.as_i32p(idx), nv.as_u32p(out), len(idx)))
         return out
 

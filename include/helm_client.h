@@ -39,7 +39,9 @@ int helm_client_rng_selftest(void);
 
 /* Named parameter sets.  "boolean_default": tfhe 0.4.1 boolean::DEFAULT_PARAMETERS
  * (what gen_keys() uses, helm.rs:241) as recalled in SURVEY.md App. B;
- * "helm_cuda": the set hard-coded at helm.rs:141-146.  Returns 0 or HELM_ERR_INVALID. */
+ * "helm_cuda": the set hard-coded at helm.rs:141-146.  "boolean_default_ks_pbs": tfhe 0.4.1 DEFAULT_PARAMETERS_KS_PBS
+ * [recalled, low-to-medium confidence] and "toy_ks_pbs", "toy_k2_ks_pbs", "toy_1024_ks_pbs": pbs_order = 1.
+ * Returns 0 or HELM_ERR_INVALID. */
 int helm_client_named_params(const char *name, helm_hip_params *params, double *lwe_noise_std,
                              double *glwe_noise_std);
 
@@ -62,7 +64,12 @@ const uint32_t *helm_client_ksk(const helm_client_key *key); /* [k*N][ks_l][n+1]
 const uint32_t *helm_client_lwe_secret(const helm_client_key *key);  /* n   */
 const uint32_t *helm_client_glwe_secret(const helm_client_key *key); /* k*N */
 
-/* ClientKey::encrypt(bool): rows of n+1 words under the small key. */
+/* Words of one boolean ciphertext of this key: n + 1 with pbs_order = 0, k*N + 1 with pbs_order = 1 (helm_hip_wire_words
+ * of a context created with the same parameters).  Negative on error. */
+int64_t helm_client_ct_words(const helm_client_key *key);
+/* ClientKey::encrypt(bool): rows of n+1 words under the small key.  A key generated with pbs_order = 1 (tfhe's
+ * EncryptionKeyChoice::Big, the *_KS_PBS boolean sets) encrypts under the GLWE key read as an LWE key of k*N bits, with
+ * glwe_noise_std: rows of helm_client_ct_words() words; decrypt_bool reads the same rows. */
 int helm_client_encrypt_bool(helm_client_key *key, const uint8_t *bits, int64_t count, uint32_t *lwe_out);
 /* ClientKey::decrypt: phase < 2^31 => true (reference src/circuit.rs:948). */
 int helm_client_decrypt_bool(const helm_client_key *key, const uint32_t *lwe, int64_t count, uint8_t *bits_out);

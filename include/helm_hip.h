@@ -30,6 +30,8 @@
  * Data layouts (torus_bits = 32: all words are uint32_t, arithmetic mod 2^32)
  *   LWE ciphertext      n mask words then 1 body word            (n+1 words)
  *   wire table          n_wires rows of n+1 words                (row-major)
+ *                       (pbs_order = 1: rows of k*N+1 words, big LWEs under the
+ *                       GLWE key - helm_hip_wire_words())
  *   bootstrapping key   standard (coefficient) domain, as tfhe's
  *                       LweBootstrapKey: [n][pbs_l][k+1][k+1][N]
  *                       entry [i][j][r][c][*] = polynomial c of the GLWE row that
@@ -78,7 +80,12 @@ typedef struct {
     int32_t ks_l;            /* keyswitch decomposition level count          */
     int32_t ks_logB;         /* keyswitch decomposition base log             */
     int32_t pbs_order;       /* 0 = bootstrap then keyswitch (wires under the
-                                small key; tfhe boolean default)             */
+                                small key; tfhe boolean default); 1 =
+                                keyswitch then bootstrap (wires under the GLWE
+                                key read as an LWE key of k*N bits: tfhe's
+                                *_KS_PBS boolean sets) - admitted by
+                                helm_hip_ctx_create_ex with
+                                HELM_HIP_CREATE_KS_PBS only                  */
     int32_t grouping_factor; /* 1 (multi-bit PBS reserved)                   */
 } helm_hip_params;
 
@@ -114,7 +121,8 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
 /* Flags of helm_hip_ctx_create_ex. */
 enum {
     HELM_HIP_CREATE_ALLOW_CRT = 1, /* admit shapes beyond the single-prime capacity bound: they run on the two-prime kernel */
-    HELM_HIP_CREATE_FORCE_CRT = 2  /* run every launch on the two-prime kernel (tests and measurement) */
+    HELM_HIP_CREATE_FORCE_CRT = 2, /* run every launch on the two-prime kernel (tests and measurement) */
+    HELM_HIP_CREATE_KS_PBS = 16    /* admit pbs_order = 1 (keyswitch then bootstrap); combines with either CRT flag */
 };
 /* helm_hip_ctx_create with flags; flags = 0 is helm_hip_ctx_create itself - the same checks in the same order, the same
  * messages.  Every single-prime kernel admits a shape only while its exact products stay below half its prime,
@@ -133,7 +141,16 @@ enum {
  * shape outside the domain is HELM_ERR_INVALID.
  * Any other bit, or both bits together, is HELM_ERR_INVALID.  A context whose launches run k_pbs_crt accepts
  * HELM_HIP_PBS_VARIANT unset or 0 only (every other value names a single-prime build), and the bound-checking build
- * (libhelm_hip_check.so) refuses it at creation with HELM_ERR_STATE. */
+ * (libhelm_hip_check.so) refuses it at creation with HELM_ERR_STATE.
+ * HELM_HIP_CREATE_KS_PBS: pbs_order = 1 is admitted (without the bit it is refused as before, and a pbs_order outside
+ * {0, 1} always is); every other check runs unchanged and in the same order, and with pbs_order = 0 the bit creates exactly
+ * the context it creates without it.  The order is orthogonal to the kernel class: the bit combines with either CRT flag
+ * (17 and 18 are valid, 19 is not), and helm_hip_kernel_class, helm_hip_field_bits and helm_hip_launch_quantum report what
+ * they report for the same shape in order 0.  In order 1 a wire row is a big LWE of k*N + 1 words under the GLWE key
+ * (helm_hip_wire_words), and a bootstrapped gate is gate linear combination -> keyswitch -> bootstrap with the sample
+ * extract as its row; a MUX is two of those whose rows are added, + 1/8 on the body.  NOT, BUF, DFF and the constants are
+ * the linear forms at dimension k*N.  The bootstrap kernels are the ones of order 0 (they take the keyswitched rows as raw
+ * LWEs); the bits 4 and 8 stay unknown. */
 int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_t flags, helm_hip_ctx **out);
 int helm_hip_ctx_destroy(helm_hip_ctx *ctx);
 /* The parameter set the context was created with. */
@@ -150,6 +167,11 @@ int helm_hip_sync(helm_hip_ctx *ctx);
  * workgroups per compute unit (one bootstrap each, from the HIP occupancy calculator at the context's LDS size) x compute
  * units.  Negative on error. */
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx);
+/* Words of one row of a wire table of this context - the one place the row width comes from: n + 1 with pbs_order = 0,
+ * k*N + 1 with pbs_order = 1.  Every wire-table call (upload, download, copy, set_trivial, device_ptr), the staging and
+ * gather buffers of the sharded passes and the exchange callback's rows use it.  helm_hip_pbs_batch,
+ * helm_hip_keyswitch_batch and the key loaders keep their widths in both orders.  Negative on error. */
+int64_t helm_hip_wire_words(const helm_hip_ctx *ctx);
 
 /* Which blind-rotate kernel class the context's shape (N, k, pbs_l) runs on: 0 = the tuned builds (k_pbs, k_pbs_wide,
  * k_pbs_duo, k_pbs_trio, k_pbs_tri10: (512,2,3) (512,1,3) (512,1,2) (1024,1,3) (1024,1,2)), 1 = the generic kernel

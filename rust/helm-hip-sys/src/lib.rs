@@ -15,7 +15,7 @@ pub struct helm_hip_params {
     pub pbs_logB: i32,
     pub ks_l: i32,
     pub ks_logB: i32,
-    pub pbs_order: i32,       // 0 = bootstrap then keyswitch (tfhe boolean)
+    pub pbs_order: i32,       // 0 = bootstrap then keyswitch (tfhe boolean); 1 = keyswitch then bootstrap (the *_KS_PBS sets)
     pub grouping_factor: i32, // 1
 }
 
@@ -64,6 +64,7 @@ pub const HELM_GATE_CONST_ZERO: i32 = 12;
 // capacity bound - few, wide decomposition levels - passes ALLOW_CRT)
 pub const HELM_HIP_CREATE_ALLOW_CRT: u32 = 1;
 pub const HELM_HIP_CREATE_FORCE_CRT: u32 = 2; // every launch on the two-prime kernel (tests and measurement)
+pub const HELM_HIP_CREATE_KS_PBS: u32 = 16; // admit pbs_order = 1 (EncryptionKeyChoice::Big); combines with either CRT flag
 // include/helm_shortint.h: flags of helm_si_ctx_create_ex (an importer that meets an untuned key shape passes ALLOW_GENERIC)
 pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
 pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
@@ -113,6 +114,7 @@ extern "C" {
     pub fn helm_hip_set_stream(ctx: *mut helm_hip_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn helm_hip_sync(ctx: *mut helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_quantum(ctx: *const helm_hip_ctx) -> i64;
+    pub fn helm_hip_wire_words(ctx: *const helm_hip_ctx) -> i64;
     pub fn helm_hip_kernel_class(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_digit_batch(ctx: *const helm_hip_ctx) -> c_int;
     pub fn helm_hip_launch_costs(ctx: *const helm_hip_ctx, cost: *mut f64) -> c_int;

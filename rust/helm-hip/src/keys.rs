@@ -34,7 +34,9 @@ pub fn engine_params(p: &BooleanParameters) -> sys::helm_hip_params {
         pbs_logB: p.pbs_base_log.0 as i32,
         ks_l: p.ks_level.0 as i32,
         ks_logB: p.ks_base_log.0 as i32,
-        pbs_order: 0,
+        // [RECALLED] `encryption_key_choice` of the 0.4 parameter struct: Big = ciphertexts under the GLWE key, keyswitch
+        // first (the *_KS_PBS sets); Small = the boolean default
+        pbs_order: match p.encryption_key_choice { EncryptionKeyChoice::Big => 1, EncryptionKeyChoice::Small => 0 },
         grouping_factor: 1,
     }
 }

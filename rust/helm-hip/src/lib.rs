@@ -107,15 +107,18 @@ impl<'a> HipGateCircuit<'a> {
                         crt: Option<u32>) -> Self {
         assert_one_hip_runtime();
         let mut ctx = std::ptr::null_mut();
-        match crt {
-            None => check(unsafe { sys::helm_hip_ctx_create(device_id, &std_keys.params, &mut ctx) }),
-            Some(flags) => check(unsafe { sys::helm_hip_ctx_create_ex(device_id, &std_keys.params, flags, &mut ctx) }),
+        // a key whose parameters carry EncryptionKeyChoice::Big (pbs_order = 1) asks for the keyswitch-first level
+        let ks_pbs = if std_keys.params.pbs_order == 1 { sys::HELM_HIP_CREATE_KS_PBS } else { 0 };
+        match (crt, ks_pbs) {
+            (None, 0) => check(unsafe { sys::helm_hip_ctx_create(device_id, &std_keys.params, &mut ctx) }),
+            (flags, _) => check(unsafe { sys::helm_hip_ctx_create_ex(device_id, &std_keys.params, flags.unwrap_or(0) | ks_pbs, &mut ctx) }),
         }
         check(unsafe { sys::helm_hip_load_bootstrap_key(ctx, std_keys.bsk.as_ptr(), std_keys.bsk.len()) });
         check(unsafe { sys::helm_hip_load_keyswitch_key(ctx, std_keys.ksk.as_ptr(), std_keys.ksk.len()) });
         HipGateCircuit {
             circuit, client_key, ctx, wires: std::ptr::null_mut(), prog: std::ptr::null_mut(),
-            row_of: HashMap::new(), n_launches: 0, lwe_words: std_keys.params.n as usize + 1,
+            // n + 1 words, or k N + 1 under a keyswitch-first key: the context says which
+            row_of: HashMap::new(), n_launches: 0, lwe_words: unsafe { sys::helm_hip_wire_words(ctx) } as usize,
             comm: std::ptr::null_mut(), world: 1, replicate_below: 256, overlap: false,
         }
     }
