@@ -78,6 +78,7 @@ HOST_API = {
     "helm_host_si_enc_map_blocks": (C.c_int, [vp]),
     "helm_host_si_enc_map_row_words": (C.c_int, [vp]),
     "helm_host_si_enc_map_insert": (C.c_int, [vp, cp, u64p]),
+    "helm_host_si_enc_map_insert_words": (C.c_int, [vp, cp, u64p, C.c_int64]),
     "helm_host_si_enc_map_get": (C.c_int, [vp, cp, u64p]),
     "helm_host_si_enc_map_contains_key": (C.c_int, [vp, cp]),
     "helm_host_si_enc_map_keys": (vp, [vp]),

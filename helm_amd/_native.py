@@ -225,6 +225,8 @@ SI_API = {
     "helm_si_ctx_create": (C.c_int, [C.c_int, C.POINTER(SiParams), C.POINTER(vp)]),
     "helm_si_ctx_create_ex": (C.c_int, [C.c_int, C.POINTER(SiParams), C.c_int, C.POINTER(vp)]),
     "helm_si_kernel_class": (C.c_int, [vp]),
+    "helm_si_pbs_order": (C.c_int, [vp]),
+    "helm_si_wire_words": (C.c_int64, [vp]),
     "helm_si_ctx_destroy": (C.c_int, [vp]),
     "helm_si_ctx_fork": (C.c_int, [vp, C.POINTER(vp)]),
     "helm_si_get_params": (C.c_int, [vp, C.POINTER(SiParams)]),
@@ -314,6 +316,8 @@ SI_CLIENT_API = {
     "helm_si_client_glwe_secret": (u64p, [vp]),
     "helm_si_client_encrypt": (C.c_int, [vp, u64p, C.c_int64, u64p]),
     "helm_si_client_decrypt": (C.c_int, [vp, u64p, C.c_int64, u64p]),
+    "helm_si_client_encrypt_small": (C.c_int, [vp, u64p, C.c_int64, u64p]),
+    "helm_si_client_decrypt_small": (C.c_int, [vp, u64p, C.c_int64, u64p]),
     "helm_si_client_phase": (C.c_int, [vp, u64p, C.c_int64, C.c_int, u64p]),
 }
 

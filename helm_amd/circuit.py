@@ -181,8 +181,8 @@ class SiEncWireMap:
             self._h = None
 
     def insert(self, wire, ct):
-        ct = np.ascontiguousarray(ct, dtype=np.uint64).reshape(self.blocks, self.row_words)
-        H.check(H.host.helm_host_si_enc_map_insert(self._h, wire.encode(), nv.as_u64p(ct)))
+        ct = np.ascontiguousarray(ct, dtype=np.uint64).reshape(-1)   # (the library refuses a buffer of another width)
+        H.check(H.host.helm_host_si_enc_map_insert_words(self._h, wire.encode(), nv.as_u64p(ct), ct.size))
 
     __setitem__ = insert
 

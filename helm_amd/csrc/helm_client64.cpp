@@ -48,6 +48,24 @@ int helm_si_client_named_params(const char *name, helm_si_params *p, double *lwe
         p->n = 742; p->N = 2048; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 5; p->ks_logB = 3;
         *lwe_std = 0.000007069849454709433;
         *glwe_std = 0.00000000000000029403601535432533;
+    } else if (s == "shortint_m2c2_pbs_ks") {
+        // shortint_m2c2's shape for the bootstrap-first order (HELM_SI_CREATE_PBS_KS; tfhe's PARAM_MESSAGE_2_CARRY_2_PBS_KS):
+        // k = 1, N = 2048, one PBS level of 23 bits [shape as shortint_m2c2; tfhe's own n, keyswitch decomposition and noise
+        // for this set are NOT in the tree and not recalled: an approximate set, chosen here.  The order is not a parameter -
+        // the set runs in either - but in order 0 a wire row carries the KEYSWITCH's noise, which every linear combination
+        // amplifies before the next modulus switch, so m2c2's LWE side does not carry over: with n = 742, KS 5 x 3 the
+        // formulas below give 2^-40.3 on a fresh output but 2^-13 on 2x + y and 2^-4.4 on 4x + 2y + z.  Taken: n = 840 with
+        // the LWE noise on tfhe's security line through its n = 684 (2.04e-5) and n = 742 (7.07e-6) sets -
+        // log2 sigma = -15.58 - 0.02643 (n - 684) = -19.70, sigma = 1.17e-6 - a keyswitch of 6 levels x 3 bits, and m2c2's
+        // GLWE noise.  By the formulas of tests/test_gpu_noise.py (variances, torus units): blind rotation 2^-30.9,
+        // keyswitch 2^-23.3 (the key's noise through the digits; the rounding term is 2^-29.6), modulus switch
+        // (1 + n/2) / (48 N^2) = 2^-18.9.  A wire row holds blind rotation + keyswitch; the next look-up adds the modulus
+        // switch; half a box is 1 / (4 t) = 2^-6.  Failure probability per look-up in order 0: 2^-84 on a fresh output
+        // (variance br + ks + ms, sigma 2^-9.4), 2^-72 on 2x + y (5 (br + ks) + ms), 2^-46.5 on 4x + 2y + z of three
+        // look-up outputs (21 (br + ks) + ms).  These are predictions of the formulas, not measured here]
+        p->n = 840; p->N = 2048; p->pbs_l = 1; p->pbs_logB = 23; p->ks_l = 6; p->ks_logB = 3;
+        *lwe_std = 0.000001172;
+        *glwe_std = 0.00000000000000029403601535432533;
     } else if (s == "shortint_m2c2_multibit3") {
         // PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_3_KS_PBS, the set of reference src/bin/helm.rs:83
         // [dimensions recalled; noise: the LWE value extrapolated along tfhe's
@@ -275,6 +293,25 @@ int helm_si_client_encrypt(helm_si_client_key *key, const uint64_t *values, int6
     return 0;
 }
 
+// Rows of n + 1 words under the LWE key with the LWE noise: the wire rows of a context in the bootstrap-first order
+// (HELM_SI_CREATE_PBS_KS; tfhe's EncryptionKeyChoice::Small).  The same encoding v * delta.
+int helm_si_client_encrypt_small(helm_si_client_key *key, const uint64_t *values, int64_t count, uint64_t *out)
+{
+    if (!key || !values || !out || count < 0) return fail64(HELM_ERR_INVALID, "bad argument");
+    const int n = key->P.n;
+    const uint64_t t = (uint64_t)key->P.message_modulus * key->P.carry_modulus;
+    for (int64_t g = 0; g < count; g++) {
+        uint64_t *ct = out + (size_t)g * (n + 1);
+        uint64_t b = key->enc_rng.noise64(key->lwe_std);
+        for (int i = 0; i < n; i++) {
+            ct[i] = key->enc_rng.next();
+            if (key->lwe_sk[i]) b += ct[i];
+        }
+        ct[n] = b + (values[g] % t) * key->delta;
+    }
+    return 0;
+}
+
 int helm_si_client_phase(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, int small, uint64_t *ph)
 {
     if (!key || !lwe || !ph || count < 0) return fail64(HELM_ERR_INVALID, "bad argument");
@@ -290,11 +327,11 @@ int helm_si_client_phase(const helm_si_client_key *key, const uint64_t *lwe, int
     return 0;
 }
 
-int helm_si_client_decrypt(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values)
+static int decrypt_rows(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, int small, uint64_t *values)
 {
     if (!key || !lwe || !values || count < 0) return fail64(HELM_ERR_INVALID, "bad argument");
     std::vector<uint64_t> ph((size_t)count);
-    if (int rc = helm_si_client_phase(key, lwe, count, 0, ph.data())) return rc;
+    if (int rc = helm_si_client_phase(key, lwe, count, small, ph.data())) return rc;
     const uint64_t t = (uint64_t)key->P.message_modulus * key->P.carry_modulus;
     for (int64_t g = 0; g < count; g++) {
         // round to the nearest multiple of delta; the padding bit wraps into mod 2t, then mod t
@@ -302,6 +339,16 @@ int helm_si_client_decrypt(const helm_si_client_key *key, const uint64_t *lwe, i
         values[g] = v % t;
     }
     return 0;
+}
+
+int helm_si_client_decrypt(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values)
+{
+    return decrypt_rows(key, lwe, count, 0, values);
+}
+
+int helm_si_client_decrypt_small(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values)
+{
+    return decrypt_rows(key, lwe, count, 1, values);
 }
 
 } // extern "C"

@@ -1576,6 +1576,11 @@ struct helm_si_ctx {
     SiKeyState *keys = nullptr;         // own_keys, or the primary's: the one place shared state is read from
     helm_si_params P{};
     int logN = 0;
+    // helm_si_pbs_order: 1 = keyswitch, then bootstrap (table rows under the big key), 0 = bootstrap, then keyswitch
+    // (HELM_SI_CREATE_PBS_KS: table rows under the small key).  The one place the width of a wire row comes from.
+    int order = 1;
+    size_t wire_dim() const { return order ? (size_t)P.k * P.N : (size_t)P.n; } // mask words of a wire row
+    size_t wire_row() const { return wire_dim() + 1; }
     hipStream_t own_stream = nullptr, stream = nullptr;
     bool high_priority = false; // own_stream was created at the device's highest priority (helm_si_set_priority)
     DevBuf<int8_t> d_ksdig;
@@ -1629,7 +1634,7 @@ struct helm_si_ctx {
     // where this rank's chunk of a sharded batch goes, and the exchange that follows it
     uint64_t *x_slot(int64_t rows) const
     {
-        return x_comm ? x_gather + (size_t)x_rank * (size_t)rows * ((size_t)P.k * P.N + 1) : x_stage;
+        return x_comm ? x_gather + (size_t)x_rank * (size_t)rows * wire_row() : x_stage;
     }
 };
 
@@ -1919,8 +1924,18 @@ struct KsKey {
     int in_dim = 0, out_dim = 0, l = 0, logB = 0, kchunks = 0, ctiles = 0;
 };
 
+// Where the output rows of a keyswitch launch lie, for the sliced vector-ALU form, whose partial sums meet in rows zeroed
+// beforehand.  Without one the jobs write rows 0 .. count-1 of `out` (every order-1 launch).  The order-0 launches write
+// elsewhere: `rows` (with `none`, as many -1 entries: k_rows64 writes a zero row for a negative source) names the rows of a
+// wire table one by one - the other rows of the table are not touched - and without `rows` the first `dense` rows are zeroed
+// (a rank's exchange slot, where skipped many-LUT outputs leave gaps).
+struct KsOutRows {
+    int64_t dense = 0;
+    const int32_t *rows = nullptr, *none = nullptr;
+};
+
 hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs, int64_t count, const uint64_t *big,
-                           uint64_t *out)
+                           uint64_t *out, const KsOutRows *where = nullptr)
 {
     // `out`: rows of out_dim+1 words (job g writes row jobs[g].out_row)
     struct { int n, ks_l, ks_logB; } P{K.out_dim, K.l, K.logB};
@@ -1956,8 +1971,11 @@ hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs
     const int t_chunk = (kN + slices - 1) / slices;
     dim3 grid(gx, gy, (unsigned)slices);
     const size_t lds = (size_t)t_chunk * P.ks_l * sizeof(uint32_t);
-    if (slices > 1) {
-        hipError_t e = hipMemsetAsync(out, 0, (size_t)count * ((size_t)P.n + 1) * sizeof(uint64_t), ctx->stream);
+    if (slices > 1 && where && where->rows) {
+        hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, out, where->none, out, where->rows, P.n);
+        if (hipError_t e = hipGetLastError()) return e;
+    } else if (slices > 1) {
+        hipError_t e = hipMemsetAsync(out, 0, (size_t)(where ? where->dense : count) * ((size_t)P.n + 1) * sizeof(uint64_t), ctx->stream);
         if (e != hipSuccess) return e;
     }
 #define KS_CASE(LV)                                                                                                 \
@@ -1981,7 +1999,8 @@ hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs
     return hipGetLastError();
 }
 
-hipError_t launch_ks64(helm_si_ctx *ctx, const Ks64Job *jobs, int64_t count, const uint64_t *big, uint64_t *out)
+hipError_t launch_ks64(helm_si_ctx *ctx, const Ks64Job *jobs, int64_t count, const uint64_t *big, uint64_t *out,
+                       const KsOutRows *where = nullptr)
 {
     KsKey K;
     K.key = ctx->keys->ksk;
@@ -1992,7 +2011,7 @@ hipError_t launch_ks64(helm_si_ctx *ctx, const Ks64Job *jobs, int64_t count, con
     K.logB = ctx->P.ks_logB;
     K.kchunks = ctx->keys->ks_kchunks;
     K.ctiles = ctx->keys->ks_ctiles;
-    return launch_ks64_key(ctx, K, jobs, count, big, out);
+    return launch_ks64_key(ctx, K, jobs, count, big, out, where);
 }
 
 int check_rows(const helm_si_wires *w, const int32_t *idx, int64_t count, bool allow_neg)
@@ -2119,6 +2138,58 @@ int apply_luts_device(helm_si_ctx *ctx, const uint64_t *src, uint64_t *dst, cons
     return 0;
 }
 
+// Order 0 (HELM_SI_CREATE_PBS_KS): one bootstrap launch, then one keyswitch.  The bootstraps read their n+1-word input rows
+// in place - `src` is a wire table and Pbs64Job.in_row one of its rows - and write big rows into the stage buffer
+// (`stage_rows` of them); the keyswitch takes stage rows (Ks64Job.in_row) to rows of `dst`: a wire table (dense < 0), or a
+// rank's exchange slot of `dense` rows.  Every input row is read before any row of `dst` is written (kernel boundary), so an
+// output row may be an input row of the same call.  Many-LUT callers leave the skipped outputs off `ks`.
+int apply_luts_pbs_first(helm_si_ctx *ctx, const uint64_t *src, uint64_t *dst, const std::vector<Pbs64Job> &pbs,
+                         int64_t stage_rows, const std::vector<Ks64Job> &ks, int64_t dense, const uint64_t *luts_host,
+                         int64_t n_luts)
+{
+    const helm_si_params &P = ctx->P;
+    if (!ctx->keys->have_bsk || !ctx->keys->have_ksk) return fail(HELM_ERR_STATE, "bootstrapping / keyswitching key not loaded");
+    const int64_t count = (int64_t)pbs.size();
+    if (count == 0) return 0;
+    const size_t brow = (size_t)P.k * P.N + 1; // (a bootstrap's output row, not a wire row)
+    if (ctx->d_stage.cap < (size_t)stage_rows * brow) {
+        if (int rc = drain(ctx)) return rc; // growing the staging area frees the old one
+        if (ctx->d_stage.ensure((size_t)stage_rows * brow)) return fail(HELM_ERR_OOM, "staging");
+    }
+    if (int rc = luts_resident(ctx, luts_host, (size_t)n_luts * P.N)) return rc;
+    std::vector<int32_t> rows, none;
+    if (dense < 0) {
+        rows.resize(ks.size());
+        none.assign(ks.size(), -1);
+        for (size_t i = 0; i < ks.size(); i++) rows[i] = ks[i].out_row;
+    }
+    helm_si_ctx::CallSlot *S = nullptr;
+    if (int rc = slot_begin(ctx, ks.size() * (sizeof(Ks64Job) + 2 * sizeof(int32_t)) + pbs.size() * sizeof(Pbs64Job) + 1024, &S))
+        return rc;
+    const Ks64Job *d_ks = slot_put(*S, ks.data(), ks.size());
+    const Pbs64Job *d_pbs = slot_put(*S, pbs.data(), pbs.size());
+    KsOutRows where;
+    where.dense = dense;
+    if (dense < 0) {
+        where.rows = slot_put(*S, rows.data(), rows.size());
+        where.none = slot_put(*S, none.data(), none.size());
+    }
+    if (int rc = slot_flush(ctx, *S)) return rc;
+    {
+        Timed t(ctx, &ctx->ev_pbs);
+        HIP_TRY(launch_pbs64(ctx, d_pbs, count, src, ctx->d_luts.p, ctx->d_stage.p));
+    }
+    ctx->tacc.pbs_launches++;
+    ctx->tacc.pbs_count += count;
+    if (!ks.empty()) {
+        Timed t(ctx, &ctx->ev_ks);
+        HIP_TRY(launch_ks64(ctx, d_ks, (int64_t)ks.size(), ctx->d_stage.p, dst, &where));
+        ctx->tacc.ks_launches++;
+        ctx->tacc.ks_count += (int64_t)ks.size();
+    }
+    return slot_end(ctx, *S);
+}
+
 // Many-LUT: n functions share one blind rotation in M = the power of two >= n chunks of N/M coefficients (M <= t = message x
 // carry, so that a chunk holds whole boxes).  -> M and the `pad` of the bootstrap jobs (Pbs64Job).
 int many_lut_shape(const helm_si_ctx *ctx, int64_t n, int *M_out, int32_t *pad_out)
@@ -2137,7 +2208,7 @@ int many_lut_shape(const helm_si_ctx *ctx, int64_t n, int *M_out, int32_t *pad_o
 int apply_many_luts_stage(helm_si_ctx *ctx, const uint64_t *src, const int32_t *in_idx, const int32_t *lut_idx, int32_t n_out,
                           int32_t pad, int64_t count, const uint64_t *luts, int64_t n_luts)
 {
-    const size_t brow = (size_t)ctx->P.k * ctx->P.N + 1;
+    const size_t brow = (size_t)ctx->P.k * ctx->P.N + 1; // (a bootstrap's output row; order 1: also the wire row)
     std::vector<Ks64Job> ks((size_t)count);
     std::vector<Pbs64Job> pbs((size_t)count);
     for (int64_t g = 0; g < count; g++) {
@@ -2221,12 +2292,12 @@ int probe_spectrum_positions(helm_si_ctx *ctx)
     return 0;
 }
 
-// all-gather of `rows` big-LWE rows per rank into x_gather, on the context's stream
+// all-gather of `rows` wire rows per rank into x_gather, on the context's stream
 int si_exchange(helm_si_ctx *ctx, int64_t rows)
 {
     if (ctx->x_comm)
         return helm_comm_all_gather(ctx->x_comm, ctx->x_slot(rows), ctx->x_gather,
-                                    (size_t)rows * ((size_t)ctx->P.k * ctx->P.N + 1) * sizeof(uint64_t), ctx->stream);
+                                    (size_t)rows * ctx->wire_row() * sizeof(uint64_t), ctx->stream);
     if (int rc = ctx->x_fn(ctx->x_user, rows))
         return fail(HELM_ERR_STATE, "exchange callback failed with " + std::to_string(rc));
     return 0;
@@ -2237,7 +2308,7 @@ int si_exchange(helm_si_ctx *ctx, int64_t rows)
 int apply_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, const int32_t *lut_idx,
                        const int32_t *out_idx, int64_t count, const uint64_t *luts, int64_t n_luts)
 {
-    const int dim = ctx->P.k * ctx->P.N;
+    const int dim = (int)ctx->wire_dim();
     const int64_t world = ctx->x_world;
     for (int64_t base = 0; base < count;) {
         const int64_t per = std::min(count - base, ctx->x_cap * world);
@@ -2246,10 +2317,14 @@ int apply_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx
         std::vector<Ks64Job> ks((size_t)(hi - lo));
         std::vector<Pbs64Job> pbs((size_t)(hi - lo));
         for (int64_t g = lo; g < hi; g++) {
-            ks[(size_t)(g - lo)] = Ks64Job{in_idx[g], (int32_t)(g - lo)};
-            pbs[(size_t)(g - lo)] = Pbs64Job{(int32_t)(g - lo), lut_idx[g], (int32_t)(g - lo), 0};
+            // order 1: table row -> small row g - lo -> slot row g - lo; order 0: table row -> stage row g - lo -> slot row g - lo
+            ks[(size_t)(g - lo)] = Ks64Job{ctx->order ? in_idx[g] : (int32_t)(g - lo), (int32_t)(g - lo)};
+            pbs[(size_t)(g - lo)] = Pbs64Job{ctx->order ? (int32_t)(g - lo) : in_idx[g], lut_idx[g], (int32_t)(g - lo), 0};
         }
-        if (int rc = apply_luts_device(ctx, w->d, ctx->x_slot(rows), ks, pbs, luts, n_luts)) return rc;
+        if (ctx->order == 0) {
+            if (int rc = apply_luts_pbs_first(ctx, w->d, ctx->x_slot(rows), pbs, hi - lo, ks, rows, luts, n_luts)) return rc;
+        } else if (int rc = apply_luts_device(ctx, w->d, ctx->x_slot(rows), ks, pbs, luts, n_luts))
+            return rc;
         // the collective (the library's ncclAllGather, or the caller's callback) on this context's stream: every
         // rank calls it, also one whose chunk is empty
         if (int rc = si_exchange(ctx, rows)) return rc;
@@ -2277,7 +2352,7 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
                             int64_t n_luts)
 {
     const helm_si_params &P = ctx->P;
-    const int dim = P.k * P.N;
+    const int dim = (int)ctx->wire_dim();
     const int64_t world = ctx->x_world, cts = ctx->x_cap / n_out;
     if (cts < 1)
         return fail(HELM_ERR_INVALID, "many-LUT: n_out = " + std::to_string(n_out) + " exceeds the exchange's capacity_rows = " +
@@ -2287,6 +2362,7 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
         int64_t rows;         // ciphertexts per rank
         size_t first, mine;   // this rank's jobs: ks / pbs entries first .. first + mine
         size_t s_first, s_n;  // scatter list entries
+        size_t k_first, k_n;  // order 0: this rank's keyswitch jobs of the round (one per output that is not skipped)
     };
     std::vector<Round> rounds;
     std::vector<Ks64Job> ks;
@@ -2296,12 +2372,20 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
         const int64_t per = std::min(count - base, cts * world);
         const int64_t rows = (per + world - 1) / world;
         const int64_t lo = std::min(base + per, base + ctx->x_rank * rows), hi = std::min(base + per, lo + rows);
-        Round R{rows, ks.size(), (size_t)(hi - lo), s_row.size(), 0};
+        Round R{rows, pbs.size(), (size_t)(hi - lo), s_row.size(), 0, ks.size(), 0};
         for (int64_t g = lo; g < hi; g++) {
-            const int32_t q = (int32_t)ks.size();
-            ks.push_back(Ks64Job{in_idx[g], q});
-            pbs.push_back(Pbs64Job{q, lut_idx[g], (int32_t)((g - lo) * n_out), pad});
+            const int32_t q = (int32_t)pbs.size();
+            if (ctx->order) {
+                ks.push_back(Ks64Job{in_idx[g], q});
+                pbs.push_back(Pbs64Job{q, lut_idx[g], (int32_t)((g - lo) * n_out), pad});
+                continue;
+            }
+            // order 0: table row -> stage rows q n_out + x (every round's, before the first scatter) -> slot rows (g - lo) n_out + x
+            pbs.push_back(Pbs64Job{in_idx[g], lut_idx[g], q * n_out, pad});
+            for (int32_t x = 0; x < n_out; x++)
+                if (out_idx[g * n_out + x] >= 0) ks.push_back(Ks64Job{q * n_out + x, (int32_t)((g - lo) * n_out + x)});
         }
+        R.k_n = ks.size() - R.k_first;
         for (int64_t q = 0; q < per * n_out; q++) // the chunks are contiguous: gathered row q is output q % n_out of base + q / n_out
             if (out_idx[base * n_out + q] >= 0) {
                 s_row.push_back((int32_t)q);
@@ -2311,21 +2395,32 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
         rounds.push_back(R);
         base += per;
     }
-    const size_t mine = ks.size();
-    if (ctx->d_small.cap < mine * ((size_t)P.n + 1)) {
+    const size_t mine = pbs.size();
+    if (ctx->order == 0) {
+        const size_t need = mine * n_out * ((size_t)P.k * P.N + 1); // (bootstrap output rows)
+        if (ctx->d_stage.cap < need) {
+            if (int rc = drain(ctx)) return rc; // growing the staging area frees the old one
+            if (ctx->d_stage.ensure(need)) return fail(HELM_ERR_OOM, "staging");
+        }
+    } else if (ctx->d_small.cap < mine * ((size_t)P.n + 1)) {
         if (int rc = drain(ctx)) return rc; // growing the scratch frees the old one
         if (ctx->d_small.ensure(mine * ((size_t)P.n + 1))) return fail(HELM_ERR_OOM, "small-LWE scratch");
     }
     if (int rc = luts_resident(ctx, luts, (size_t)n_luts * P.N)) return rc;
     helm_si_ctx::CallSlot *S = nullptr;
-    if (int rc = slot_begin(ctx, mine * (sizeof(Ks64Job) + sizeof(Pbs64Job)) + 2 * s_row.size() * sizeof(int32_t) + 1024, &S))
+    if (int rc = slot_begin(ctx, ks.size() * sizeof(Ks64Job) + mine * sizeof(Pbs64Job) + 2 * s_row.size() * sizeof(int32_t) + 1024, &S))
         return rc;
     const Ks64Job *d_ks = slot_put(*S, ks.data(), ks.size());
     const Pbs64Job *d_pbs = slot_put(*S, pbs.data(), pbs.size());
     const int32_t *d_src = slot_put(*S, s_row.data(), s_row.size());
     const int32_t *d_dst = slot_put(*S, d_row.data(), d_row.size());
     if (int rc = slot_flush(ctx, *S)) return rc;
-    if (mine) {
+    if (mine && ctx->order == 0) { // this rank's share of every round, read from the table before the first scatter
+        Timed t(ctx, &ctx->ev_pbs);
+        HIP_TRY(launch_pbs64(ctx, d_pbs, (int64_t)mine, w->d, ctx->d_luts.p, ctx->d_stage.p));
+        ctx->tacc.pbs_launches++;
+        ctx->tacc.pbs_count += (int64_t)mine;
+    } else if (mine) {
         Timed t(ctx, &ctx->ev_ks);
         HIP_TRY(launch_ks64(ctx, d_ks, (int64_t)mine, w->d, ctx->d_small.p));
         ctx->tacc.ks_launches++;
@@ -2333,7 +2428,16 @@ int apply_many_luts_sharded(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
     }
     for (const Round &R : rounds) {
         const int64_t slot_rows = R.rows * n_out;
-        if (R.mine) {
+        if (ctx->order == 0) {
+            if (R.k_n) {
+                Timed t(ctx, &ctx->ev_ks);
+                KsOutRows where;
+                where.dense = slot_rows;
+                HIP_TRY(launch_ks64(ctx, d_ks + R.k_first, (int64_t)R.k_n, ctx->d_stage.p, ctx->x_slot(slot_rows), &where));
+                ctx->tacc.ks_launches++;
+                ctx->tacc.ks_count += (int64_t)R.k_n;
+            }
+        } else if (R.mine) {
             Timed t(ctx, &ctx->ev_pbs);
             HIP_TRY(launch_pbs64(ctx, d_pbs + R.first, (int64_t)R.mine, ctx->d_small.p, ctx->d_luts.p, ctx->x_slot(slot_rows)));
             ctx->tacc.pbs_launches++;
@@ -2547,14 +2651,17 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     const helm_si_params &P = *params;
     // HELM_SI_CREATE_LARGE_N matters at N >= 4096 only: below, the call is the same call without the bit
     const bool large = (flags & HELM_SI_CREATE_LARGE_N) != 0 && P.N >= 4096;
+    // HELM_SI_CREATE_PBS_KS changes no admission rule: the checks below see the flags without it
+    const bool pbs_ks = (flags & HELM_SI_CREATE_PBS_KS) != 0;
     if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT |
-                  HELM_SI_CREATE_LARGE_N))
+                  HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
                                           " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2, "
                                           "HELM_SI_CREATE_GENERIC_MULTIBIT = 16" +
                                           ((flags & HELM_SI_CREATE_LARGE_N) ? ", HELM_SI_CREATE_LARGE_N = 32" : "") +
+                                          (pbs_ks ? ", HELM_SI_CREATE_PBS_KS = 64" : "") +
                                           "; 4 and 8 are reserved)");
-    flags &= ~HELM_SI_CREATE_LARGE_N;
+    flags &= ~(HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS);
     const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
     const bool multibit = (flags & HELM_SI_CREATE_GENERIC_MULTIBIT) != 0;
     if (multibit && !(flags & (HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC)))
@@ -2618,6 +2725,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (!ctx) return fail(HELM_ERR_OOM, "ctx");
     ctx->device = device_id;
     ctx->P = P;
+    ctx->order = pbs_ks ? 0 : 1;
     ctx->n_cus = prop.multiProcessorCount;
     while ((1 << ctx->logN) < P.N) ctx->logN++;
     ctx->delta = (1ull << 63) / (uint64_t)t;
@@ -2690,6 +2798,7 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
     ctx->keys = primary->keys; // keys, tables and what a later load makes of them: the primary's, not a copy
     ctx->P = primary->P;
     ctx->logN = primary->logN;
+    ctx->order = primary->order;
     ctx->delta = primary->delta;
     ctx->n_cus = primary->n_cus;
     ctx->audit_fn = primary->audit_fn; // a lane is audited like its primary
@@ -2759,6 +2868,18 @@ int helm_si_field_bits(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
     return ctx->keys->pair == 2 ? 50 : ctx->keys->pair ? 46 : 49;
+}
+
+int helm_si_pbs_order(const helm_si_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return ctx->order;
+}
+
+int64_t helm_si_wire_words(const helm_si_ctx *ctx)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
+    return (int64_t)ctx->wire_row();
 }
 
 int helm_si_kernel_class(const helm_si_ctx *ctx)
@@ -2959,7 +3080,7 @@ int helm_si_wires_alloc(helm_si_ctx *ctx, int64_t n_rows, helm_si_wires **out)
     if (!w) return fail(HELM_ERR_OOM, "wires");
     w->owner = ctx;
     w->n_rows = n_rows;
-    const size_t bytes = (size_t)n_rows * ((size_t)ctx->P.k * ctx->P.N + 1) * sizeof(uint64_t);
+    const size_t bytes = (size_t)n_rows * ctx->wire_row() * sizeof(uint64_t);
     if (hipMalloc(&w->d, bytes) != hipSuccess) {
         delete w;
         return fail(HELM_ERR_OOM, "ciphertext table of " + std::to_string(bytes) + " bytes");
@@ -3000,7 +3121,7 @@ int helm_si_wires_upload(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *idx,
     }
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = drain(ctx)) return rc;
-    const int dim = ctx->P.k * ctx->P.N;
+    const int dim = (int)ctx->wire_dim();
     if (int rc = upload(ctx, ctx->d_stage, lwe_host, (size_t)count * (dim + 1))) return rc;
     if (int rc = upload(ctx, ctx->d_idx, idx, (size_t)count)) return rc;
     hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, ctx->d_stage.p, (const int32_t *)nullptr,
@@ -3018,7 +3139,7 @@ int helm_si_wires_download(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *id
     if (int rc = check_rows(w, idx, count, false)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = drain(ctx)) return rc;
-    const int dim = ctx->P.k * ctx->P.N;
+    const int dim = (int)ctx->wire_dim();
     if (ctx->d_stage.ensure((size_t)count * (dim + 1))) return fail(HELM_ERR_OOM, "staging");
     if (int rc = upload(ctx, ctx->d_idx, idx, (size_t)count)) return rc;
     hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, w->d, ctx->d_idx.p, ctx->d_stage.p,
@@ -3043,7 +3164,7 @@ int helm_si_wires_copy(helm_si_ctx *ctx, helm_si_wires *src, const int32_t *src_
     if (int rc = upload(ctx, ctx->d_idx, src_idx, (size_t)count)) return rc;
     if (int rc = upload(ctx, ctx->d_idx2, dst_idx, (size_t)count)) return rc;
     hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, src->d, ctx->d_idx.p, dst->d,
-                       ctx->d_idx2.p, ctx->P.k * ctx->P.N);
+                       ctx->d_idx2.p, (int)ctx->wire_dim());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3062,7 +3183,7 @@ int helm_si_wires_set_trivial(helm_si_ctx *ctx, helm_si_wires *w, const int32_t 
     if (int rc = upload(ctx, ctx->d_body, body.data(), body.size())) return rc;
     if (int rc = upload(ctx, ctx->d_idx, idx, (size_t)count)) return rc;
     hipLaunchKernelGGL(k_set_trivial64, dim3((unsigned)count), dim3(256), 0, ctx->stream, ctx->d_idx.p, ctx->d_body.p, w->d,
-                       ctx->P.k * ctx->P.N);
+                       (int)ctx->wire_dim());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -3099,7 +3220,7 @@ int helm_si_set_audit(helm_si_ctx *ctx, helm_si_audit_fn fn, void *user)
 // rows idx[0 .. count) of the table on the host (idx < 0: a zero row), for the audit
 static int audit_fetch(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *idx, int64_t count, std::vector<uint64_t> &rows)
 {
-    const size_t brow = (size_t)ctx->P.k * ctx->P.N + 1;
+    const size_t brow = ctx->wire_row();
     std::vector<int32_t> safe((size_t)count);
     for (int64_t g = 0; g < count; g++) safe[(size_t)g] = idx[g] < 0 ? 0 : idx[g];
     rows.assign((size_t)count * brow, 0);
@@ -3146,7 +3267,7 @@ static int lincomb_impl(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_id
     if (int rc = check_rows(w, in_idx, count * terms, true)) return rc;
     if (int rc = check_rows(w, out_idx, count, false)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int dim = ctx->P.k * ctx->P.N;
+    const int dim = (int)ctx->wire_dim();
     std::vector<uint64_t> body((size_t)count, 0);
     if (const_add)
         for (int64_t g = 0; g < count; g++) body[(size_t)g] = (uint64_t)const_add[g] * ctx->delta;
@@ -3211,7 +3332,13 @@ int helm_si_apply_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *in_idx
     int rc = 0;
     if (ctx->x_on && count >= ctx->x_min)
         rc = apply_luts_sharded(ctx, w, in_idx, lut_idx, out_idx, count, luts, n_luts);
-    else // every keyswitch finishes (kernel boundary) before any bootstrap writes its output row
+    else if (ctx->order == 0) { // every bootstrap finishes (kernel boundary) before any keyswitch writes its output row
+        for (int64_t g = 0; g < count; g++) {
+            pbs[(size_t)g] = Pbs64Job{in_idx[g], lut_idx[g], (int32_t)g, 0};
+            ks[(size_t)g] = Ks64Job{(int32_t)g, out_idx[g]};
+        }
+        rc = apply_luts_pbs_first(ctx, w->d, w->d, pbs, count, ks, -1, luts, n_luts);
+    } else // every keyswitch finishes (kernel boundary) before any bootstrap writes its output row
         rc = apply_luts_device(ctx, w->d, w->d, ks, pbs, luts, n_luts);
     if (rc || !ctx->audit_fn) return rc;
     if ((rc = audit_fetch(ctx, w, out_idx, count, audit_out))) return rc;
@@ -3279,6 +3406,14 @@ int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
         if (int rc = audit_fetch(ctx, w, in_idx, count, audit_in)) return rc;
     if (ctx->x_on && count >= ctx->x_min) {
         if (int rc = apply_many_luts_sharded(ctx, w, in_idx, lut_idx, out_idx, n_out, pad, count, luts, n_luts)) return rc;
+    } else if (ctx->order == 0) {
+        // One rotation per ciphertext into stage rows g n_out + x, then one keyswitch job per output that is not skipped,
+        // straight into its table row.
+        std::vector<Pbs64Job> pbs((size_t)count);
+        std::vector<Ks64Job> ks(s_row.size());
+        for (int64_t g = 0; g < count; g++) pbs[(size_t)g] = Pbs64Job{in_idx[g], lut_idx[g], (int32_t)(g * n_out), pad};
+        for (size_t i = 0; i < s_row.size(); i++) ks[i] = Ks64Job{s_row[i], d_row[i]};
+        if (int rc = apply_luts_pbs_first(ctx, w->d, w->d, pbs, n_rows, ks, -1, luts, n_luts)) return rc;
     } else {
         // Every keyswitch finishes (kernel boundary) before the scatter writes an output row: the bootstraps write the stage
         // buffer only.
@@ -3292,7 +3427,7 @@ int helm_si_apply_many_luts(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *i
             {
                 Timed t(ctx, &ctx->ev_lin);
                 hipLaunchKernelGGL(k_rows64, dim3((unsigned)d_row.size()), dim3(256), 0, ctx->stream, ctx->d_stage.p, d_src, w->d,
-                                   d_dst, ctx->P.k * ctx->P.N);
+                                   d_dst, (int)ctx->wire_dim());
                 HIP_TRY(hipGetLastError());
             }
             if (int rc = slot_end(ctx, *S)) return rc;
@@ -3367,7 +3502,7 @@ int helm_si_set_exchange_comm(helm_si_ctx *ctx, helm_comm *comm, int64_t min_bat
     if (dev != ctx->device) return fail(HELM_ERR_STATE, "helm_si_set_exchange_comm: the communicator lives on another device than the context");
     if (int rc = helm_si_set_exchange(ctx, 0, 1, 1, nullptr, nullptr, 1, nullptr, nullptr)) return rc; // releases an earlier buffer
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t brow = (size_t)ctx->P.k * ctx->P.N + 1;
+    const size_t brow = ctx->wire_row();
     HIP_TRY(hipMalloc(&ctx->x_own, (size_t)capacity_rows * (size_t)world * brow * sizeof(uint64_t)));
     ctx->x_comm = comm;
     ctx->x_gather = ctx->x_own;

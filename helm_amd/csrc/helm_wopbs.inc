@@ -595,6 +595,10 @@ int helm_wop_ctx_create(helm_si_ctx *pbs_side, const helm_wop_params *params, he
     if (pbs_side->keys->gen)
         return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context runs the generic bootstrap kernel (helm_si_kernel_class 1); "
                                       "the WoP path is built for the tuned kernels only");
+    if (pbs_side->order == 0)
+        return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context was created with HELM_SI_CREATE_PBS_KS (helm_si_pbs_order 0: "
+                                      "wire rows of n + 1 words); the WoP path's bit extraction, circuit bootstrap and result rows "
+                                      "assume big wire rows (helm_si_pbs_order 1)");
     if (pbs_side->P.k != 1 || P.k != 1)
         return fail(HELM_ERR_INVALID, "WoP-PBS: built for k = 1 on both sides (every tfhe WOPBS set and its PBS partner)");
     helm_si_params S{};

@@ -543,6 +543,10 @@ int helm_host_si_enc_map_insert(helm_si_enc_map *m, const char *wire, const uint
 {
     return guard([&] { m->m->insert(wire, lwe); });
 }
+int helm_host_si_enc_map_insert_words(helm_si_enc_map *m, const char *wire, const uint64_t *lwe, int64_t n_words)
+{
+    return guard([&] { m->m->insert(wire, lwe, n_words); });
+}
 int helm_host_si_enc_map_get(const helm_si_enc_map *m, const char *wire, uint64_t *lwe_out)
 {
     return guard([&] {

@@ -293,7 +293,8 @@ class GateCircuit : public EvalCircuit<EncWireMap> {
 
 // Device-resident replacement of HashMap<String, CtxtShortInt> / HashMap<String, FheType>
 // (circuit.rs:1046-1049, 1312-1315): wire name -> first of `blocks` consecutive rows of a
-// big-LWE table (1 row per shortint wire, 4..64 per FheUint8..128 wire).
+// wire table (1 row per shortint wire, 4..64 per FheUint8..128 wire).  The rows have the context's width
+// (helm_si_wire_words): big-LWE rows of k N + 1 words, or n + 1 words in the bootstrap-first order.
 class SiEncWireMap {
   public:
     SiEncWireMap(helm_si_ctx *ctx, int blocks);
@@ -308,6 +309,8 @@ class SiEncWireMap {
     int row(const std::string &k) const;                    // first row; throws Panic if absent
     std::vector<uint64_t> get(const std::string &k) const;  // download `blocks` ciphertexts
     void insert(const std::string &k, const uint64_t *lwe); // upload (adds the key if new)
+    // the same for a client buffer of n_words words: refused unless it holds `blocks` rows of the context's width
+    void insert(const std::string &k, const uint64_t *lwe, int64_t n_words);
     std::unique_ptr<SiEncWireMap> clone(int64_t scratch_rows) const;
     void reserve_keys(const std::vector<std::string> &names, int64_t scratch_rows);
     int scratch(int64_t rows); // first row of a scratch region behind the named rows

@@ -33,9 +33,22 @@ static void si_ok(int rc, const char *what)
 // ---------------------------------------------------------------------------------------
 SiEncWireMap::SiEncWireMap(helm_si_ctx *ctx, int blocks) : ctx_(ctx), blocks_(blocks)
 {
-    helm_si_params P;
-    si_ok(helm_si_get_params(ctx, &P), "get_params");
-    dim_ = P.k * P.N;
+    // the row width is the context's: k N + 1 words, or n + 1 in the bootstrap-first order (HELM_SI_CREATE_PBS_KS)
+    const int64_t words = helm_si_wire_words(ctx);
+    if (words <= 0) throw Panic(std::string("wire_words: ") + helm_hip_last_error());
+    dim_ = (int)words - 1;
+}
+
+// client-side rows of the context's width: under the big key, or under the small key in the bootstrap-first order
+static int si_encrypt_rows(helm_si_ctx *ctx, helm_si_client_key *key, const uint64_t *values, int64_t count, uint64_t *out)
+{
+    return helm_si_pbs_order(ctx) == 0 ? helm_si_client_encrypt_small(key, values, count, out)
+                                       : helm_si_client_encrypt(key, values, count, out);
+}
+static int si_decrypt_rows(helm_si_ctx *ctx, const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values)
+{
+    return helm_si_pbs_order(ctx) == 0 ? helm_si_client_decrypt_small(key, lwe, count, values)
+                                       : helm_si_client_decrypt(key, lwe, count, values);
 }
 
 SiEncWireMap::~SiEncWireMap()
@@ -127,6 +140,17 @@ void SiEncWireMap::insert(const std::string &k, const uint64_t *lwe)
     gen_++;
 }
 
+void SiEncWireMap::insert(const std::string &k, const uint64_t *lwe, int64_t n_words)
+{
+    if (n_words != (int64_t)blocks_ * row_words())
+        throw Panic("wire \"" + k + "\": the client buffer holds " + std::to_string(n_words) + " words (" +
+                    (blocks_ > 0 && n_words % blocks_ == 0 ? "rows of " + std::to_string(n_words / blocks_) + " words"
+                                                           : std::string("no whole rows")) +
+                    "), the server key's wires take " + std::to_string(blocks_) + " row(s) of " + std::to_string(row_words()) +
+                    " words (helm_si_wire_words: the ciphertext order of the client's rows and the context's differ)");
+    insert(k, lwe);
+}
+
 std::unique_ptr<SiEncWireMap> SiEncWireMap::clone(int64_t scratch_rows) const
 {
     auto m = std::make_unique<SiEncWireMap>(ctx_, blocks_);
@@ -194,9 +218,9 @@ std::unique_ptr<SiEncWireMap> LutCircuit::encrypt_inputs(const std::set<std::str
         }
     }
     if (!idx.empty()) {
-        const size_t row = (size_t)P_.k * P_.N + 1;
+        const size_t row = (size_t)helm_si_wire_words(server_key_);
         std::vector<uint64_t> cts(idx.size() * row);
-        if (helm_si_client_encrypt(client_key_, vals.data(), (int64_t)vals.size(), cts.data())) throw Panic(client_key_ ? "encrypt failed" : "evaluation-only circuit (no client key): encrypt with the caller's keys and insert the ciphertext words");
+        if (si_encrypt_rows(server_key_, client_key_, vals.data(), (int64_t)vals.size(), cts.data())) throw Panic(client_key_ ? "encrypt failed" : "evaluation-only circuit (no client key): encrypt with the caller's keys and insert the ciphertext words");
         si_ok(helm_si_wires_upload(server_key_, m->table(), idx.data(), cts.data(), (int64_t)idx.size()), "wires_upload");
     }
     return m;
@@ -253,6 +277,10 @@ void LutCircuit::evaluate_ready(const SiEncWireMap &enc_wire_map, SiEncWireMap &
 
 void LutCircuit::set_wide_lut_key(helm_wop_ctx *wop, int bits_per_block)
 {
+    if (wop && helm_si_pbs_order(server_key_) == 0) // (the engine's refusal: helm_wop_ctx_create on such a PBS side)
+        throw Panic("WoP-PBS: the PBS-side context was created with HELM_SI_CREATE_PBS_KS (helm_si_pbs_order 0: wire rows of "
+                    "n + 1 words); the WoP path's bit extraction, circuit bootstrap and result rows assume big wire rows "
+                    "(helm_si_pbs_order 1)");
     if (wop) {
         helm_wop_params W{};
         si_ok(helm_wop_get_params(wop, &W), "wop_get_params");
@@ -433,7 +461,7 @@ std::map<std::string, PtxtType> LutCircuit::decrypt_outputs(const SiEncWireMap &
     for (auto &w : circuit_.output_wires()) {
         auto ct = enc_wire_map.get(w);
         uint64_t v = 0;
-        if (helm_si_client_decrypt(client_key_, ct.data(), 1, &v)) throw Panic(client_key_ ? "decrypt failed" : "evaluation-only circuit (no client key): read the ciphertext words and decrypt with the caller's keys");
+        if (si_decrypt_rows(server_key_, client_key_, ct.data(), 1, &v)) throw Panic(client_key_ ? "decrypt failed" : "evaluation-only circuit (no client key): read the ciphertext words and decrypt with the caller's keys");
         PtxtType p;
         p.kind = PtxtType::U64;
         p.value = v % (uint64_t)P_.message_modulus; // ClientKey::decrypt: the message part
@@ -1500,8 +1528,8 @@ void ArithCircuit::encrypt_value(SiEncWireMap &m, const std::string &wire, unsig
     const int nb = m.blocks();
     std::vector<uint64_t> digits((size_t)nb);
     for (int i = 0; i < nb; i++) digits[(size_t)i] = (uint64_t)((value >> (2 * i)) & 3);
-    std::vector<uint64_t> cts((size_t)nb * ((size_t)P_.k * P_.N + 1));
-    if (helm_si_client_encrypt(client_key_, digits.data(), nb, cts.data())) throw Panic(client_key_ ? "encrypt failed" : "evaluation-only circuit (no client key): encrypt with the caller's keys and insert the ciphertext words");
+    std::vector<uint64_t> cts((size_t)nb * (size_t)helm_si_wire_words(server_key_));
+    if (si_encrypt_rows(server_key_, client_key_, digits.data(), nb, cts.data())) throw Panic(client_key_ ? "encrypt failed" : "evaluation-only circuit (no client key): encrypt with the caller's keys and insert the ciphertext words");
     m.insert(wire, cts.data());
 }
 
@@ -1927,7 +1955,7 @@ std::map<std::string, PtxtType> ArithCircuit::decrypt_outputs(const SiEncWireMap
     for (auto &w : circuit_.output_wires()) {
         auto ct = enc_wire_map.get(w);
         std::vector<uint64_t> vals((size_t)nb);
-        if (helm_si_client_decrypt(client_key_, ct.data(), nb, vals.data())) throw Panic(client_key_ ? "decrypt failed" : "evaluation-only circuit (no client key): read the ciphertext words and decrypt with the caller's keys");
+        if (si_decrypt_rows(server_key_, client_key_, ct.data(), nb, vals.data())) throw Panic(client_key_ ? "decrypt failed" : "evaluation-only circuit (no client key): read the ciphertext words and decrypt with the caller's keys");
         unsigned __int128 v = 0;
         for (int i = nb - 1; i >= 0; i--) v = (v << 2) + vals[(size_t)i]; // carries included, wrapping
         if (bits < 128) v &= (((unsigned __int128)1 << bits) - 1);

@@ -75,27 +75,30 @@ class SiClientKey:
     def glwe_secret(self):
         return self._view(host.helm_si_client_glwe_secret, self.dim)
 
-    def encrypt(self, values):
-        """int or sequence -> [count, k*N+1] uint64 (ClientKey::encrypt(u64))."""
+    def encrypt(self, values, small=False):
+        """int or sequence -> [count, k*N+1] uint64 (ClientKey::encrypt(u64)); small=True: [count, n+1] under the LWE key,
+        the wire rows of a server key of order "pbs_ks" (helm_si_client_encrypt_small)."""
         scalar = np.isscalar(values)
         v = np.ascontiguousarray(np.atleast_1d(np.asarray(values)).astype(np.uint64))
-        out = np.zeros((len(v), self.dim + 1), dtype=np.uint64)
-        rc = host.helm_si_client_encrypt(self._h, nv.as_u64p(v), len(v), nv.as_u64p(out))
+        out = np.zeros((len(v), (self.params.n if small else self.dim) + 1), dtype=np.uint64)
+        fn = host.helm_si_client_encrypt_small if small else host.helm_si_client_encrypt
+        rc = fn(self._h, nv.as_u64p(v), len(v), nv.as_u64p(out))
         assert rc == 0
         return out[0] if scalar else out
 
-    def decrypt_message_and_carry(self, lwe):
+    def decrypt_message_and_carry(self, lwe, small=False):
         a = np.ascontiguousarray(lwe, dtype=np.uint64)
         one = a.ndim == 1
-        a2 = a.reshape(-1, self.dim + 1)
+        a2 = a.reshape(-1, (self.params.n if small else self.dim) + 1)
         out = np.zeros(len(a2), dtype=np.uint64)
-        rc = host.helm_si_client_decrypt(self._h, nv.as_u64p(a2), len(a2), nv.as_u64p(out))
+        fn = host.helm_si_client_decrypt_small if small else host.helm_si_client_decrypt
+        rc = fn(self._h, nv.as_u64p(a2), len(a2), nv.as_u64p(out))
         assert rc == 0
         return int(out[0]) if one else out
 
-    def decrypt(self, lwe):
+    def decrypt(self, lwe, small=False):
         """ClientKey::decrypt: the message part (mod message_modulus)."""
-        v = self.decrypt_message_and_carry(lwe)
+        v = self.decrypt_message_and_carry(lwe, small)
         return v % self.params.message_modulus
 
     def phase(self, lwe, small=False):
@@ -111,6 +114,8 @@ SI_CREATE_ALLOW_GENERIC = 1  # include/helm_shortint.h HELM_SI_CREATE_*
 SI_CREATE_FORCE_GENERIC = 2
 SI_CREATE_GENERIC_MULTIBIT = 16
 SI_CREATE_LARGE_N = 32
+SI_CREATE_PBS_KS = 64
+_ORDER_FLAGS = {"ks_pbs": 0, "pbs_ks": SI_CREATE_PBS_KS}
 _GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC,
                   "allow+multibit": SI_CREATE_ALLOW_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
                   "force+multibit": SI_CREATE_FORCE_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
@@ -129,18 +134,28 @@ class SiServerKey:
     bootstrapping key must then pass the load-time capacity check (include/helm_shortint.h).  "large" (alone, or as
     "allow+large" / "force+large" beside the generic settings) adds HELM_SI_CREATE_LARGE_N: k = 1, N = 4096 - the 5-bit sets,
     message_modulus * carry_modulus = 32 - is admitted and runs on the large-N kernel; any smaller shape behaves as without
-    it.  Lanes inherit the setting."""
+    it.  Lanes inherit the setting.
 
-    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, generic=None):
+    order: "ks_pbs" (the default: the flags are passed as without it) keeps ciphertexts under the big key, a look-up is
+    keyswitch, then bootstrap; "pbs_ks" adds HELM_SI_CREATE_PBS_KS: wire rows are n + 1 words under the small key
+    (SiClientKey.encrypt(..., small=True)), a look-up is bootstrap, then keyswitch.  The keys are the same; pbs_order() and
+    wire_words() report the setting, and SiWires takes its row width from it."""
+
+    def __init__(self, client_key=None, params=None, bsk=None, ksk=None, device=0, generic=None, order="ks_pbs"):
+        if order not in _ORDER_FLAGS:
+            raise ValueError(f"order must be 'ks_pbs' or 'pbs_ks', not {order!r}")
         if generic not in _GENERIC_FLAGS:
             raise ValueError("generic must be None, 'allow', 'force', 'allow+multibit', 'force+multibit', 'large', "
                              f"'allow+large' or 'force+large', not {generic!r}")
         self.params = client_key.params if client_key is not None else params
         self.generic = generic
+        self.order = order
         h = nv.vp()
-        hip_check(hip.helm_si_ctx_create_ex(device, C.byref(self.params), _GENERIC_FLAGS[generic], C.byref(h)))
+        hip_check(hip.helm_si_ctx_create_ex(device, C.byref(self.params), _GENERIC_FLAGS[generic] | _ORDER_FLAGS[order],
+                                            C.byref(h)))
         self._h = h
-        self.dim = self.params.k * self.params.N
+        self.dim = self.params.k * self.params.N  # of a big row (keyswitch_batch / pbs_batch), whatever the order
+        self.wire_dim = self.wire_words() - 1     # of a wire row
         if client_key is not None:
             bsk, ksk = client_key.bsk, client_key.ksk
         if bsk is not None:
@@ -154,6 +169,7 @@ class SiServerKey:
         """A lane (helm_si_ctx_fork): shares this key's device-resident keys and wire tables, own stream and scratch."""
         lane = SiServerKey.__new__(SiServerKey)
         lane.params, lane.dim, lane.generic = self.params, self.dim, self.generic
+        lane.order, lane.wire_dim = self.order, self.wire_dim
         h = nv.vp()
         hip_check(hip.helm_si_ctx_fork(self._h, C.byref(h)))
         lane._h = h
@@ -186,6 +202,20 @@ class SiServerKey:
         """49, 46 or 50: the CRT pair of prime fields this context's bootstrap kernels compute in (helm_si_field_bits: it
         follows the loaded key for k > 1 contexts; 50 is the large-N kernel's pair)."""
         return int(hip.helm_si_field_bits(self._h))
+
+    def pbs_order(self):
+        """helm_si_pbs_order: 1 = keyswitch, then bootstrap (order "ks_pbs"), 0 = bootstrap, then keyswitch ("pbs_ks")."""
+        v = int(hip.helm_si_pbs_order(self._h))
+        if v < 0:
+            hip_check(v)
+        return v
+
+    def wire_words(self):
+        """helm_si_wire_words: words of a wire row, k*N + 1 in order 1 and n + 1 in order 0."""
+        v = int(hip.helm_si_wire_words(self._h))
+        if v < 0:
+            hip_check(v)
+        return v
 
     def kernel_class(self):
         """"tuned" when a tuned bootstrap build runs this context's launches, "generic" when the generic kernel does (a shape
@@ -224,7 +254,7 @@ class SiServerKey:
             hip_check(hip.helm_si_set_audit(self._h, nv.SI_AUDIT_FN(0), None))
             self._audit = None
             return
-        brow = self.params.k * self.params.N + 1
+        brow = self.wire_dim + 1
         N = self.params.N
 
         def trampoline(_user, recp):
@@ -283,7 +313,7 @@ class SiServerKey:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         self.set_stream(torch.cuda.current_stream().cuda_stream)
-        row = self.dim + 1
+        row = self.wire_dim + 1
         stage = torch.empty((capacity_rows, row), dtype=torch.int64, device=dev)
         gather = torch.empty((capacity_rows * world, row), dtype=torch.int64, device=dev)
 
@@ -378,7 +408,7 @@ class SiServerKey:
 
 
 class SiWires:
-    """HBM-resident ciphertext table: rows of k*N+1 uint64."""
+    """HBM-resident ciphertext table: rows of the server key's wire_words() uint64 (k*N+1, or n+1 in order "pbs_ks")."""
 
     def __init__(self, server_key, n_rows):
         self.sk = server_key
@@ -397,14 +427,14 @@ class SiWires:
 
     def upload(self, idx, lwe):
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        lwe = np.ascontiguousarray(lwe, dtype=np.uint64).reshape(len(idx), self.sk.dim + 1)
+        lwe = np.ascontiguousarray(lwe, dtype=np.uint64).reshape(len(idx), self.sk.wire_dim + 1)
         hip_check(hip.helm_si_wires_upload(self.sk._h, self._h, nv.as_i32p(idx), nv.as_u64p(lwe), len(idx)))
 
     def download(self, idx=None):
         if idx is None:
             idx = np.arange(self.n_rows)
         idx = np.ascontiguousarray(idx, dtype=np.int32)
-        out = np.zeros((len(idx), self.sk.dim + 1), dtype=np.uint64)
+        out = np.zeros((len(idx), self.sk.wire_dim + 1), dtype=np.uint64)
         hip_check(hip.helm_si_wires_download(self.sk._h, self._h, nv.as_i32p(idx), nv.as_u64p(out), len(idx)))
         return out
 

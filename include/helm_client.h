@@ -79,12 +79,16 @@ int helm_client_phase(const helm_client_key *key, const uint32_t *lwe, int64_t c
 /* ---- shortint (LUT / arithmetic mode) client: 64-bit torus, KS_PBS order ------------
  * tfhe::shortint::gen_keys(PARAM_...)              reference src/bin/helm.rs:301
  * ClientKey::encrypt(u64) / decrypt                reference src/circuit.rs:982-996, 1092
- * Ciphertexts are encrypted under the BIG key (k*N words + body). */
+ * Ciphertexts are encrypted under the BIG key (k*N words + body); for a context in the bootstrap-first order
+ * (HELM_SI_CREATE_PBS_KS, include/helm_shortint.h) the *_small functions below encrypt under the SMALL key (n words + body).
+ * Key generation is the same for both orders: one key drives contexts of either. */
 typedef struct helm_si_client_key helm_si_client_key;
 /* "shortint_m2c2": PARAM_MESSAGE_2_CARRY_2_KS_PBS [recalled; the 3-bit-capable
  * class tests/circuit_test.rs:287 needs]; "shortint_m2c2_multibit3":
  * PARAM_MULTI_BIT_MESSAGE_2_CARRY_2_GROUP_3_KS_PBS, the arithmetic-mode set of src/bin/helm.rs:83
- * [dimensions recalled]; "si_toy_*": small sets for exact oracle comparisons. */
+ * [dimensions recalled]; "shortint_m2c2_pbs_ks": shortint_m2c2's shape with an LWE side chosen for the bootstrap-first
+ * order [APPROXIMATE: not tfhe's PARAM_MESSAGE_2_CARRY_2_PBS_KS values, see helm_client64.cpp]; "si_toy_*": small sets for
+ * exact oracle comparisons. */
 int helm_si_client_named_params(const char *name, helm_si_params *params, double *lwe_noise_std,
                                 double *glwe_noise_std);
 int helm_si_client_keygen(const helm_si_params *params, double lwe_noise_std, double glwe_noise_std,
@@ -105,6 +109,10 @@ int helm_si_client_encrypt(helm_si_client_key *key, const uint64_t *values, int6
  * ClientKey::decrypt is this value mod message_modulus */
 int helm_si_client_decrypt(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values_out);
 int helm_si_client_phase(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, int small, uint64_t *phase_out);
+/* The same under the small (LWE) key: rows of n + 1 words, the LWE noise, the same encoding v * delta - the wire rows of a
+ * context created with HELM_SI_CREATE_PBS_KS (helm_si_client_phase with small = 1 reads such rows). */
+int helm_si_client_encrypt_small(helm_si_client_key *key, const uint64_t *values, int64_t count, uint64_t *lwe_out);
+int helm_si_client_decrypt_small(const helm_si_client_key *key, const uint64_t *lwe, int64_t count, uint64_t *values_out);
 
 /* ---- key import: tfhe-rs 0.4 containers <-> this ABI (helm_amd/csrc/host/key_import.cpp) ----------
  * What the Rust shim (rust/helm-hip) calls between tfhe's `LweBootstrapKey` / `LweKeyswitchKey`

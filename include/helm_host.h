@@ -231,6 +231,10 @@ void helm_host_si_enc_map_free(helm_si_enc_map *m);
 int helm_host_si_enc_map_blocks(const helm_si_enc_map *m);
 int helm_host_si_enc_map_row_words(const helm_si_enc_map *m);
 int helm_host_si_enc_map_insert(helm_si_enc_map *m, const char *wire, const uint64_t *lwe);
+/* The same for a client buffer whose length is known: n_words must be blocks x helm_host_si_enc_map_row_words() - rows of
+ * the server key's width (helm_si_wire_words: k N + 1 words, or n + 1 under HELM_SI_CREATE_PBS_KS) - or the call is refused
+ * with a message that names both widths and nothing is uploaded. */
+int helm_host_si_enc_map_insert_words(helm_si_enc_map *m, const char *wire, const uint64_t *lwe, int64_t n_words);
 int helm_host_si_enc_map_get(const helm_si_enc_map *m, const char *wire, uint64_t *lwe_out);
 int helm_host_si_enc_map_contains_key(const helm_si_enc_map *m, const char *wire);
 char *helm_host_si_enc_map_keys(const helm_si_enc_map *m);

@@ -28,7 +28,8 @@
  * stream-asynchronous with helm_si_sync(), no CPU fallback.
  *
  * Layouts (all words uint64_t, arithmetic mod 2^64)
- *   big LWE / wire row   k*N mask words + body
+ *   big LWE row          k*N mask words + body: the wire row of a context in order 1 (the default)
+ *   small LWE row        n mask words + body: the wire row under HELM_SI_CREATE_PBS_KS (helm_si_wire_words)
  *   bootstrapping key    [n][pbs_l][k+1][k+1][N]      (as helm_hip.h, 64-bit); multi-bit sets
  *                        (grouping_factor g > 1): [n/g][2^g][pbs_l][k+1][k+1][N]
  *   keyswitching key     [k*N][ks_l][n+1]
@@ -82,7 +83,8 @@ enum {
     HELM_SI_CREATE_FORCE_GENERIC = 2, /* run every launch on the generic kernel, tuned shapes too (implies 1) */
     /* 4 and 8 are reserved: refused as unknown bits */
     HELM_SI_CREATE_GENERIC_MULTIBIT = 16, /* with 1 or 2: multi-bit shapes may run on the generic kernel's multi-bit form */
-    HELM_SI_CREATE_LARGE_N = 32 /* admit k = 1, N = 4096 (the 5-bit shortint sets): it runs on the large-N kernel */
+    HELM_SI_CREATE_LARGE_N = 32, /* admit k = 1, N = 4096 (the 5-bit shortint sets): it runs on the large-N kernel */
+    HELM_SI_CREATE_PBS_KS = 64 /* bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words under the small key */
 };
 /* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
  * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
@@ -119,6 +121,22 @@ enum {
  * unchanged, many-LUT included.  Refused with a message that names the large-N domain: k > 1 at N = 4096, multi-bit at
  * N = 4096, and N = 8192 (its accumulator alone is 128 KiB of LDS, and its products exceed the pair).  helm_wop_ctx_create
  * refuses a PBS-side context of this class, and the bound-checking build refuses the class at creation.
+ * HELM_SI_CREATE_PBS_KS (alone or beside any admitted combination of the bits above) chooses the other ciphertext order of a
+ * tfhe shortint set (EncryptionKeyChoice::Small, the PARAM_*_PBS_KS sets): wire rows are LWE ciphertexts under the SMALL key,
+ * n + 1 words, and a look-up is programmable bootstrap small->big, then keyswitch big->small.  The keys are the same keys in
+ * the same layouts, and the bit changes no admission rule: the same shapes are admitted and refused with the same messages,
+ * the capacity check and the kernel class chosen are those of the call without it.  What changes is the row width of
+ * everything that holds wire rows (helm_si_wire_words) and the launch sequence of a look-up: ONE bootstrap launch whose jobs
+ * read their input rows straight from the wire table and write big rows into the context's stage buffer, then ONE keyswitch
+ * whose jobs take stage rows to table rows.  Every input row is read before any output row is written, so a call whose
+ * output row is its own or another job's input row leaves what the call without the bit leaves for the same hazard (the
+ * plaintexts under it; the words differ, they are ciphertexts under another key).  helm_si_apply_luts,
+ * helm_si_apply_many_luts (n_out keyswitches per rotation, none for an output of -1), helm_si_eval_lut_level and
+ * helm_si_set_level_many_lut follow it, lanes and the audit hook included.  Under an exchange a rank bootstraps its chunk,
+ * keyswitches it into its exchange slot, rows of n + 1 words are gathered and scattered; capacity_rows counts rows whatever
+ * their width, and the table is word for word the unsharded one.  helm_wop_ctx_create refuses such a PBS side by name (its
+ * bit extraction, circuit bootstrap and result rows assume big rows).  The bound-checking build admits the order: nothing in
+ * it depends on the row width.
  * Unknown flag bits (4 and 8 are reserved): HELM_ERR_INVALID. */
 int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
 /* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic), 2 = the large-N
@@ -127,6 +145,13 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
  * this reports the kernel the launches actually run on: HELM_SI_CREATE_FORCE_GENERIC is part of this API, so a forced
  * tuned shape reports 1.  A lane reports its primary's class.  Negative on error. */
 int helm_si_kernel_class(const helm_si_ctx *ctx);
+/* The ciphertext order of the context, numbered as helm_hip_pbs_order of the boolean engine: 1 = keyswitch, then bootstrap
+ * (wire rows under the big key; every context made without HELM_SI_CREATE_PBS_KS), 0 = bootstrap, then keyswitch.  A lane
+ * reports its primary's order.  Negative on error. */
+int helm_si_pbs_order(const helm_si_ctx *ctx);
+/* Words of a wire row: k*N + 1 in order 1, n + 1 in order 0.  The width of the rows of helm_si_wires_*, helm_si_lincomb, the
+ * exchange buffers (stage_dev, gather_dev) and the audit records.  A lane reports its primary's width.  Negative on error. */
+int64_t helm_si_wire_words(const helm_si_ctx *ctx);
 int helm_si_ctx_destroy(helm_si_ctx *ctx);
 /* A lane: a second context on the same device that shares `primary`'s keys and may work on its wire tables, with
  * its own stream and scratch - independent parts of a circuit can then be evaluated concurrently (one host thread
@@ -165,7 +190,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
 int helm_si_load_keyswitch_key(helm_si_ctx *ctx, const uint64_t *ksk, size_t n_words);
 
 /* Device-resident ciphertext table (replaces HashMap<String, Arc<RwLock<CtxtShortInt>>>,
- * circuit.rs:1046-1049).  Rows of k*N+1 words. */
+ * circuit.rs:1046-1049).  Rows of helm_si_wire_words() words: k*N+1, or n+1 under HELM_SI_CREATE_PBS_KS. */
 int helm_si_wires_alloc(helm_si_ctx *ctx, int64_t n_rows, helm_si_wires **out);
 int helm_si_wires_free(helm_si_ctx *ctx, helm_si_wires *w);
 int helm_si_wires_upload(helm_si_ctx *ctx, helm_si_wires *w, const int32_t *idx, const uint64_t *lwe_host,
@@ -252,7 +277,7 @@ int helm_si_set_level_many_lut(helm_si_ctx *ctx, int on);
  * bootstrap batch of at least `min_batch` ciphertexts - helm_si_apply_luts() and everything
  * built on it: helm_si_eval_lut_level(), the radix operators of the host library - is split
  * into `world` contiguous chunks.  This rank keyswitches and bootstraps chunk `rank` into
- * `stage_dev` (rows of k*N+1 words), calls fn(user, rows_per_rank), which must all-gather
+ * `stage_dev` (rows of helm_si_wire_words() words), calls fn(user, rows_per_rank), which must all-gather
  * rows_per_rank rows of stage_dev from every rank into gather_dev in rank order ON THE
  * CONTEXT'S STREAM (ncclAllGather over RCCL/xGMI; helm_si_set_stream) and return 0, and then
  * scatters the gathered rows into the table.  Every rank must issue the same calls in the same
@@ -284,14 +309,15 @@ int helm_si_exchange_world(const helm_si_ctx *ctx);
  * `fn` together with the call's arguments; a non-zero return fails the call.  How tests/test_gpu_audit.py checks whole
  * evaluations at the full parameter sets against the CPU oracle, operation by operation (each batch's outputs == the
  * oracle's on the GPU's own inputs, hence every wire).  Slow by construction (two synchronous copies per call); lanes
- * forked AFTER this call inherit it.  fn = NULL switches it off. */
+ * forked AFTER this call inherit it.  fn = NULL switches it off.  The rows handed over are wire rows of the context's width,
+ * helm_si_wire_words() words each: k*N+1 in order 1, n+1 under HELM_SI_CREATE_PBS_KS. */
 typedef struct {
     int32_t kind;             /* 0 = helm_si_apply_luts, 1 = helm_si_lincomb, 2 = helm_si_apply_many_luts (fields as kind 0, but
                                * terms = n_out and out_rows = count * n_out rows, output x of ciphertext g at row g * n_out + x,
                                * a skipped output: zeros) */
     int32_t terms;            /* lincomb: operands per output; apply_many_luts: n_out */
     int64_t count, n_luts;
-    const uint64_t *in_rows;  /* apply_luts: count rows of k*N+1 words; lincomb: count * terms (a skipped operand: zeros) */
+    const uint64_t *in_rows;  /* apply_luts: count wire rows; lincomb: count * terms (a skipped operand: zeros) */
     const uint64_t *out_rows; /* count rows */
     const int32_t *lut_idx;   /* apply_luts */
     const uint64_t *luts;     /* apply_luts: n_luts test polynomials of N words */
@@ -312,7 +338,8 @@ int helm_si_bound_violations(helm_si_ctx *ctx, uint32_t counts[8], int reset);
  * size; the host library merges the look-up rounds of concurrent operators into launches of at most this size. */
 int64_t helm_si_round_capacity(helm_si_ctx *ctx);
 
-/* Primitive forms on host buffers (tests).  small: count x (n+1); big: count x (k*N+1). */
+/* Primitive forms on host buffers (tests).  small: count x (n+1); big: count x (k*N+1).  They work on host buffers of these
+ * two widths whatever the context's order: HELM_SI_CREATE_PBS_KS changes nothing about them. */
 int helm_si_keyswitch_batch(helm_si_ctx *ctx, const uint64_t *in_big, uint64_t *out_small, int64_t count);
 int helm_si_pbs_batch(helm_si_ctx *ctx, const uint64_t *in_small, const uint64_t *luts, int64_t n_luts,
                       const int32_t *lut_idx, uint64_t *out_big, int64_t count);

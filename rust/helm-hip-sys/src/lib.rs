@@ -70,6 +70,7 @@ pub const HELM_SI_CREATE_ALLOW_GENERIC: i32 = 1;
 pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
 pub const HELM_SI_CREATE_GENERIC_MULTIBIT: i32 = 16; // with one of the two above: the generic kernel's multi-bit form
 pub const HELM_SI_CREATE_LARGE_N: i32 = 32; // admit k = 1, N = 4096 (the 5-bit shortint sets): the large-N kernel
+pub const HELM_SI_CREATE_PBS_KS: i32 = 64; // bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words
 
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
@@ -218,6 +219,8 @@ extern "C" {
     pub fn helm_si_ctx_create(device_id: c_int, params: *const helm_si_params, out: *mut *mut helm_si_ctx) -> c_int;
     pub fn helm_si_ctx_create_ex(device_id: c_int, params: *const helm_si_params, flags: c_int, out: *mut *mut helm_si_ctx) -> c_int;
     pub fn helm_si_kernel_class(ctx: *const helm_si_ctx) -> c_int;
+    pub fn helm_si_pbs_order(ctx: *const helm_si_ctx) -> c_int;
+    pub fn helm_si_wire_words(ctx: *const helm_si_ctx) -> i64;
     pub fn helm_si_ctx_destroy(ctx: *mut helm_si_ctx) -> c_int;
     pub fn helm_si_ctx_fork(primary: *mut helm_si_ctx, lane_out: *mut *mut helm_si_ctx) -> c_int;
     pub fn helm_si_load_bootstrap_key(ctx: *mut helm_si_ctx, bsk_std: *const u64, n_words: usize) -> c_int;

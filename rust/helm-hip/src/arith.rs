@@ -37,11 +37,19 @@ fn blocks_of(ptxt_type: &str) -> i32 {
 
 impl<'a> HipArithCircuit<'a> {
     pub fn new(client_key: tfhe::ClientKey, keys: &crate::keys::StandardKeys64, circuit: Circuit<'a>, device_id: i32) -> Self {
+        Self::new_with_order(client_key, keys, circuit, device_id, false)
+    }
+
+    /// `new` for either ciphertext order (HipLutCircuit::new_with_order): `pbs_ks` = true for a client key of a
+    /// `PARAM_*_PBS_KS` set, whose radix blocks are LWE ciphertexts under the small key, n + 1 words each.
+    pub fn new_with_order(client_key: tfhe::ClientKey, keys: &crate::keys::StandardKeys64, circuit: Circuit<'a>, device_id: i32,
+                          pbs_ks: bool) -> Self {
         let mut ctx = std::ptr::null_mut();
-        crate::check(unsafe { sys::helm_si_ctx_create(device_id, &keys.params, &mut ctx) });
+        let flags = if pbs_ks { sys::HELM_SI_CREATE_PBS_KS } else { 0 };
+        crate::check(unsafe { sys::helm_si_ctx_create_ex(device_id, &keys.params, flags, &mut ctx) });
         crate::check(unsafe { sys::helm_si_load_bootstrap_key(ctx, keys.bsk.as_ptr(), keys.bsk.len()) });
         crate::check(unsafe { sys::helm_si_load_keyswitch_key(ctx, keys.ksk.as_ptr(), keys.ksk.len()) });
-        let row_words = (keys.params.k * keys.params.N) as usize + 1;
+        let row_words = unsafe { sys::helm_si_wire_words(ctx) } as usize;
         HipArithCircuit { circuit, client_key, ctx, wires: std::ptr::null_mut(), row_of: HashMap::new(), blocks: 0,
                           row_words, scratch_first_row: 0, evaluated_cycle: None, many_lut: false }
     }

@@ -21,7 +21,7 @@ pub struct HipLutCircuit<'a> {
     pub(crate) ctx: *mut sys::helm_si_ctx,
     wires: *mut sys::helm_si_wires,
     row_of: HashMap<String, i32>,
-    row_words: usize, // k N + 1
+    row_words: usize, // helm_si_wire_words: k N + 1, or n + 1 in the bootstrap-first order
     /// same-cycle memo (gates.rs:55-59, 288-292): the cycle whose outputs the table holds
     evaluated_cycle: Option<usize>,
 }
@@ -30,11 +30,21 @@ impl<'a> HipLutCircuit<'a> {
     /// `LutCircuit::new(client_key, server_key, circuit)` (circuit.rs:393-406) with the server key replaced by an engine
     /// context holding the same key material in the standard domain (keys.rs::standard_keys64).
     pub fn new(client_key: ClientKey, keys: &crate::keys::StandardKeys64, circuit: Circuit<'a>, device_id: i32) -> Self {
+        Self::new_with_order(client_key, keys, circuit, device_id, false)
+    }
+
+    /// `new` for either ciphertext order of a tfhe shortint set.  `pbs_ks` = true is for a client key generated from a
+    /// `PARAM_*_PBS_KS` set ([RECALLED] `EncryptionKeyChoice::Small`): `client_key.encrypt(v).ct` is then an LWE ciphertext
+    /// under the SMALL key, n + 1 words, the context is created with HELM_SI_CREATE_PBS_KS and every row of the table has
+    /// that width (helm_si_wire_words).  The key material of `keys` is the same in both orders.
+    pub fn new_with_order(client_key: ClientKey, keys: &crate::keys::StandardKeys64, circuit: Circuit<'a>, device_id: i32,
+                          pbs_ks: bool) -> Self {
         let mut ctx = std::ptr::null_mut();
-        check(unsafe { sys::helm_si_ctx_create(device_id, &keys.params, &mut ctx) });
+        let flags = if pbs_ks { sys::HELM_SI_CREATE_PBS_KS } else { 0 };
+        check(unsafe { sys::helm_si_ctx_create_ex(device_id, &keys.params, flags, &mut ctx) });
         check(unsafe { sys::helm_si_load_bootstrap_key(ctx, keys.bsk.as_ptr(), keys.bsk.len()) });
         check(unsafe { sys::helm_si_load_keyswitch_key(ctx, keys.ksk.as_ptr(), keys.ksk.len()) });
-        let row_words = (keys.params.k * keys.params.N) as usize + 1;
+        let row_words = unsafe { sys::helm_si_wire_words(ctx) } as usize;
         HipLutCircuit { circuit, client_key, ctx, wires: std::ptr::null_mut(), row_of: HashMap::new(), row_words,
                         evaluated_cycle: None }
     }
