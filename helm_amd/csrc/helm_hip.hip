@@ -15,6 +15,7 @@
 #include "../../include/helm_comm.h"
 #include "ntt_fp64.h"
 #include "shard_rule.h"
+#include "keyswitch.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -1706,139 +1707,44 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
 
 #if HELM_HIP_TU == 0 // the keyswitch, linear and table kernels: main translation unit only (see launch_pbs_wide)
 // ------------------------------------------------------------------------------------
-// k_keyswitch: grid (ceil(jobs / 4), column chunks); 256 threads; one output column per
-// thread, FOUR gates per workgroup so that every key word fetched (from L2 / Infinity
-// Cache: the key is 12 MB and shared by all gates) feeds four multiply-adds.
-//   out[c] = (c == n ? body : 0) - sum_t sum_j digit(t,j) * KSK[t][j][c]
-// The digits of the four gates are decomposed once into LDS, packed as 4 x int8 per word
-// (one broadcast ds_read_b32 per key word).  MUX recombination (sum of two bootstrap
-// outputs + 1/8) is folded into the input read.
+// The keyswitch kernels: wrappers over the bodies of keyswitch.h, one set per row policy.
+//   k_keyswitch / k_keyswitch_gate      vector-ALU form, ks_l in 1..6, 8
+//   k_ks_digits / k_ks_gate_digits      matrix-core form (ks_l in {1, 2, 4, 8}): digits in A-fragment order ...
+//   k_ks_mfma                           ... times the key's four byte planes, two column tiles per wave
+//                                       (int32 accumulators: |sum| <= 4096 * 64 * 128 < 2^25)
 // ------------------------------------------------------------------------------------
+// KsJob rows: one row of the big-LWE buffer or the sum of two (MUX recombination: two bootstrap outputs + 1/8 on the body)
+struct KsRows {
+    using Job = KsJob;
+    using Word = uint32_t;
+    const KsJob &job;
+    const uint32_t *big;
+    size_t row;
+    __device__ __forceinline__ KsRows(const KsJob &job, const uint32_t *big, size_t row) : job(job), big(big), row(row) {}
+    __device__ __forceinline__ uint32_t word(int t) const
+    {
+        uint32_t v = big[row * (size_t)job.big0 + t];
+        if (job.big1 >= 0) v += big[row * (size_t)job.big1 + t];
+        return v;
+    }
+    __device__ __forceinline__ uint32_t body(int kN) const { return word(kN) + job.add_body; }
+    static __device__ __forceinline__ int out_row(const KsJob &job, int) { return job.out; }
+};
+
 template <int KSL>
 __global__ __launch_bounds__(256) void k_keyswitch(const KsJob *__restrict__ jobs, const uint32_t *__restrict__ big,
                                                    const uint32_t *__restrict__ ksk, uint32_t *__restrict__ out,
                                                    int n, int kN, int logB, int count, int t_chunk)
 {
-    // blockIdx.z selects a slice of t_chunk input coefficients (narrow launches: the k*N*ks_l key rows
-    // are split over several workgroups whose partial sums meet in `out` by atomic add - wrapping
-    // integer adds, any order; the rows are zeroed beforehand).  gridDim.z == 1: plain stores.
-    constexpr int G = 4;
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *DIG = reinterpret_cast<uint32_t *>(smem); // [t_chunk * KSL] words, byte g = digit of gate g
-    const int g0 = blockIdx.x * G;
-    const int ng = min(G, count - g0);
-    const int t0 = blockIdx.z * t_chunk, t1 = min(kN, t0 + t_chunk);
-    KsJob job[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) job[g] = jobs[g0 + (g < ng ? g : 0)];
-    const size_t brow = (size_t)kN + 1;
-    for (int t = t0 + threadIdx.x; t < t1; t += 256) {
-        uint32_t packed[KSL];
-#pragma unroll
-        for (int j = 0; j < KSL; j++) packed[j] = 0;
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            if (g < ng) {
-                uint32_t v = big[brow * (size_t)job[g].big0 + t];
-                if (job[g].big1 >= 0) v += big[brow * (size_t)job[g].big1 + t];
-                int dig[KSL];
-                decompose<KSL>(v, logB, dig);
-#pragma unroll
-                for (int j = 0; j < KSL; j++) packed[j] |= ((uint32_t)dig[j] & 0xFFu) << (8 * g);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KSL; j++) DIG[(t - t0) * KSL + j] = packed[j];
-    }
-    __syncthreads();
-    const int c = blockIdx.y * 256 + threadIdx.x;
-    if (c > n) return;
-    const size_t krow = (size_t)n + 1;
-    uint32_t acc[G] = {0, 0, 0, 0};
-    const uint32_t *kp = ksk + (size_t)t0 * KSL * krow + c;
-    const int rows = (t1 - t0) * KSL;
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t w = kp[(size_t)r * krow];
-        const uint32_t pk = DIG[r];
-#pragma unroll
-        for (int g = 0; g < G; g++) acc[g] += (uint32_t)__builtin_amdgcn_sbfe(pk, 8 * g, 8) * w;
-    }
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        if (g < ng) {
-            uint32_t body = 0;
-            if (c == n && blockIdx.z == 0) {
-                body = big[brow * (size_t)job[g].big0 + kN] + job[g].add_body;
-                if (job[g].big1 >= 0) body += big[brow * (size_t)job[g].big1 + kN];
-            }
-            uint32_t *dst = out + krow * (size_t)job[g].out + c;
-            if (gridDim.z == 1) *dst = body - acc[g];
-            else atomicAdd(dst, body - acc[g]);
-        }
-    }
+    helm_ks::vector_body<KSL, KsRows>(jobs, big, ksk, out, n, kN, logB, count, t_chunk);
 }
 
-// ------------------------------------------------------------------------------------
-// Keyswitch on the matrix cores (ks_l in {1, 2, 4, 8}): the keyswitch of a level is a GEMM
-//   out[g][c] = body_g [c == n] - sum_r D[g][r] * K[r][c]     (mod 2^32),  r = t * ks_l + level
-// with D the signed digits (|d| <= 2^(logB-1) <= 64: int8) of the big LWE's mask words and K the key.
-// K is split into its four bytes, each recentred to a signed byte K_b - 128 (v_mfma_i32_16x16x64_i8 is
-// signed x signed):   sum_r d K = sum_b 2^(8b) sum_r d (K_b - 128)  +  0x80808080 * sum_r d
-// - four int8 GEMMs with exact int32 accumulators (|sum| <= 4096 * 64 * 128 < 2^25) and a per-gate
-// correction.  k_ks_digits decomposes once per gate (MUX recombination folded in) and writes D in
-// A-fragment order; k_ks_mfma: one wave = 64 gates x 32 key columns, the four gate tiles of a wave reuse
-// every B fragment (1 KiB, coalesced) four times.  Integer arithmetic: bit-identical to k_keyswitch.
-// ------------------------------------------------------------------------------------
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// fragment (tile, kc): 64 lanes x 16 bytes; lane = (k-quarter << 4 | row or column), byte j: k = 64 kc + 16 kq + j
 template <int KSL>
 __global__ __launch_bounds__(256) void k_ks_digits(const KsJob *__restrict__ jobs, const uint32_t *__restrict__ big,
                                                    int8_t *__restrict__ dig, int32_t *__restrict__ dsum,
                                                    uint32_t *__restrict__ body, int kN, int logB, int count, int kchunks)
 {
-    const int g = blockIdx.x; // padded gate index; g >= count: an all-zero row
-    __shared__ int red[256];
-    int local = 0;
-    const size_t brow = (size_t)kN + 1;
-    const bool live = g < count;
-    KsJob job{};
-    if (live) job = jobs[g];
-    int8_t *tile = dig + (size_t)(g >> 4) * kchunks * 1024;
-    for (int t = threadIdx.x; t < kN; t += 256) {
-        int d[KSL];
-        if (live) {
-            uint32_t v = big[brow * (size_t)job.big0 + t];
-            if (job.big1 >= 0) v += big[brow * (size_t)job.big1 + t];
-            decompose<KSL>(v, logB, d);
-        } else {
-#pragma unroll
-            for (int j = 0; j < KSL; j++) d[j] = 0;
-        }
-        const int r0 = t * KSL, kc = r0 >> 6, kq = (r0 & 63) >> 4, j0 = r0 & 15;
-        int8_t *dst = tile + ((size_t)kc * 64 + (kq << 4 | (g & 15))) * 16 + j0;
-#pragma unroll
-        for (int j = 0; j < KSL; j++) {
-            dst[j] = (int8_t)d[j];
-            local += d[j];
-        }
-    }
-    red[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        dsum[g] = red[0];
-        uint32_t b = 0;
-        if (live) {
-            b = big[brow * (size_t)job.big0 + kN] + job.add_body;
-            if (job.big1 >= 0) b += big[brow * (size_t)job.big1 + kN];
-        }
-        body[g] = b;
-    }
+    helm_ks::digits_body<KSL, KSL, KsRows>(jobs, big, dig, dsum, body, kN, logB, count, kchunks);
 }
 
 __global__ __launch_bounds__(64) void k_ks_mfma(const KsJob *__restrict__ jobs, const int8_t *__restrict__ dig,
@@ -1846,57 +1752,7 @@ __global__ __launch_bounds__(64) void k_ks_mfma(const KsJob *__restrict__ jobs, 
                                                 const int8_t *__restrict__ kplanes, uint32_t *__restrict__ out, int n,
                                                 int count, int kchunks, int ctiles)
 {
-    constexpr int GT = 4, CT = 2; // gate tiles (16 gates each) and column tiles (16 columns each) per wave
-    const int lane = threadIdx.x;
-    const int gt0 = blockIdx.x * GT, ct0 = blockIdx.y * CT;
-    const v4i *A = reinterpret_cast<const v4i *>(dig) + (size_t)gt0 * kchunks * 64 + lane;
-    const v4i *B = reinterpret_cast<const v4i *>(kplanes) + lane;
-    const size_t plane = (size_t)ctiles * kchunks * 64; // fragments of one byte plane, in v4i units
-    v4i acc[GT][CT][4];
-#pragma unroll
-    for (int a = 0; a < GT; a++)
-#pragma unroll
-        for (int c = 0; c < CT; c++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) acc[a][c][b] = v4i{0, 0, 0, 0};
-    for (int kc = 0; kc < kchunks; kc++) {
-        v4i fa[GT], fb[CT][4];
-#pragma unroll
-        for (int a = 0; a < GT; a++) fa[a] = A[((size_t)a * kchunks + kc) * 64];
-#pragma unroll
-        for (int c = 0; c < CT; c++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int ct = ct0 + c < ctiles ? ct0 + c : ctiles - 1; // a wave past the last tile repeats it (discarded)
-                fb[c][b] = B[(size_t)b * plane + ((size_t)ct * kchunks + kc) * 64];
-            }
-#pragma unroll
-        for (int a = 0; a < GT; a++)
-#pragma unroll
-            for (int c = 0; c < CT; c++)
-#pragma unroll
-                for (int b = 0; b < 4; b++)
-                    acc[a][c][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[a], fb[c][b], acc[a][c][b], 0, 0, 0);
-    }
-    // C/D map: column = lane & 15, row = (lane >> 4) * 4 + reg
-    const size_t krow = (size_t)n + 1;
-#pragma unroll
-    for (int a = 0; a < GT; a++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) {
-            const int g = (gt0 + a) * 16 + (lane >> 4) * 4 + reg;
-            if (g >= count) continue;
-            const uint32_t corr = 0x80808080u * (uint32_t)dsum[g];
-            uint32_t *dst = out + krow * (size_t)jobs[g].out;
-#pragma unroll
-            for (int c = 0; c < CT; c++) {
-                const int col = (ct0 + c) * 16 + (lane & 15);
-                if (ct0 + c >= ctiles || col > n) continue;
-                const uint32_t s = (uint32_t)acc[a][c][0][reg] + ((uint32_t)acc[a][c][1][reg] << 8) +
-                                   ((uint32_t)acc[a][c][2][reg] << 16) + ((uint32_t)acc[a][c][3][reg] << 24) + corr;
-                dst[col] = (col == n ? body[g] : 0u) - s;
-            }
-        }
+    helm_ks::product_body<2, KsRows>(jobs, dig, dsum, body, kplanes, out, n, count, kchunks, ctiles);
 }
 
 // rows named by the keyswitch jobs <- 0 (before a row-split keyswitch accumulates into them)
@@ -1909,10 +1765,9 @@ __global__ __launch_bounds__(256) void k_ks_zero(const KsJob *__restrict__ jobs,
 // ------------------------------------------------------------------------------------
 // Keyswitch-first levels (pbs_order = 1: wires are big LWE rows of k*N + 1 words under the GLWE key).  A gate is linear
 // combination -> keyswitch -> bootstrap, so the keyswitch is the front of the level: k_keyswitch_gate and k_ks_gate_digits
-// are k_keyswitch and k_ks_digits fed by the level's PbsJob list - they form gate_lincomb() of up to three wire rows as they
-// read them (the +-1/8 on the body word, index k*N) - with the same decompose<>, the same packed-byte LDS layout and row
-// split, the same A-fragment order, dsum and body arrays (k_ks_mfma runs unchanged behind k_ks_gate_digits).  The small row
-// of job i is row i of the context's staging buffer (`out`); the blind-rotate kernels then take those rows as raw LWEs.
+// are the keyswitch bodies fed by the level's PbsJob list - they form gate_lincomb() of up to three wire rows as they read
+// them (the +-1/8 on the body word, index k*N); k_ks_mfma runs behind k_ks_gate_digits with the identity job list.  The small
+// row of job i is row i of the context's staging buffer (`out`); the blind-rotate kernels then take those rows as raw LWEs.
 // ------------------------------------------------------------------------------------
 struct GateRows {
     const uint32_t *a0, *a1, *a2;
@@ -1927,63 +1782,24 @@ struct GateRows {
     }
 };
 
+// PbsJob rows: the gate's linear combination of its wire rows; job g writes row g
+struct GateKsRows {
+    using Job = PbsJob;
+    using Word = uint32_t;
+    const PbsJob &job;
+    const GateRows rows;
+    __device__ __forceinline__ GateKsRows(const PbsJob &job, const uint32_t *wires, size_t row) : job(job), rows(job, wires, row) {}
+    __device__ __forceinline__ uint32_t word(int t) const { return rows.word(job, t, false); }
+    __device__ __forceinline__ uint32_t body(int kN) const { return rows.word(job, kN, true); }
+    static __device__ __forceinline__ int out_row(const PbsJob &, int g) { return g; }
+};
+
 template <int KSL>
 __global__ __launch_bounds__(256) void k_keyswitch_gate(const PbsJob *__restrict__ jobs, const uint32_t *__restrict__ wires,
                                                         const uint32_t *__restrict__ ksk, uint32_t *__restrict__ out,
                                                         int n, int kN, int logB, int count, int t_chunk)
 {
-    // grid, LDS layout and row split of k_keyswitch; gate g0 + g writes row g0 + g of `out`
-    constexpr int G = 4;
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *DIG = reinterpret_cast<uint32_t *>(smem); // [t_chunk * KSL] words, byte g = digit of gate g
-    const int g0 = blockIdx.x * G;
-    const int ng = min(G, count - g0);
-    const int t0 = blockIdx.z * t_chunk, t1 = min(kN, t0 + t_chunk);
-    const size_t brow = (size_t)kN + 1;
-    PbsJob job[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) job[g] = jobs[g0 + (g < ng ? g : 0)];
-    for (int t = t0 + threadIdx.x; t < t1; t += 256) {
-        uint32_t packed[KSL];
-#pragma unroll
-        for (int j = 0; j < KSL; j++) packed[j] = 0;
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            if (g < ng) {
-                const uint32_t v = GateRows(job[g], wires, brow).word(job[g], t, false);
-                int dig[KSL];
-                decompose<KSL>(v, logB, dig);
-#pragma unroll
-                for (int j = 0; j < KSL; j++) packed[j] |= ((uint32_t)dig[j] & 0xFFu) << (8 * g);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KSL; j++) DIG[(t - t0) * KSL + j] = packed[j];
-    }
-    __syncthreads();
-    const int c = blockIdx.y * 256 + threadIdx.x;
-    if (c > n) return;
-    const size_t krow = (size_t)n + 1;
-    uint32_t acc[G] = {0, 0, 0, 0};
-    const uint32_t *kp = ksk + (size_t)t0 * KSL * krow + c;
-    const int rows = (t1 - t0) * KSL;
-#pragma unroll 8
-    for (int r = 0; r < rows; r++) {
-        const uint32_t w = kp[(size_t)r * krow];
-        const uint32_t pk = DIG[r];
-#pragma unroll
-        for (int g = 0; g < G; g++) acc[g] += (uint32_t)__builtin_amdgcn_sbfe(pk, 8 * g, 8) * w;
-    }
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        if (g < ng) {
-            uint32_t body = 0;
-            if (c == n && blockIdx.z == 0) body = GateRows(job[g], wires, brow).word(job[g], kN, true);
-            uint32_t *dst = out + krow * (size_t)(g0 + g) + c;
-            if (gridDim.z == 1) *dst = body - acc[g];
-            else atomicAdd(dst, body - acc[g]);
-        }
-    }
+    helm_ks::vector_body<KSL, GateKsRows>(jobs, wires, ksk, out, n, kN, logB, count, t_chunk);
 }
 
 template <int KSL>
@@ -1991,40 +1807,7 @@ __global__ __launch_bounds__(256) void k_ks_gate_digits(const PbsJob *__restrict
                                                         int8_t *__restrict__ dig, int32_t *__restrict__ dsum,
                                                         uint32_t *__restrict__ body, int kN, int logB, int count, int kchunks)
 {
-    const int g = blockIdx.x; // padded gate index; g >= count: an all-zero row
-    __shared__ int red[256];
-    int local = 0;
-    const bool live = g < count;
-    PbsJob job{};
-    if (live) job = jobs[g];
-    const GateRows rows(job, wires, (size_t)kN + 1);
-    int8_t *tile = dig + (size_t)(g >> 4) * kchunks * 1024;
-    for (int t = threadIdx.x; t < kN; t += 256) {
-        int d[KSL];
-        if (live) {
-            decompose<KSL>(rows.word(job, t, false), logB, d);
-        } else {
-#pragma unroll
-            for (int j = 0; j < KSL; j++) d[j] = 0;
-        }
-        const int r0 = t * KSL, kc = r0 >> 6, kq = (r0 & 63) >> 4, j0 = r0 & 15;
-        int8_t *dst = tile + ((size_t)kc * 64 + (kq << 4 | (g & 15))) * 16 + j0;
-#pragma unroll
-        for (int j = 0; j < KSL; j++) {
-            dst[j] = (int8_t)d[j];
-            local += d[j];
-        }
-    }
-    red[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        dsum[g] = red[0];
-        body[g] = live ? rows.word(job, kN, true) : 0u;
-    }
+    helm_ks::digits_body<KSL, KSL, GateKsRows>(jobs, wires, dig, dsum, body, kN, logB, count, kchunks);
 }
 
 // raw[i] = {op -1, in0 = i, tv 0} (the bootstrap of staging row i), ident[i] = {out = i} (k_ks_mfma's and k_ks_zero's
@@ -2244,9 +2027,9 @@ struct helm_hip_ctx {
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: the key's four byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0;
     int ks_mfma = 1;             // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
-    DevBuf<int8_t> d_dig;
-    DevBuf<int32_t> d_dsum;
-    DevBuf<uint32_t> d_body;
+    DevBuf<int8_t> d_ksdig;
+    DevBuf<int32_t> d_ksdsum;
+    DevBuf<uint32_t> d_ksbody;
     uint32_t *tv_bool = nullptr; // one row: all +1/8
     bool have_bsk = false, have_ksk = false;
     int field = 51; // 51: FpH, 49: FpG (lazy) - both with short eighth roots of unity -, chosen from the parameter set
@@ -2841,55 +2624,48 @@ static hipError_t launch_pbs(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t coun
     return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
 }
 
-static hipError_t launch_ks(helm_hip_ctx *ctx, const KsJob *jobs, int64_t count, const uint32_t *big, uint32_t *out)
-{
-    const helm_hip_params &P = ctx->P;
-    const int kN = P.k * P.N;
-    if (ctx->ksk_planes && ctx->ks_mfma) {
-        // matrix-core path: digits once per gate, then the int8 GEMM over the key's byte planes
-        const int64_t padded = (count + 63) / 64 * 64;
-        if (ctx->d_dig.ensure((size_t)padded * kN * P.ks_l) || ctx->d_dsum.ensure((size_t)padded) || ctx->d_body.ensure((size_t)padded))
-            return hipErrorOutOfMemory;
-#define KSD_CASE(LV)                                                                                              \
-    case LV:                                                                                                      \
-        hipLaunchKernelGGL(k_ks_digits<LV>, dim3((unsigned)padded), dim3(256), 0, ctx->stream, jobs, big, ctx->d_dig.p, \
-                           ctx->d_dsum.p, ctx->d_body.p, kN, P.ks_logB, (int)count, ctx->ks_kchunks);            \
-        break;
-        switch (P.ks_l) {
-            KSD_CASE(1) KSD_CASE(2) KSD_CASE(4) KSD_CASE(8)
-        default: return hipErrorInvalidValue;
-        }
-#undef KSD_CASE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ks_mfma, dim3((unsigned)(padded / 64), (unsigned)((ctx->ks_ctiles + 1) / 2)), dim3(64), 0, ctx->stream,
-                           jobs, ctx->d_dig.p, ctx->d_dsum.p, ctx->d_body.p, ctx->ksk_planes, out, P.n, (int)count,
-                           ctx->ks_kchunks, ctx->ks_ctiles);
+// What the boolean engine's keyswitch launches have of their own (helm_ks::launch): the matrix-core form whenever the key
+// has byte planes (ks_l in {1, 2, 4, 8}), two column tiles per product wave, no level padding, no ks_l = 7, the default
+// dynamic-LDS limit, and k_ks_zero over the product kernel's job list before a sliced launch.
+struct KsEngine32 {
+    using Word = uint32_t;
+    using Ctx = helm_hip_ctx;
+    using OutJob = KsJob;
+    using Where = std::nullptr_t;
+    using VectorLevels = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8>;
+    using DigitLevels = std::integer_sequence<int, 1, 2, 4, 8>;
+    static constexpr int CT = 2;
+    static constexpr int padded_levels(int ks_l) { return ks_l; }
+    static auto product_kernel() { return k_ks_mfma; }
+    static bool matrix_path(const Ctx *ctx, const helm_ks::Key<uint32_t> &K, int64_t) { return K.planes && ctx->ks_mfma; }
+    static hipError_t zero_rows(Ctx *ctx, const KsJob *out_jobs, Where, uint32_t *out, int64_t count, int n)
+    {
+        hipLaunchKernelGGL(k_ks_zero, dim3((unsigned)count), dim3(256), 0, ctx->stream, out_jobs, out, n);
         return hipGetLastError();
     }
-    const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((P.n + 1 + 255) / 256);
-    // narrow launches: split the key rows until ~2 workgroups per CU exist (at most 16 slices)
-    int slices = 1;
-    while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)ctx->n_cus && kN / (slices * 2) >= 64) slices *= 2;
-    const int t_chunk = (kN + slices - 1) / slices;
-    dim3 grid(gx, gy, (unsigned)slices);
-    const size_t lds = (size_t)t_chunk * P.ks_l * sizeof(uint32_t);
-    if (slices > 1) {
-        hipLaunchKernelGGL(k_ks_zero, dim3((unsigned)count), dim3(256), 0, ctx->stream, jobs, out, P.n);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-#define KS_CASE(LV)                                                                                       \
-    case LV:                                                                                              \
-        hipLaunchKernelGGL(k_keyswitch<LV>, grid, dim3(256), lds, ctx->stream, jobs, big, ctx->ksk, out, P.n, kN, \
-                           P.ks_logB, (int)count, t_chunk);                                               \
-        break;
-    switch (P.ks_l) {
-        KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) KS_CASE(5) KS_CASE(6) KS_CASE(8)
-    default: return hipErrorInvalidValue;
-    }
-#undef KS_CASE
-    return hipGetLastError();
+    template <typename> static hipError_t allow_lds(Ctx *, const void *) { return hipSuccess; }
+};
+
+static helm_ks::Key<uint32_t> ks_key(const helm_hip_ctx *ctx)
+{
+    const helm_hip_params &P = ctx->P;
+    helm_ks::Key<uint32_t> K;
+    K.key = ctx->ksk;
+    K.planes = ctx->ksk_planes;
+    K.in_dim = P.k * P.N;
+    K.out_dim = P.n;
+    K.l = P.ks_l;
+    K.logB = P.ks_logB;
+    K.kchunks = ctx->ks_kchunks;
+    K.ctiles = ctx->ks_ctiles;
+    return K;
+}
+
+static hipError_t launch_ks(helm_hip_ctx *ctx, const KsJob *jobs, int64_t count, const uint32_t *big, uint32_t *out)
+{
+    return helm_ks::launch<KsEngine32>(
+        ctx, ks_key(ctx), jobs, jobs, count, big, out, nullptr, [](auto lv) { return k_ks_digits<decltype(lv)::value>; },
+        [](auto lv) { return k_keyswitch<decltype(lv)::value>; });
 }
 
 // pbs_order = 1: the level-independent job lists of `count` rows (grown on demand, filled on the context's stream)
@@ -2910,55 +2686,13 @@ static hipError_t ensure_iota_jobs(helm_hip_ctx *ctx, int64_t count)
     return e;
 }
 
-// The front of a keyswitch-first level: launch_ks with the gate's linear combination folded into the read - job i of the
-// level's PbsJob list, over the big wire rows, to row i of `out`.  Same path choice, padding, slices and LDS size.
+// The front of a keyswitch-first level: job i of the level's PbsJob list, over the big wire rows, to row i of `out` (the
+// identity job list names those rows to k_ks_mfma and k_ks_zero).
 static hipError_t launch_ks_gate(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires, uint32_t *out)
 {
-    const helm_hip_params &P = ctx->P;
-    const int kN = P.k * P.N;
-    if (ctx->ksk_planes && ctx->ks_mfma) {
-        const int64_t padded = (count + 63) / 64 * 64;
-        if (ctx->d_dig.ensure((size_t)padded * kN * P.ks_l) || ctx->d_dsum.ensure((size_t)padded) || ctx->d_body.ensure((size_t)padded))
-            return hipErrorOutOfMemory;
-#define KSD_CASE(LV)                                                                                                        \
-    case LV:                                                                                                                \
-        hipLaunchKernelGGL(k_ks_gate_digits<LV>, dim3((unsigned)padded), dim3(256), 0, ctx->stream, jobs, wires, ctx->d_dig.p, \
-                           ctx->d_dsum.p, ctx->d_body.p, kN, P.ks_logB, (int)count, ctx->ks_kchunks);                      \
-        break;
-        switch (P.ks_l) {
-            KSD_CASE(1) KSD_CASE(2) KSD_CASE(4) KSD_CASE(8)
-        default: return hipErrorInvalidValue;
-        }
-#undef KSD_CASE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ks_mfma, dim3((unsigned)(padded / 64), (unsigned)((ctx->ks_ctiles + 1) / 2)), dim3(64), 0, ctx->stream,
-                           ctx->d_ident.p, ctx->d_dig.p, ctx->d_dsum.p, ctx->d_body.p, ctx->ksk_planes, out, P.n, (int)count,
-                           ctx->ks_kchunks, ctx->ks_ctiles);
-        return hipGetLastError();
-    }
-    const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((P.n + 1 + 255) / 256);
-    int slices = 1;
-    while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)ctx->n_cus && kN / (slices * 2) >= 64) slices *= 2;
-    const int t_chunk = (kN + slices - 1) / slices;
-    dim3 grid(gx, gy, (unsigned)slices);
-    const size_t lds = (size_t)t_chunk * P.ks_l * sizeof(uint32_t);
-    if (slices > 1) {
-        hipLaunchKernelGGL(k_ks_zero, dim3((unsigned)count), dim3(256), 0, ctx->stream, ctx->d_ident.p, out, P.n);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-#define KS_CASE(LV)                                                                                                  \
-    case LV:                                                                                                         \
-        hipLaunchKernelGGL(k_keyswitch_gate<LV>, grid, dim3(256), lds, ctx->stream, jobs, wires, ctx->ksk, out, P.n, kN, \
-                           P.ks_logB, (int)count, t_chunk);                                                          \
-        break;
-    switch (P.ks_l) {
-        KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) KS_CASE(5) KS_CASE(6) KS_CASE(8)
-    default: return hipErrorInvalidValue;
-    }
-#undef KS_CASE
-    return hipGetLastError();
+    return helm_ks::launch<KsEngine32>(
+        ctx, ks_key(ctx), jobs, ctx->d_ident.p, count, wires, out, nullptr,
+        [](auto lv) { return k_ks_gate_digits<decltype(lv)::value>; }, [](auto lv) { return k_keyswitch_gate<decltype(lv)::value>; });
 }
 
 // A keyswitch-first level (pbs_order = 1): gate keyswitch from the big wire rows to the small staging, bootstrap of the
@@ -3322,9 +3056,9 @@ int helm_hip_ctx_destroy(helm_hip_ctx *ctx)
     (void)hipFree(ctx->bsk);
     (void)hipFree(ctx->ksk);
     (void)hipFree(ctx->ksk_planes);
-    ctx->d_dig.release();
-    ctx->d_dsum.release();
-    ctx->d_body.release();
+    ctx->d_ksdig.release();
+    ctx->d_ksdsum.release();
+    ctx->d_ksbody.release();
     (void)hipFree(ctx->tv_bool);
     ctx->d_pbs.release();
     ctx->d_ks.release();
@@ -3582,28 +3316,14 @@ int helm_hip_load_keyswitch_key(helm_hip_ctx *ctx, const uint32_t *ksk, size_t n
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     // byte planes for the matrix-core keyswitch: ks_l must divide 16 (a lane's 16 fragment bytes hold whole words'
     // digits), the rows must fill 64-row chunks, digits must fit a signed byte (ks_logB <= 7: checked at ctx_create)
-    const int R = P.k * P.N * P.ks_l;
-    if ((P.ks_l == 1 || P.ks_l == 2 || P.ks_l == 4 || P.ks_l == 8) && R % 64 == 0) {
-        const int kchunks = R / 64, ctiles = (P.n + 1 + 15) / 16;
-        const size_t frag_per_plane = (size_t)ctiles * kchunks * 64;
-        std::vector<int8_t> planes(4 * frag_per_plane * 16);
-        const size_t krow = (size_t)P.n + 1;
-        for (int ct = 0; ct < ctiles; ct++)
-            for (int kc = 0; kc < kchunks; kc++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int c = ct * 16 + (lane & 15);
-                    for (int j = 0; j < 16; j++) {
-                        const int r = kc * 64 + 16 * (lane >> 4) + j;
-                        const uint32_t w = c <= P.n ? ksk[(size_t)r * krow + c] : 0u;
-                        for (int b = 0; b < 4; b++)
-                            planes[((size_t)b * frag_per_plane + ((size_t)ct * kchunks + kc) * 64 + lane) * 16 + j] =
-                                (int8_t)((int)((w >> (8 * b)) & 255u) - 128);
-                    }
-                }
-        if (!ctx->ksk_planes) HIP_TRY(hipMalloc(&ctx->ksk_planes, planes.size()));
-        HIP_TRY(hipMemcpy(ctx->ksk_planes, planes.data(), planes.size(), hipMemcpyHostToDevice));
-        ctx->ks_kchunks = kchunks;
-        ctx->ks_ctiles = ctiles;
+    if (P.ks_l == 1 || P.ks_l == 2 || P.ks_l == 4 || P.ks_l == 8) {
+        const helm_ks::Planes planes = helm_ks::build_planes(ksk, P.k * P.N, P.ks_l, P.ks_l, P.n);
+        if (!planes.bytes.empty()) {
+            if (!ctx->ksk_planes) HIP_TRY(hipMalloc(&ctx->ksk_planes, planes.bytes.size()));
+            HIP_TRY(hipMemcpy(ctx->ksk_planes, planes.bytes.data(), planes.bytes.size(), hipMemcpyHostToDevice));
+            ctx->ks_kchunks = planes.kchunks;
+            ctx->ks_ctiles = planes.ctiles;
+        }
     }
     ctx->have_ksk = true;
     return 0;

@@ -18,6 +18,7 @@
 #include "../../include/helm_comm.h"
 #include "ntt_fp64.h"
 #include "many_lut_rule.h"
+#include "keyswitch.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -1245,136 +1246,36 @@ __global__ __launch_bounds__(64) void k_bsk_convert64s(const uint64_t *__restric
 }
 
 // ------------------------------------------------------------------------------------
-// k_keyswitch64: as k_keyswitch of helm_hip.hip, 64-bit words.  Grid (ceil(jobs/4),
-// column chunks of 256); digits of four ciphertexts packed as 4 x int8 per LDS word.
-//   out[c] = (c == n ? body : 0) - sum_t sum_j digit(t,j) * KSK[t][j][c]
+// The keyswitch kernels, big LWE (k*N) -> small LWE (n): wrappers over the bodies of keyswitch.h for Ks64Job rows.
+//   k_keyswitch64                     vector-ALU form, four ciphertexts per key pass
+//   k_ks64_digits / k_ks64_mfma       matrix-core form: the level count padded to LP in {1, 2, 4, 8}, the key's EIGHT byte
+//                                     planes; one wave = 64 ciphertexts x 16 key columns x 8 planes (128 accumulator registers)
 // ------------------------------------------------------------------------------------
+struct Ks64Rows {
+    using Job = Ks64Job;
+    using Word = uint64_t;
+    const uint64_t *in;
+    __device__ __forceinline__ Ks64Rows(const Ks64Job &job, const uint64_t *big, size_t row) : in(big + row * (size_t)job.in_row) {}
+    __device__ __forceinline__ uint64_t word(int t) const { return in[t]; }
+    __device__ __forceinline__ uint64_t body(int kN) const { return in[kN]; }
+    static __device__ __forceinline__ int out_row(const Ks64Job &job, int) { return job.out_row; }
+};
+constexpr int ks64_padded_levels(int ks_l) { return ks_l <= 1 ? 1 : ks_l <= 2 ? 2 : ks_l <= 4 ? 4 : 8; }
+
 template <int KSL>
 __global__ __launch_bounds__(256) void k_keyswitch64(const Ks64Job *__restrict__ jobs, const uint64_t *__restrict__ big,
                                                      const uint64_t *__restrict__ ksk, uint64_t *__restrict__ out,
                                                      int n, int kN, int logB, int count, int t_chunk)
 {
-    // blockIdx.z: slice of t_chunk input coefficients (see k_keyswitch of helm_hip.hip); with more
-    // than one slice the partial sums meet in `out` (zeroed beforehand) by 64-bit atomic add
-    constexpr int GN = 4;
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *DIG = reinterpret_cast<uint32_t *>(smem); // [t_chunk * KSL]
-    const int g0 = blockIdx.x * GN;
-    const int ng = min(GN, count - g0);
-    const int t0 = blockIdx.z * t_chunk, t1 = min(kN, t0 + t_chunk);
-    Ks64Job job[GN];
-#pragma unroll
-    for (int g = 0; g < GN; g++) job[g] = jobs[g0 + (g < ng ? g : 0)];
-    const size_t brow = (size_t)kN + 1;
-    const int rep = logB * KSL;
-    const uint64_t mask = (1ull << logB) - 1ull;
-    for (int t = t0 + threadIdx.x; t < t1; t += 256) {
-        uint32_t packed[KSL];
-#pragma unroll
-        for (int j = 0; j < KSL; j++) packed[j] = 0;
-#pragma unroll
-        for (int g = 0; g < GN; g++) {
-            if (g < ng) {
-                const uint64_t v = big[brow * (size_t)job[g].in_row + t];
-                uint64_t state = (v + (1ull << (63 - rep))) >> (64 - rep);
-#pragma unroll
-                for (int lev = KSL - 1; lev >= 0; lev--) {
-                    const uint64_t d = state & mask;
-                    state >>= logB;
-                    const uint64_t carry = (((d - 1ull) | state) & d) >> (logB - 1);
-                    state += carry;
-                    const int dig = (int)(uint32_t)d - (int)((uint32_t)carry << logB);
-                    packed[lev] |= ((uint32_t)dig & 0xFFu) << (8 * g);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KSL; j++) DIG[(t - t0) * KSL + j] = packed[j];
-    }
-    __syncthreads();
-    const int c = blockIdx.y * 256 + threadIdx.x;
-    if (c > n) return;
-    const size_t krow = (size_t)n + 1;
-    uint64_t acc[GN] = {0, 0, 0, 0};
-    const uint64_t *kp = ksk + (size_t)t0 * KSL * krow + c;
-    const int rows = (t1 - t0) * KSL;
-#pragma unroll 4
-    for (int r = 0; r < rows; r++) {
-        const uint64_t kw = kp[(size_t)r * krow];
-        const uint32_t pk = DIG[r];
-#pragma unroll
-        for (int g = 0; g < GN; g++) acc[g] += (uint64_t)(int64_t)(int32_t)__builtin_amdgcn_sbfe(pk, 8 * g, 8) * kw;
-    }
-#pragma unroll
-    for (int g = 0; g < GN; g++) {
-        if (g < ng) {
-            const uint64_t body = (c == n && blockIdx.z == 0) ? big[brow * (size_t)job[g].in_row + kN] : 0ull;
-            uint64_t *dst = out + krow * (size_t)job[g].out_row + c;
-            if (gridDim.z == 1) *dst = body - acc[g];
-            else atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)(body - acc[g]));
-        }
-    }
+    helm_ks::vector_body<KSL, Ks64Rows>(jobs, big, ksk, out, n, kN, logB, count, t_chunk);
 }
-
-// ------------------------------------------------------------------------------------
-// Keyswitch on the matrix cores (as k_ks_digits / k_ks_mfma of helm_hip.hip, 64-bit words): the key's EIGHT
-// byte planes as signed bytes (K_b - 128), the level count padded to LP in {1, 2, 4, 8} (a lane's 16 fragment
-// bytes hold whole words' digits; padded levels carry zero digits), int32 accumulators per plane, exact:
-//   sum_r d K = sum_b 2^(8b) sum_r d (K_b - 128) + 0x8080808080808080 * sum_r d      (mod 2^64)
-// One wave = 64 ciphertexts x 16 key columns x 8 planes (128 accumulator registers).
-// ------------------------------------------------------------------------------------
-typedef int v4i64k __attribute__((ext_vector_type(4)));
 
 template <int KSL>
 __global__ __launch_bounds__(256) void k_ks64_digits(const Ks64Job *__restrict__ jobs, const uint64_t *__restrict__ big,
                                                      int8_t *__restrict__ dig, int32_t *__restrict__ dsum,
                                                      uint64_t *__restrict__ body, int kN, int logB, int count, int kchunks)
 {
-    constexpr int LP = KSL <= 1 ? 1 : KSL <= 2 ? 2 : KSL <= 4 ? 4 : 8;
-    const int g = blockIdx.x; // padded index; g >= count: an all-zero row
-    __shared__ int red[256];
-    int local = 0;
-    const size_t brow = (size_t)kN + 1;
-    const bool live = g < count;
-    Ks64Job job{};
-    if (live) job = jobs[g];
-    int8_t *tile = dig + (size_t)(g >> 4) * kchunks * 1024;
-    const int rep = logB * KSL;
-    const uint64_t mask = (1ull << logB) - 1ull;
-    for (int t = threadIdx.x; t < kN; t += 256) {
-        int d[LP];
-#pragma unroll
-        for (int j = 0; j < LP; j++) d[j] = 0;
-        if (live) {
-            const uint64_t v = big[brow * (size_t)job.in_row + t];
-            uint64_t state = (v + (1ull << (63 - rep))) >> (64 - rep);
-#pragma unroll
-            for (int lev = KSL - 1; lev >= 0; lev--) {
-                const uint64_t dd = state & mask;
-                state >>= logB;
-                const uint64_t carry = (((dd - 1ull) | state) & dd) >> (logB - 1);
-                state += carry;
-                d[lev] = (int)(uint32_t)dd - (int)((uint32_t)carry << logB);
-            }
-        }
-        const int r0 = t * LP, kc = r0 >> 6, kq = (r0 & 63) >> 4, j0 = r0 & 15;
-        int8_t *dst = tile + ((size_t)kc * 64 + (kq << 4 | (g & 15))) * 16 + j0;
-#pragma unroll
-        for (int j = 0; j < LP; j++) {
-            dst[j] = (int8_t)d[j];
-            local += d[j];
-        }
-    }
-    red[threadIdx.x] = local;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        dsum[g] = red[0];
-        body[g] = live ? big[brow * (size_t)job.in_row + kN] : 0ull;
-    }
+    helm_ks::digits_body<KSL, ks64_padded_levels(KSL), Ks64Rows>(jobs, big, dig, dsum, body, kN, logB, count, kchunks);
 }
 
 __global__ __launch_bounds__(64) void k_ks64_mfma(const Ks64Job *__restrict__ jobs, const int8_t *__restrict__ dig,
@@ -1382,41 +1283,7 @@ __global__ __launch_bounds__(64) void k_ks64_mfma(const Ks64Job *__restrict__ jo
                                                   const int8_t *__restrict__ kplanes, uint64_t *__restrict__ out, int n,
                                                   int count, int kchunks, int ctiles)
 {
-    constexpr int GT = 4; // gate tiles of 16 per wave; one column tile of 16; eight byte planes
-    const int lane = threadIdx.x;
-    const int gt0 = blockIdx.x * GT, ct = blockIdx.y;
-    const v4i64k *A = reinterpret_cast<const v4i64k *>(dig) + (size_t)gt0 * kchunks * 64 + lane;
-    const v4i64k *B = reinterpret_cast<const v4i64k *>(kplanes) + (size_t)ct * kchunks * 64 + lane;
-    const size_t plane = (size_t)ctiles * kchunks * 64;
-    v4i64k acc[GT][8];
-#pragma unroll
-    for (int a = 0; a < GT; a++)
-#pragma unroll
-        for (int b = 0; b < 8; b++) acc[a][b] = v4i64k{0, 0, 0, 0};
-    for (int kc = 0; kc < kchunks; kc++) {
-        v4i64k fa[GT], fb[8];
-#pragma unroll
-        for (int a = 0; a < GT; a++) fa[a] = A[((size_t)a * kchunks + kc) * 64];
-#pragma unroll
-        for (int b = 0; b < 8; b++) fb[b] = B[(size_t)b * plane + (size_t)kc * 64];
-#pragma unroll
-        for (int a = 0; a < GT; a++)
-#pragma unroll
-            for (int b = 0; b < 8; b++) acc[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[a], fb[b], acc[a][b], 0, 0, 0);
-    }
-    const size_t krow = (size_t)n + 1;
-    const int col = ct * 16 + (lane & 15);
-#pragma unroll
-    for (int a = 0; a < GT; a++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) {
-            const int g = (gt0 + a) * 16 + (lane >> 4) * 4 + reg; // C/D map: column = lane & 15, row = (lane >> 4) * 4 + reg
-            if (g >= count || col > n) continue;
-            uint64_t s = 0x8080808080808080ull * (uint64_t)(int64_t)dsum[g];
-#pragma unroll
-            for (int b = 0; b < 8; b++) s += (uint64_t)(int64_t)acc[a][b][reg] << (8 * b);
-            out[krow * (size_t)jobs[g].out_row + col] = (col == n ? body[g] : 0ull) - s;
-        }
+    helm_ks::product_body<1, Ks64Rows>(jobs, dig, dsum, body, kplanes, out, n, count, kchunks, ctiles);
 }
 
 // out row = sum coef * in rows + const (body only).  One workgroup per output row.
@@ -1918,11 +1785,7 @@ hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, c
 
 // A keyswitching key on the device: in_dim input words (+ body) -> out_dim mask words + body.  The context's own
 // key (big -> small) and the WoP-PBS path's extra keys go through the same kernels.
-struct KsKey {
-    const uint64_t *key = nullptr; // [in_dim][l][out_dim+1]
-    const int8_t *planes = nullptr; // byte planes for the matrix-core kernel, or null
-    int in_dim = 0, out_dim = 0, l = 0, logB = 0, kchunks = 0, ctiles = 0;
-};
+using KsKey = helm_ks::Key<uint64_t>;
 
 // Where the output rows of a keyswitch launch lie, for the sliced vector-ALU form, whose partial sums meet in rows zeroed
 // beforehand.  Without one the jobs write rows 0 .. count-1 of `out` (every order-1 launch).  The order-0 launches write
@@ -1934,69 +1797,48 @@ struct KsOutRows {
     const int32_t *rows = nullptr, *none = nullptr;
 };
 
-hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs, int64_t count, const uint64_t *big,
-                           uint64_t *out, const KsOutRows *where = nullptr)
-{
-    // `out`: rows of out_dim+1 words (job g writes row jobs[g].out_row)
-    struct { int n, ks_l, ks_logB; } P{K.out_dim, K.l, K.logB};
-    const int kN = K.in_dim;
+// What the 64-bit engine's keyswitch launches have of their own (helm_ks::launch): every ks_l in 1..8 with the level count
+// padded to 1, 2, 4 or 8 on the matrix cores, one column tile per product wave, the 160 KiB dynamic-LDS limit on the vector
+// kernels (an unsliced digit buffer is up to 128 KiB at in_dim = 4096), and output rows named by KsOutRows.
+struct KsEngine64 {
+    using Word = uint64_t;
+    using Ctx = helm_si_ctx;
+    using OutJob = Ks64Job;
+    using Where = const KsOutRows *;
+    using VectorLevels = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;
+    using DigitLevels = VectorLevels;
+    static constexpr int CT = 1;
+    static constexpr int padded_levels(int ks_l) { return ks64_padded_levels(ks_l); }
+    static auto product_kernel() { return k_ks64_mfma; }
     // narrow batches stay on the vector-ALU kernel, whose key rows are split over workgroup slices: a matrix-core
     // wave walks the whole key column by column tile (0.23 ms whatever the width; vector ALU: 0.11 ms for 64, 0.37 ms
     // for 256 ciphertexts under PARAM_MESSAGE_2_CARRY_2)
-    if (K.planes && ctx->keys->ks_mfma && count >= 160) {
-        const int64_t padded = (count + 63) / 64 * 64;
-        const int LP = P.ks_l <= 1 ? 1 : P.ks_l <= 2 ? 2 : P.ks_l <= 4 ? 4 : 8;
-        if (ctx->d_ksdig.ensure((size_t)padded * kN * LP) || ctx->d_ksdsum.ensure((size_t)padded) || ctx->d_ksbody.ensure((size_t)padded))
-            return hipErrorOutOfMemory;
-#define KSD_CASE(LV)                                                                                                  \
-    case LV:                                                                                                          \
-        hipLaunchKernelGGL(k_ks64_digits<LV>, dim3((unsigned)padded), dim3(256), 0, ctx->stream, jobs, big, ctx->d_ksdig.p, \
-                           ctx->d_ksdsum.p, ctx->d_ksbody.p, kN, P.ks_logB, (int)count, K.kchunks);                 \
-        break;
-        switch (P.ks_l) {
-            KSD_CASE(1) KSD_CASE(2) KSD_CASE(3) KSD_CASE(4) KSD_CASE(5) KSD_CASE(6) KSD_CASE(7) KSD_CASE(8)
-        default: return hipErrorInvalidValue;
+    static bool matrix_path(const Ctx *ctx, const KsKey &K, int64_t count) { return K.planes && ctx->keys->ks_mfma && count >= 160; }
+    static hipError_t zero_rows(Ctx *ctx, const Ks64Job *, Where where, uint64_t *out, int64_t count, int n)
+    {
+        if (where && where->rows) {
+            hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, out, where->none, out, where->rows, n);
+            return hipGetLastError();
         }
-#undef KSD_CASE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ks64_mfma, dim3((unsigned)(padded / 64), (unsigned)K.ctiles), dim3(64), 0, ctx->stream, jobs,
-                           ctx->d_ksdig.p, ctx->d_ksdsum.p, ctx->d_ksbody.p, K.planes, out, P.n, (int)count,
-                           K.kchunks, K.ctiles);
-        return hipGetLastError();
+        return hipMemsetAsync(out, 0, (size_t)(where ? where->dense : count) * ((size_t)n + 1) * sizeof(uint64_t), ctx->stream);
     }
-    const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((P.n + 1 + 255) / 256);
-    int slices = 1;
-    while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)ctx->n_cus && kN / (slices * 2) >= 64) slices *= 2;
-    const int t_chunk = (kN + slices - 1) / slices;
-    dim3 grid(gx, gy, (unsigned)slices);
-    const size_t lds = (size_t)t_chunk * P.ks_l * sizeof(uint32_t);
-    if (slices > 1 && where && where->rows) {
-        hipLaunchKernelGGL(k_rows64, dim3((unsigned)count), dim3(256), 0, ctx->stream, out, where->none, out, where->rows, P.n);
-        if (hipError_t e = hipGetLastError()) return e;
-    } else if (slices > 1) {
-        hipError_t e = hipMemsetAsync(out, 0, (size_t)(where ? where->dense : count) * ((size_t)P.n + 1) * sizeof(uint64_t), ctx->stream);
-        if (e != hipSuccess) return e;
+    template <typename> static hipError_t allow_lds(Ctx *ctx, const void *kernel)
+    {
+        static bool done[64] = {false}; // per kernel and device: the attribute belongs to the device's code object
+        if (done[ctx->device & 63]) return hipSuccess;
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        done[ctx->device & 63] = e == hipSuccess;
+        return e;
     }
-#define KS_CASE(LV)                                                                                                 \
-    case LV: {                                                                                                      \
-        static bool done[64] = {false}; /* per device: the attribute belongs to the device's code object */         \
-        if (!done[ctx->device & 63]) {                                                                              \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_keyswitch64<LV>),                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);             \
-            if (e != hipSuccess) return e;                                                                          \
-            done[ctx->device & 63] = true;                                                                          \
-        }                                                                                                           \
-        hipLaunchKernelGGL(k_keyswitch64<LV>, grid, dim3(256), lds, ctx->stream, jobs, big, K.key, out, P.n, kN,   \
-                           P.ks_logB, (int)count, t_chunk);                                                         \
-        break;                                                                                                      \
-    }
-    switch (P.ks_l) {
-        KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) KS_CASE(5) KS_CASE(6) KS_CASE(7) KS_CASE(8)
-    default: return hipErrorInvalidValue;
-    }
-#undef KS_CASE
-    return hipGetLastError();
+};
+
+// `out`: rows of out_dim+1 words (job g writes row jobs[g].out_row)
+hipError_t launch_ks64_key(helm_si_ctx *ctx, const KsKey &K, const Ks64Job *jobs, int64_t count, const uint64_t *big,
+                           uint64_t *out, const KsOutRows *where = nullptr)
+{
+    return helm_ks::launch<KsEngine64>(
+        ctx, K, jobs, jobs, count, big, out, where, [](auto lv) { return k_ks64_digits<decltype(lv)::value>; },
+        [](auto lv) { return k_keyswitch64<decltype(lv)::value>; });
 }
 
 hipError_t launch_ks64(helm_si_ctx *ctx, const Ks64Job *jobs, int64_t count, const uint64_t *big, uint64_t *out,
@@ -3041,31 +2883,12 @@ int helm_si_load_keyswitch_key(helm_si_ctx *ctx, const uint64_t *ksk, size_t n_w
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     {
         // byte planes for the matrix-core keyswitch (levels padded to LP: the padding rows pair zero digits with -128)
-        const int LP = P.ks_l <= 1 ? 1 : P.ks_l <= 2 ? 2 : P.ks_l <= 4 ? 4 : 8;
-        const int R = P.k * P.N * LP;
-        if (R % 64 == 0) {
-            const int kchunks = R / 64, ctiles = (P.n + 1 + 15) / 16;
-            const size_t frag_per_plane = (size_t)ctiles * kchunks * 64;
-            std::vector<int8_t> planes(8 * frag_per_plane * 16, (int8_t)-128);
-            const size_t krow = (size_t)P.n + 1;
-            for (int ct = 0; ct < ctiles; ct++)
-                for (int kc = 0; kc < kchunks; kc++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int c = ct * 16 + (lane & 15);
-                        if (c > P.n) continue;
-                        for (int j = 0; j < 16; j++) {
-                            const int r = kc * 64 + 16 * (lane >> 4) + j, t = r / LP, lev = r % LP;
-                            if (lev >= P.ks_l) continue;
-                            const uint64_t w = ksk[((size_t)t * P.ks_l + lev) * krow + c];
-                            for (int b = 0; b < 8; b++)
-                                planes[((size_t)b * frag_per_plane + ((size_t)ct * kchunks + kc) * 64 + lane) * 16 + j] =
-                                    (int8_t)((int)((w >> (8 * b)) & 255u) - 128);
-                        }
-                    }
-            if (!K.ksk_planes) HIP_TRY(hipMalloc(&K.ksk_planes, planes.size()));
-            HIP_TRY(hipMemcpy(K.ksk_planes, planes.data(), planes.size(), hipMemcpyHostToDevice));
-            K.ks_kchunks = kchunks;
-            K.ks_ctiles = ctiles;
+        const helm_ks::Planes planes = helm_ks::build_planes(ksk, P.k * P.N, P.ks_l, ks64_padded_levels(P.ks_l), P.n);
+        if (!planes.bytes.empty()) {
+            if (!K.ksk_planes) HIP_TRY(hipMalloc(&K.ksk_planes, planes.bytes.size()));
+            HIP_TRY(hipMemcpy(K.ksk_planes, planes.bytes.data(), planes.bytes.size(), hipMemcpyHostToDevice));
+            K.ks_kchunks = planes.kchunks;
+            K.ks_ctiles = planes.ctiles;
         }
     }
     K.have_ksk = true;

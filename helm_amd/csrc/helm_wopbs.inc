@@ -64,26 +64,13 @@ __global__ __launch_bounds__(256) void k_pfpks64(const PfJob *__restrict__ jobs,
     PfJob job[GN];
 #pragma unroll
     for (int g = 0; g < GN; g++) job[g] = jobs[g0 + (g < ng ? g : 0)];
-    const int rep = logB * L;
-    const uint64_t mask = (1ull << logB) - 1ull;
     for (int t = t0 + threadIdx.x; t < t1; t += 256) {
 #pragma unroll
         for (int g = 0; g < GN; g++) {
-            int32_t d[L];
+            int d[L];
 #pragma unroll
             for (int j = 0; j < L; j++) d[j] = 0;
-            if (g < ng) {
-                const uint64_t v = big[(size_t)in_words * (size_t)job[g].in_row + t];
-                uint64_t state = (v + (1ull << (63 - rep))) >> (64 - rep);
-#pragma unroll
-                for (int lev = L - 1; lev >= 0; lev--) {
-                    const uint64_t dd = state & mask;
-                    state >>= logB;
-                    const uint64_t carry = (((dd - 1ull) | state) & dd) >> (logB - 1);
-                    state += carry;
-                    d[lev] = (int32_t)(uint32_t)dd - (int32_t)((uint32_t)carry << logB);
-                }
-            }
+            if (g < ng) helm_ks::ks_decompose<L>(big[(size_t)in_words * (size_t)job[g].in_row + t], logB, d);
 #pragma unroll
             for (int j = 0; j < L; j++) DIG[((t - t0) * L + j) * GN + g] = d[j];
         }
@@ -137,25 +124,14 @@ __global__ __launch_bounds__(256) void k_pfpks_digits(const PfJob *__restrict__ 
     PfJob job{};
     if (live) job = jobs[g];
     int8_t *tile = dig + (size_t)(g >> 4) * kchunks * 1024;
-    const int rep = logB * L;
-    const uint64_t mask = (1ull << logB) - 1ull;
     const int padded_words = kchunks * 64 / LP;
     for (int t = threadIdx.x; t < padded_words; t += 256) {
         int8_t b[LP];
 #pragma unroll
         for (int j = 0; j < LP; j++) b[j] = 0;
         if (live && t < in_words) {
-            const uint64_t v = big[(size_t)in_words * (size_t)job.in_row + t];
-            uint64_t state = (v + (1ull << (63 - rep))) >> (64 - rep);
             int d[L];
-#pragma unroll
-            for (int lev = L - 1; lev >= 0; lev--) {
-                const uint64_t dd = state & mask;
-                state >>= logB;
-                const uint64_t carry = (((dd - 1ull) | state) & dd) >> (logB - 1);
-                state += carry;
-                d[lev] = (int)(uint32_t)dd - (int)((uint32_t)carry << logB);
-            }
+            helm_ks::ks_decompose<L>(big[(size_t)in_words * (size_t)job.in_row + t], logB, d);
 #pragma unroll
             for (int lev = 0; lev < L; lev++) {
                 const int lo = ((d[lev] + 128) & 255) - 128, hi = (d[lev] - lo) >> 8;

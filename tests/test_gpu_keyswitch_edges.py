@@ -95,7 +95,8 @@ def _oracle_rows(width, p, key, rows):
 
 
 def route(width, kN, l, count, mfma_env):
-    """The kernel pair the launchers' rules give a launch - launch_ks and launch_ks64_key restated, since the ABI does not
+    """The kernel pair the launchers' rules give a launch - KsEngine32::matrix_path (helm_hip.hip) and
+    KsEngine64::matrix_path (helm_shortint.hip), with the loaders' conditions for byte planes, restated, since the ABI does not
     report the kernel that ran.  The assertion against a case's expected routes therefore checks this model, not the
     device: should the launchers' rules change without it, the unset and the = 0 run of a case could take the same kernel
     unnoticed.  What the device shows is that the two runs, and the integer reference, agree word for word."""
