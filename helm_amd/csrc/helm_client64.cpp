@@ -141,6 +141,31 @@ int helm_si_client_named_params(const char *name, helm_si_params *p, double *lwe
         p->carry_modulus = 8;
         *lwe_std = 1e-9;
         *glwe_std = 1e-17;
+    } else if (s == "shortint_m3c3") {
+        // A 6-bit set, message_modulus 8 x carry_modulus 8 (tfhe's PARAM_MESSAGE_3_CARRY_3_KS_PBS): k = 1, N = 8192, PBS 15 x 2
+        // (two levels of 15 bits), KS 3 x 6 (six levels of 3 bits), n = 864 [all recalled, none checked against tfhe's source:
+        // an approximate set, like shortint_m2c3.  The LWE noise is not recalled: it is taken on tfhe's security line through
+        // its n = 684 (2.04e-5) and n = 742 (7.07e-6) sets, log2 sigma = -15.58 - 0.02643 (n - 684) = -20.34, 7.55e-7; the
+        // GLWE noise is tfhe's value for N >= 4096, recalled as 2^-62 = 2.168e-19.
+        // By the formulas of tests/test_gpu_noise.py (variances, torus units): blind rotation 2^-42.8 (the decomposition's
+        // rounding; the key's noise through the digits is 2^-72.8), keyswitch 2^-22.6 (the key's noise through the digits; the
+        // rounding term is 2^-27.6), modulus switch (1 + n/2) / (48 N^2) = 2^-22.8.  Half a box is 1 / (4 t) = 2^-8 at t = 64.
+        // Failure probability per look-up (variance weight x blind rotation + keyswitch + modulus switch: wires are big rows,
+        // the operand is packed on them and keyswitched ONCE): 2^-40.7 on one look-up output or a fresh encryption (sigma
+        // 2^-10.85: 7.2 standard deviations), and 2^-40.7 as well on a 6-input operand 32x + 16y + 8z + 4u + 2v + w of six
+        // look-up outputs - the weight 1365 raises the blind rotation's term to 2^-32.4 only, far below the keyswitch and the
+        // modulus switch, so a chain of 6-input gates costs no margin in this order.  (Under HELM_SI_CREATE_PBS_KS wires are
+        // keyswitched rows and the keyswitch term would be weighted too: 1365 x 2^-22.6, which fails; this set is the KS_PBS
+        // one.)  These are predictions of the formulas, not measured here]
+        p->n = 864; p->N = 8192; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 6; p->ks_logB = 3;
+        p->message_modulus = 8; p->carry_modulus = 8;
+        *lwe_std = 0.000000755;
+        *glwe_std = 0.0000000000000000002168404344971009;
+    } else if (s == "si_toy_8192") { // shortint_m3c3's shape at toy size (oracle-sized): 64 plaintext values
+        p->n = 12; p->N = 8192; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 3; p->ks_logB = 5;
+        p->message_modulus = 8; p->carry_modulus = 8;
+        *lwe_std = 1e-9;
+        *glwe_std = 1e-17;
     } else if (s == "si_toy_512") {
         p->n = 12; p->N = 512; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 4; p->ks_logB = 4;
         *lwe_std = 1e-9;

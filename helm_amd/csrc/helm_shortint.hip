@@ -1399,7 +1399,8 @@ struct SiKeyState {
     double n_inv[2] = {0, 0}, two32[2] = {0, 0};
     double p0inv_mod_p1 = 0;
     int pair = 0;                // CRT pair of the tables above: 0 = FpG / FpG2 (49 bits), 1 = FpJ / FpJ2 (46 bits: k_pbs64k contexts
-                                 // whose loaded key fits, helm_si_load_bootstrap_key), 2 = FpG / FpI (k_pbs64_large: N = 4096)
+                                 // whose loaded key fits, helm_si_load_bootstrap_key), 2 = FpG / FpI (k_pbs64_large: N = 4096,
+                                 // k_pbs64_n8192: N = 8192)
     double *bsk = nullptr;
     double *bsk_split = nullptr; // layout of k_pbs64s (N >= 1024, pbs_l = 1)
     double *tw_sub = nullptr;    // derived half-transform tables [2 fields][2 halves][N/2]
@@ -1420,6 +1421,10 @@ struct SiKeyState {
     bool large = false;
     size_t large_lds = 0;                 // LDS bytes per workgroup (Large64Lds)
     int large_per_cu = 1;                 // resident workgroups per CU
+    // helm_si_ctx_create_ex under HELM_SI_CREATE_N8192 at N = 8192: k_pbs64_n8192 runs every bootstrap launch, in the same pair
+    // and key layout as the large-N class (k_bsk_convert64_n8192), one workgroup per CU
+    bool n8192 = false;
+    size_t n8192_lds = 0;                 // LDS bytes per workgroup (N8192Lds)
     uint64_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: eight byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0, ks_mfma = 1; // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
@@ -1462,6 +1467,10 @@ struct helm_si_ctx {
     DevBuf<uint64_t> d_small, d_luts, d_stage, d_body;
     DevBuf<int32_t> d_idx, d_idx2;
     DevBuf<int64_t> d_coef;
+    // k_pbs64_n8192: the accumulator rows of this context's launches, [n_cus][2][N] words, allocated when the context is made
+    // (alloc_acc8192).  A lane has its own (it launches on its own stream); launches of one context follow each other on its
+    // stream, so they share the rows.
+    uint64_t *d_acc8192 = nullptr;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pbs, ev_ks, ev_lin;
     helm_si_timing tacc{};
@@ -1708,6 +1717,33 @@ hipError_t launch_pbs64_large(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
     return hipGetLastError();
 }
 
+// k_pbs64_n8192: k = 1, N = 8192 (helm_si_ctx_create_ex with HELM_SI_CREATE_N8192)
+#include "helm_pbs64_n8192.inc"
+
+// The kernel's accumulator rows are indexed by blockIdx.x, so a launch is at most as wide as the context's row buffer: one
+// round (a workgroup per CU).  A wider batch goes out in chunks of a round, one after the other on the context's stream.
+hipError_t launch_pbs64_n8192(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                              const uint64_t *luts, uint64_t *out, int *per_cu)
+{
+    // (the dynamic LDS attribute is set by helm_si_ctx_create_ex: setup_n8192)
+    const SiKeyState &K = *ctx->keys;
+    if (per_cu) {
+        *per_cu = 1;
+        return hipSuccess;
+    }
+    if (ctx->logN != N8192_LOGN || ctx->P.k != 1) return hipErrorInvalidValue;
+    const int64_t rows = std::max(ctx->n_cus, 1); // (the rows of d_acc8192: alloc_acc8192)
+    if (!ctx->d_acc8192) return hipErrorInvalidValue;
+    for (int64_t off = 0; off < count; off += rows) {
+        const int64_t chunk = std::min(rows, count - off);
+        hipLaunchKernelGGL(k_pbs64_n8192, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds, ctx->stream, jobs + off, small,
+                           luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], out, ctx->d_acc8192, ctx->P.n, ctx->P.pbs_l,
+                           ctx->P.pbs_logB, K.p0inv_mod_p1);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 template <int LOGN, int GG>
 hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                                   const uint64_t *luts, uint64_t *out)
@@ -1763,6 +1799,7 @@ const void *pbs64_generic_kernel(int logN, int group)
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                         const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
+    if (ctx->keys->n8192) return launch_pbs64_n8192(ctx, jobs, count, small, luts, out, per_cu);
     if (ctx->keys->large) return launch_pbs64_large(ctx, jobs, count, small, luts, out, per_cu);
     if (ctx->keys->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
     const helm_si_params &P = ctx->P;
@@ -2433,6 +2470,64 @@ int setup_large(helm_si_ctx *ctx)
 #endif
 }
 
+// the shapes k_pbs64_n8192 takes (helm_si_ctx_create_ex with HELM_SI_CREATE_N8192): k = 1, N = 8192, classical blind rotation
+bool si_n8192_domain(const helm_si_params &P)
+{
+    return P.k == 1 && P.N == 8192 && P.pbs_l >= 1 && P.grouping_factor <= 1;
+}
+
+// The accumulator rows of a context (primary or lane) whose launches run k_pbs64_n8192: one row of 2 N words per CU, the
+// width of a launch chunk (launch_pbs64_n8192).  Made with the context, never resized.
+int alloc_acc8192(helm_si_ctx *ctx)
+{
+    const size_t words = (size_t)std::max(ctx->n_cus, 1) * ((size_t)2 << N8192_LOGN);
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_acc8192), words * sizeof(uint64_t)));
+    return 0;
+}
+
+// A context whose launches run k_pbs64_n8192: the inverse twiddle tables of the pair FpG / FpI and the dynamic-LDS limits of
+// the kernel and of its key conversion.
+int setup_n8192(helm_si_ctx *ctx)
+{
+#ifdef HELM_CHECK_BOUNDS
+    // as setup_large: the bound-checking build runs the tuned kernels only, and refuses before anything is launched
+    (void)ctx;
+    return fail(HELM_ERR_STATE, "the N = 8192 kernel is not available in the bound-checking build (libhelm_hip_check.so): "
+                                "use the regular library for HELM_SI_CREATE_N8192 contexts");
+#else
+    SiKeyState &K = *ctx->keys;
+    const helm_si_params &P = ctx->P;
+    const int N = P.N, logN = ctx->logN;
+    for (int f = 0; f < 2; f++) {
+        const uint64_t p = si_modulus(2, f);
+        std::vector<double> ti(N);
+        power_table(ti.data(), powmod_u64(si_psi(N, 2, f), p - 2, p), p, N, logN);
+        if (!K.twi[f]) HIP_TRY(hipMalloc(&K.twi[f], sizeof(double) * N));
+        HIP_TRY(hipMemcpy(K.twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    // the attributes are the kernels', shared by every context of the process: the layout at the largest n
+    static std::atomic<bool> attr_done[64], conv_done[64];
+    const void *kern = reinterpret_cast<const void *>(k_pbs64_n8192);
+    HIP_TRY(lds_attr_once(attr_done, ctx->device, {kern}, N8192Lds(1024).bytes));
+    HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_n8192)},
+                          sizeof(double) * 2 * (size_t)N));
+    K.n8192_lds = N8192Lds(P.n).bytes;
+    int nb = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, L64_THREADS, K.n8192_lds));
+    if (nb < 1)
+        return fail(HELM_ERR_INVALID, "k_pbs64_n8192: no workgroup of " + std::to_string(K.n8192_lds) + " B LDS fits a CU");
+    if (int rc = alloc_acc8192(ctx)) return rc;
+    K.n8192 = true;
+    if (getenv("HELM_HIP_VERBOSE")) {
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, kern);
+        fprintf(stderr, "[helm_si] k_pbs64_n8192 l=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", P.pbs_l,
+                K.n8192_lds, fa.numRegs, (size_t)fa.localSizeBytes, nb);
+    }
+    return 0;
+#endif
+}
+
 // The step bound of a bootstrapping key: the exact integer coefficient of one blind-rotation step is at most B/2 x the largest
 // l1-norm over the key polynomials (taken as centred 64-bit words) that meet in one output column - or, transposed, in one row.
 // A step sums `per_step` polynomials, laid out [...][r][c][N] (classical: the pbs_l (k+1)^2 of one GGSW; the generic multi-bit
@@ -2492,18 +2587,21 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     *out = nullptr;
     const helm_si_params &P = *params;
     // HELM_SI_CREATE_LARGE_N matters at N >= 4096 only: below, the call is the same call without the bit
-    const bool large = (flags & HELM_SI_CREATE_LARGE_N) != 0 && P.N >= 4096;
+    // HELM_SI_CREATE_N8192 matters at N >= 8192 only, in the same way; beside HELM_SI_CREATE_LARGE_N, N selects the kernel
+    const bool n8192 = (flags & HELM_SI_CREATE_N8192) != 0 && P.N >= 8192;
+    const bool large = (flags & HELM_SI_CREATE_LARGE_N) != 0 && P.N >= 4096 && !n8192;
     // HELM_SI_CREATE_PBS_KS changes no admission rule: the checks below see the flags without it
     const bool pbs_ks = (flags & HELM_SI_CREATE_PBS_KS) != 0;
     if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT |
-                  HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS))
+                  HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
                                           " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2, "
                                           "HELM_SI_CREATE_GENERIC_MULTIBIT = 16" +
                                           ((flags & HELM_SI_CREATE_LARGE_N) ? ", HELM_SI_CREATE_LARGE_N = 32" : "") +
                                           (pbs_ks ? ", HELM_SI_CREATE_PBS_KS = 64" : "") +
+                                          ((flags & HELM_SI_CREATE_N8192) ? ", HELM_SI_CREATE_N8192 = 256" : "") +
                                           "; 4 and 8 are reserved)");
-    flags &= ~(HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS);
+    flags &= ~(HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192);
     const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
     const bool multibit = (flags & HELM_SI_CREATE_GENERIC_MULTIBIT) != 0;
     if (multibit && !(flags & (HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC)))
@@ -2516,13 +2614,17 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the large-N kernel: its domain under HELM_SI_CREATE_LARGE_N is "
                                       "k = 1, N = 4096, pbs_l >= 1, grouping_factor <= 1 (k > 1 at N = 4096, multi-bit at "
                                       "N = 4096 and N = 8192 are out of scope)");
-    const bool tuned = large || (si_supported(P) && !(multibit && P.grouping_factor > 1 && !si_tuned_multibit(P)));
+    if (n8192 && !si_n8192_domain(P))
+        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the N = 8192 kernel: its domain under HELM_SI_CREATE_N8192 is "
+                                      "k = 1, N = 8192, pbs_l >= 1, grouping_factor <= 1 (k > 1 at N = 8192, multi-bit at "
+                                      "N = 8192 and N >= 16384 are out of scope)");
+    const bool tuned = large || n8192 || (si_supported(P) && !(multibit && P.grouping_factor > 1 && !si_tuned_multibit(P)));
     if (!tuned && flags == 0)
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l): built variants are k = 1, N in {512,1024,2048}, pbs_l in {1,2}; k in {2,3}, N = 512, pbs_l = 1; k = 2, N = 1024, pbs_l = 1");
     if (!tuned && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation (grouping_factor > 1) runs on the tuned builds only: this shape "
                                       "(k,N,pbs_l) has none, and the generic kernel has no multi-bit form");
-    const bool run_generic = !large && (force || !tuned); // (the large-N shape has one kernel, under every generic bit)
+    const bool run_generic = !large && !n8192 && (force || !tuned); // (the large-N shapes have one kernel each, under every generic bit)
     const bool gen_mb = run_generic && multibit && P.grouping_factor > 1; // the generic kernel's multi-bit form
     if (gen_mb && (P.grouping_factor > 3 || P.n % P.grouping_factor))
         return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
@@ -2549,7 +2651,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
         const long double bound = (long double)(P.k + 1) * P.pbs_l * P.N * (long double)(1ull << (P.pbs_logB - 1)) *
                                   9223372036854775808.0L;
         // (a large-N context computes in its own pair: p0 p1 / 2 = 2^97.87)
-        const long double half = large ? (long double)L0::P * (long double)L1::P / 2 : (long double)F0::P * (long double)F1::P / 2;
+        const long double half = (large || n8192) ? (long double)L0::P * (long double)L1::P / 2 : (long double)F0::P * (long double)F1::P / 2;
         if (bound * 1.001L >= half) return fail(HELM_ERR_INVALID, "parameter set exceeds the two-prime NTT capacity");
         // per-field operands: digits must be far below p
         if ((double)(1ull << (P.pbs_logB - 1)) * 4 >= F1::P / 2) return fail(HELM_ERR_INVALID, "pbs_logB too large");
@@ -2581,12 +2683,18 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
     const int N = P.N;
-    if (int rc = setup_pair_tables(ctx, large ? 2 : 0)) {
+    if (int rc = setup_pair_tables(ctx, (large || n8192) ? 2 : 0)) {
         (void)helm_si_ctx_destroy(ctx);
         return rc;
     }
     if (large) {
         if (int rc = setup_large(ctx)) {
+            (void)helm_si_ctx_destroy(ctx);
+            return rc;
+        }
+    }
+    if (n8192) {
+        if (int rc = setup_n8192(ctx)) {
             (void)helm_si_ctx_destroy(ctx);
             return rc;
         }
@@ -2609,7 +2717,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     K.use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
     if (const char *v = getenv("HELM_HIP_KS_MFMA")) K.ks_mfma = atoi(v);
     if (const char *v = getenv("HELM_SI_SPLIT")) K.use_split = (K.use_split && atoi(v) != 0) || group > 1;
-    if (K.gen || K.large) K.use_split = false; // (a generic or large-N context reads one key layout, multi-bit too)
+    if (K.gen || K.large || K.n8192) K.use_split = false; // (a generic or large-N context reads one key layout, multi-bit too)
     if (K.use_split) {
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
@@ -2652,6 +2760,13 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
         return fail(HELM_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
     }
     ctx->stream = ctx->own_stream;
+    if (primary->keys->n8192) { // a lane launches on its own stream: accumulator rows of its own
+        if (int rc = alloc_acc8192(ctx)) {
+            (void)hipStreamDestroy(ctx->own_stream);
+            delete ctx;
+            return rc;
+        }
+    }
     primary->lanes.push_back(ctx);
     *out = ctx;
     return 0;
@@ -2694,6 +2809,7 @@ int helm_si_ctx_destroy(helm_si_ctx *ctx)
     ctx->d_idx.release();
     ctx->d_idx2.release();
     ctx->d_coef.release();
+    (void)hipFree(ctx->d_acc8192);
     (void)hipStreamDestroy(ctx->own_stream);
     delete ctx; // (a primary's key state goes with it: SiKeyState frees its device memory)
     return 0;
@@ -2727,7 +2843,7 @@ int64_t helm_si_wire_words(const helm_si_ctx *ctx)
 int helm_si_kernel_class(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->keys->large ? 2 : ctx->keys->gen ? 1 : 0;
+    return ctx->keys->n8192 ? 3 : ctx->keys->large ? 2 : ctx->keys->gen ? 1 : 0;
 }
 
 int helm_si_set_stream(helm_si_ctx *ctx, void *hip_stream)
@@ -2818,7 +2934,11 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (K.large) { // the generic layout in the pair FpG / FpI (k_bsk_convert64_large)
+    if (K.n8192) { // the same layout and pair at N = 8192, through dynamic LDS (k_bsk_convert64_n8192)
+        hipLaunchKernelGGL(k_bsk_convert64_n8192, dim3((unsigned)polys), dim3(L64_THREADS), sizeof(double) * 2 * (size_t)P.N,
+                           ctx->stream, d_std, K.bsk, K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1,
+                           P.pbs_l);
+    } else if (K.large) { // the generic layout in the pair FpG / FpI (k_bsk_convert64_large)
         hipLaunchKernelGGL(k_bsk_convert64_large<12>, dim3((unsigned)polys), dim3(L64_THREADS), 0, ctx->stream, d_std, K.bsk,
                            K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l);
     } else if (K.gen) {

@@ -290,7 +290,7 @@ template <typename W> Planes build_planes(const W *key, int in_dim, int ks_l, in
 }
 
 // The vector-ALU launch of `count` jobs: four jobs and 256 columns per workgroup; narrow launches split the key rows until
-// ~2 workgroups per CU exist (at most 16 slices of at least 64 input words).
+// ~2 workgroups per CU exist (at most 16 slices of at least 64 input words), and wherever one slice's digits would not fit LDS.
 struct Geometry {
     dim3 grid;
     int slices, t_chunk;
@@ -301,6 +301,11 @@ inline Geometry vector_geometry(int64_t count, int n, int kN, int ks_l, int n_cu
     const unsigned gx = (unsigned)((count + 3) / 4), gy = (unsigned)((n + 1 + 255) / 256);
     int slices = 1;
     while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)n_cus && kN / (slices * 2) >= 64) slices *= 2;
+    // ... and at least as many as keep a slice's digit buffer within the 160 KiB of LDS a workgroup can have.  Unsliced it is
+    // kN x ks_l x 4 B: at most 128 KiB for kN <= 4096 and ks_l <= 8, so this clause fires only where the runtime would refuse
+    // the launch above (kN = 8192 with ks_l >= 6, wide vector-ALU batches) and every shape with kN <= 4096 - all of the
+    // boolean engine's among them - keeps the geometry it had.
+    while ((size_t)((kN + slices - 1) / slices) * ks_l * sizeof(uint32_t) > (size_t)160 * 1024) slices *= 2;
     const int t_chunk = (kN + slices - 1) / slices;
     return Geometry{dim3(gx, gy, (unsigned)slices), slices, t_chunk, (size_t)t_chunk * ks_l * sizeof(uint32_t)};
 }

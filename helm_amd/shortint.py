@@ -115,12 +115,16 @@ SI_CREATE_FORCE_GENERIC = 2
 SI_CREATE_GENERIC_MULTIBIT = 16
 SI_CREATE_LARGE_N = 32
 SI_CREATE_PBS_KS = 64
+SI_CREATE_N8192 = 256
 _ORDER_FLAGS = {"ks_pbs": 0, "pbs_ks": SI_CREATE_PBS_KS}
 _GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC,
                   "allow+multibit": SI_CREATE_ALLOW_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
                   "force+multibit": SI_CREATE_FORCE_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
                   "large": SI_CREATE_LARGE_N, "allow+large": SI_CREATE_ALLOW_GENERIC | SI_CREATE_LARGE_N,
-                  "force+large": SI_CREATE_FORCE_GENERIC | SI_CREATE_LARGE_N}
+                  "force+large": SI_CREATE_FORCE_GENERIC | SI_CREATE_LARGE_N,
+                  "n8192": SI_CREATE_N8192, "allow+n8192": SI_CREATE_ALLOW_GENERIC | SI_CREATE_N8192,
+                  "force+n8192": SI_CREATE_FORCE_GENERIC | SI_CREATE_N8192,
+                  "large+n8192": SI_CREATE_LARGE_N | SI_CREATE_N8192}
 
 
 class SiServerKey:
@@ -134,7 +138,10 @@ class SiServerKey:
     bootstrapping key must then pass the load-time capacity check (include/helm_shortint.h).  "large" (alone, or as
     "allow+large" / "force+large" beside the generic settings) adds HELM_SI_CREATE_LARGE_N: k = 1, N = 4096 - the 5-bit sets,
     message_modulus * carry_modulus = 32 - is admitted and runs on the large-N kernel; any smaller shape behaves as without
-    it.  Lanes inherit the setting.
+    it.  "n8192" (alone, or as "allow+n8192" / "force+n8192" / "large+n8192") adds HELM_SI_CREATE_N8192: k = 1, N = 8192 - the
+    6-bit sets, message_modulus * carry_modulus = 64, the space of a 6-input look-up table - is admitted and runs on the
+    N = 8192 kernel; any smaller shape behaves as without it, and under "large+n8192" N selects the kernel.  Lanes inherit the
+    setting.
 
     order: "ks_pbs" (the default: the flags are passed as without it) keeps ciphertexts under the big key, a look-up is
     keyswitch, then bootstrap; "pbs_ks" adds HELM_SI_CREATE_PBS_KS: wire rows are n + 1 words under the small key
@@ -146,7 +153,8 @@ class SiServerKey:
             raise ValueError(f"order must be 'ks_pbs' or 'pbs_ks', not {order!r}")
         if generic not in _GENERIC_FLAGS:
             raise ValueError("generic must be None, 'allow', 'force', 'allow+multibit', 'force+multibit', 'large', "
-                             f"'allow+large' or 'force+large', not {generic!r}")
+                             "'allow+large' or 'force+large', or 'n8192', 'allow+n8192', 'force+n8192' or 'large+n8192', "
+                             f"not {generic!r}")
         self.params = client_key.params if client_key is not None else params
         self.generic = generic
         self.order = order
@@ -200,7 +208,7 @@ class SiServerKey:
 
     def field_bits(self):
         """49, 46 or 50: the CRT pair of prime fields this context's bootstrap kernels compute in (helm_si_field_bits: it
-        follows the loaded key for k > 1 contexts; 50 is the large-N kernel's pair)."""
+        follows the loaded key for k > 1 contexts; 50 is the pair of the large-N and N = 8192 kernels)."""
         return int(hip.helm_si_field_bits(self._h))
 
     def pbs_order(self):
@@ -220,11 +228,12 @@ class SiServerKey:
     def kernel_class(self):
         """"tuned" when a tuned bootstrap build runs this context's launches, "generic" when the generic kernel does (a shape
         no tuned build covers under generic="allow", or any shape under generic="force"), "large" when the large-N kernel
-        does (k = 1, N = 4096 under generic="large"; helm_si_kernel_class)."""
+        does (k = 1, N = 4096 under generic="large"), "n8192" when the N = 8192 kernel does (k = 1, N = 8192 under
+        generic="n8192"; helm_si_kernel_class)."""
         v = int(hip.helm_si_kernel_class(self._h))
         if v < 0:
             hip_check(v)
-        return "large" if v == 2 else "generic" if v == 1 else "tuned"
+        return "n8192" if v == 3 else "large" if v == 2 else "generic" if v == 1 else "tuned"
 
     def set_level_many_lut(self, on=True):
         """helm_si_set_level_many_lut: SiWires.eval_lut_level groups the gates of a level that have the same inputs in the same

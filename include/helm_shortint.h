@@ -84,7 +84,9 @@ enum {
     /* 4 and 8 are reserved: refused as unknown bits */
     HELM_SI_CREATE_GENERIC_MULTIBIT = 16, /* with 1 or 2: multi-bit shapes may run on the generic kernel's multi-bit form */
     HELM_SI_CREATE_LARGE_N = 32, /* admit k = 1, N = 4096 (the 5-bit shortint sets): it runs on the large-N kernel */
-    HELM_SI_CREATE_PBS_KS = 64 /* bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words under the small key */
+    HELM_SI_CREATE_PBS_KS = 64, /* bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words under the small key */
+    /* 128 is not assigned: refused as an unknown bit */
+    HELM_SI_CREATE_N8192 = 256 /* admit k = 1, N = 8192 (the 6-bit shortint sets): it runs on the N = 8192 kernel */
 };
 /* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
  * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
@@ -119,7 +121,7 @@ enum {
  * and its bootstraps run on k_pbs64_large: one workgroup of 1024 threads per bootstrap, one per CU, in the pair 5072^4 + 1
  * and 5440^4 + 1 (helm_si_field_bits() returns 50, helm_si_kernel_class() 2).  Everything above the bootstrap kernel works
  * unchanged, many-LUT included.  Refused with a message that names the large-N domain: k > 1 at N = 4096, multi-bit at
- * N = 4096, and N = 8192 (its accumulator alone is 128 KiB of LDS, and its products exceed the pair).  helm_wop_ctx_create
+ * N = 4096, and N = 8192 (that size has a kernel and a bit of its own: HELM_SI_CREATE_N8192, below).  helm_wop_ctx_create
  * refuses a PBS-side context of this class, and the bound-checking build refuses the class at creation.
  * HELM_SI_CREATE_PBS_KS (alone or beside any admitted combination of the bits above) chooses the other ciphertext order of a
  * tfhe shortint set (EncryptionKeyChoice::Small, the PARAM_*_PBS_KS sets): wire rows are LWE ciphertexts under the SMALL key,
@@ -137,10 +139,25 @@ enum {
  * their width, and the table is word for word the unsharded one.  helm_wop_ctx_create refuses such a PBS side by name (its
  * bit extraction, circuit bootstrap and result rows assume big rows).  The bound-checking build admits the order: nothing in
  * it depends on the row width.
- * Unknown flag bits (4 and 8 are reserved): HELM_ERR_INVALID. */
+ * HELM_SI_CREATE_N8192 (alone or beside any combination of the bits above) admits k = 1, N = 8192, pbs_l >= 1,
+ * grouping_factor <= 1 - every 6-bit set (message_modulus * carry_modulus = 64: tfhe's MESSAGE_3_CARRY_3 and
+ * MESSAGE_2_CARRY_4), the plaintext space a 6-input look-up table needs.  It matters at N = 8192 only: on any smaller N
+ * the call is the same call without the bit (same status, message, class and field), and without the bit every call is
+ * what it was, N = 8192 under HELM_SI_CREATE_LARGE_N alone included.  Beside HELM_SI_CREATE_LARGE_N, N selects the kernel.
+ * Such a shape passes every other check of helm_si_ctx_create in the same order, the capacity bound with the product of
+ * the large-N pair: 2 pbs_l N 2^(pbs_logB-1) 2^63 x 1.001 < p0 p1 / 2 = 2^97.87 - one level of 21 bits is at 0.547 of it,
+ * 22 bits are refused, tfhe's 2 levels of 15 bits are at 2^92.  Its bootstraps run on k_pbs64_n8192: one workgroup of 1024
+ * threads per bootstrap, one per CU, the accumulator in a row of device memory that belongs to the launching context (a
+ * primary and each lane have their own; a batch wider than a round goes out in chunks of a round).  helm_si_field_bits()
+ * returns 50, helm_si_kernel_class() 3, helm_si_round_capacity() the CU count.  Everything above the bootstrap kernel works
+ * unchanged: keyswitch at in_dim = 8192, many-LUT, both look-up orders, lanes, audit, sharding.  Refused with a message that
+ * names HELM_SI_CREATE_N8192: k > 1 at N = 8192, multi-bit at N = 8192, and N >= 16384.  helm_wop_ctx_create refuses a
+ * PBS-side context of this class by name, and the bound-checking build refuses the class at creation.
+ * Unknown flag bits (4 and 8 are reserved, 128 is not assigned): HELM_ERR_INVALID. */
 int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
 /* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic), 2 = the large-N
- * kernel (k_pbs64_large: k = 1, N = 4096 under HELM_SI_CREATE_LARGE_N, whatever generic bits stand beside it).  Unlike
+ * kernel (k_pbs64_large: k = 1, N = 4096 under HELM_SI_CREATE_LARGE_N, whatever generic bits stand beside it), 3 = the
+ * N = 8192 kernel (k_pbs64_n8192: k = 1, N = 8192 under HELM_SI_CREATE_N8192, likewise).  Unlike
  * helm_hip_kernel_class of the boolean engine, which reports the parameter shape only (its forcing is a debug variable),
  * this reports the kernel the launches actually run on: HELM_SI_CREATE_FORCE_GENERIC is part of this API, so a forced
  * tuned shape reports 1.  A lane reports its primary's class.  Negative on error. */

@@ -71,6 +71,7 @@ pub const HELM_SI_CREATE_FORCE_GENERIC: i32 = 2;
 pub const HELM_SI_CREATE_GENERIC_MULTIBIT: i32 = 16; // with one of the two above: the generic kernel's multi-bit form
 pub const HELM_SI_CREATE_LARGE_N: i32 = 32; // admit k = 1, N = 4096 (the 5-bit shortint sets): the large-N kernel
 pub const HELM_SI_CREATE_PBS_KS: i32 = 64; // bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words
+pub const HELM_SI_CREATE_N8192: i32 = 256; // admit k = 1, N = 8192 (the 6-bit shortint sets): the N = 8192 kernel
 
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
