@@ -302,9 +302,11 @@ inline Geometry vector_geometry(int64_t count, int n, int kN, int ks_l, int n_cu
     int slices = 1;
     while (slices < 16 && (int64_t)gx * gy * slices < 2 * (int64_t)n_cus && kN / (slices * 2) >= 64) slices *= 2;
     // ... and at least as many as keep a slice's digit buffer within the 160 KiB of LDS a workgroup can have.  Unsliced it is
-    // kN x ks_l x 4 B: at most 128 KiB for kN <= 4096 and ks_l <= 8, so this clause fires only where the runtime would refuse
-    // the launch above (kN = 8192 with ks_l >= 6, wide vector-ALU batches) and every shape with kN <= 4096 - all of the
-    // boolean engine's among them - keeps the geometry it had.
+    // kN x ks_l x 4 B: at most 128 KiB for kN <= 4096 and ks_l <= 8, so every shape with kN <= 4096 keeps the grid clause's
+    // geometry and this clause fires only on wide vector-ALU batches (one slice by the grid clause) beyond it: the 64-bit
+    // engine's kN = 8192 with ks_l >= 6, and the boolean engine's kN >= 6912 with ks_l = 6 and kN >= 5376 with ks_l = 8 (there
+    // only under HELM_HIP_KS_MFMA=0: ks_l = 8 has byte planes).  A slice of exactly 160 KiB (kN x ks_l = 40,960) goes out whole.
+    // tests/ks_edges.py restates this function; tests/test_ks_geometry.py holds the two together.
     while ((size_t)((kN + slices - 1) / slices) * ks_l * sizeof(uint32_t) > (size_t)160 * 1024) slices *= 2;
     const int t_chunk = (kN + slices - 1) / slices;
     return Geometry{dim3(gx, gy, (unsigned)slices), slices, t_chunk, (size_t)t_chunk * ks_l * sizeof(uint32_t)};

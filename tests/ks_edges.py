@@ -20,7 +20,8 @@ No GPU and no project code: digits_of is tfhe's closest-representable balanced d
 (NOT the kernels' one-addition recurrence; rep == w, where nothing is cut off, included), keyswitch_plain the double loop on
 Python integers, keyswitch_exact the same sums in int64 limbs for whole launches (pinned to keyswitch_plain by
 tests/test_keyswitch_edges.py).  The shape enumerators restate the admission rules of helm_hip_ctx_create,
-helm_si_ctx_create_ex and helm_wop_ctx_create.
+helm_si_ctx_create_ex and helm_wop_ctx_create; vector_geometry restates the launch geometry of the vector-ALU form
+(helm_ks::vector_geometry), and wide_cases lists the launches of tests/test_gpu_keyswitch_wide.py by the LDS band they are in.
 """
 import os
 import sys
@@ -245,10 +246,16 @@ def keyswitch_exact(rows, key, logB, l, width, body=True, limb=16):
     mod 2^w in unsigned wrapping arithmetic.  limb=8: narrower limbs, for the packing keyswitch's digits of up to 30 bits.
     -> [rows, out_words] words"""
     key = np.asarray(key)
-    in_dim, _, out_words = key.shape
+    in_dim = key.shape[0]
     rows = np.asarray(rows)
-    assert limb in (8, 16) and in_dim * l * (1 << (logB - 1)) * (1 << limb) < (1 << 53)
     D = digits_rows(rows[:, :in_dim], logB, l, width).reshape(len(rows), in_dim * l).astype(np.float64)
+    return _exact_from_digits(D, rows, key, logB, l, width, body, limb)
+
+
+def _exact_from_digits(D, rows, key, logB, l, width, body, limb):
+    """keyswitch_exact's sums from the float64 digit matrix D [rows, in_dim * l]."""
+    in_dim, _, out_words = key.shape
+    assert limb in (8, 16) and in_dim * l * (1 << (logB - 1)) * (1 << limb) < (1 << 53)
     K = key.reshape(in_dim * l, out_words).astype(np.uint64)
     total = np.zeros((len(rows), out_words), dtype=np.uint64)
     for i in range(width // limb):
@@ -261,6 +268,23 @@ def keyswitch_exact(rows, key, logB, l, width, body=True, limb=16):
     if width == 32:
         return (out & np.uint64(0xFFFFFFFF)).astype(np.uint32)
     return out
+
+
+def keyswitch_exact_wide(rows, keys, logB, l, width, chunk=256):
+    """keyswitch_exact of a wide launch under several keys: the digit matrix is rows x in_dim x l float64 (0.5 MiB a row at
+    in_dim 8192, l = 8), so the rows go through in chunks of at most `chunk`, each decomposed once for all keys.
+    keys: dict name -> key.  -> dict name -> [rows, out_words] words"""
+    assert 1 <= chunk <= 256
+    rows = np.asarray(rows)
+    keys = {name: np.asarray(key) for name, key in keys.items()}
+    in_dim = next(iter(keys.values())).shape[0]
+    parts = {name: [] for name in keys}
+    for a in range(0, len(rows), chunk):
+        part = rows[a:a + chunk]
+        D = digits_rows(part[:, :in_dim], logB, l, width).reshape(len(part), in_dim * l).astype(np.float64)
+        for name, key in keys.items():
+            parts[name].append(_exact_from_digits(D, part, key, logB, l, width, True, 16))
+    return {name: np.concatenate(p) for name, p in parts.items()}
 
 
 def plane_accumulators(row, key, logB, l, width, split_bytes=False):
@@ -308,14 +332,149 @@ def pfks_shapes(matrix_cores=None):
     return [s for s in out if (s[1] <= 15) == matrix_cores]
 
 
-def max_in_dim(width):
-    """The largest k N a context admits: (k+1) N <= 8192 (32-bit: pbs_admitted) / 4096 (64-bit: si_generic_domain), N >= 256."""
-    return (8192 if width == 32 else 4096) - 256
+def max_in_dim(width, large=False, n8192=False):
+    """The largest k N a context admits.  32-bit: (k+1) N <= 8192 (pbs_admitted), N >= 256: 7936.  64-bit: (k+1) N <= 4096
+    (si_generic_domain): 3840; with the large-N bit k = 1, N = 4096 as well (si_large_domain): 4096; with the N = 8192 bit
+    k = 1, N = 8192 (si_n8192_domain): 8192."""
+    if width == 32:
+        return 8192 - 256
+    return 8192 if n8192 else 4096 if large else 4096 - 256
+
+
+def in_dims(width):
+    """Every k N some admitted context has, as far as the keyswitch geometry can tell them apart: multiples of 256 up to
+    max_in_dim, and on the 64-bit engine the two sizes the large-N and the N = 8192 bit add."""
+    if width == 32:
+        return list(range(256, max_in_dim(32) + 1, 256))
+    return list(range(256, max_in_dim(64) + 1, 256)) + [LARGE_IN_DIM, N8192_IN_DIM]
 
 
 MIN_IN_DIM = 256
+LARGE_IN_DIM = 4096                                          # k = 1, N = 4096: SiServerKey(generic="large")
+N8192_IN_DIM = 8192                                          # k = 1, N = 8192: SiServerKey(generic="n8192")
 MAX_N = 1024                                                 # n must be in [1, 1024], both engines
 WOP_MAX_IN_WORDS = 2048 + 1                                  # k = 1, N <= 2048, body word included
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the launch geometry of the vector-ALU form (helm_ks::vector_geometry, restated; tests/test_ks_geometry.py pins the
+# three deciding lines of the source)
+# ------------------------------------------------------------------------------------------------------------------
+LDS_DEFAULT = 64 * 1024                                      # dynamic LDS a kernel may ask for without an attribute
+LDS_LIMIT = 160 * 1024                                       # LDS of a gfx950 workgroup; the attribute the engines set
+BANDS = ("default", "raised", "limit", "clause")
+
+
+def grid_slices(count, n, kN, n_cus):
+    """The grid clause alone: double the slices while fewer than two workgroups per CU exist, up to 16, each slice at
+    least 64 input words.  -> (gx, gy, slices)"""
+    gx, gy = (count + 3) // 4, (n + 1 + 255) // 256
+    slices = 1
+    while slices < 16 and gx * gy * slices < 2 * n_cus and kN // (slices * 2) >= 64:
+        slices *= 2
+    return gx, gy, slices
+
+
+def vector_geometry(count, n, kN, ks_l, n_cus):
+    """helm_ks::vector_geometry: the grid clause, then the LDS clause (double the slices while one slice's digits,
+    ceil(kN / slices) x ks_l x 4 B, exceed 160 KiB).  -> (gx, gy, slices, t_chunk, lds)"""
+    gx, gy, slices = grid_slices(count, n, kN, n_cus)
+    while (kN + slices - 1) // slices * ks_l * 4 > LDS_LIMIT:
+        slices *= 2
+    t_chunk = (kN + slices - 1) // slices
+    return gx, gy, slices, t_chunk, t_chunk * ks_l * 4
+
+
+def lds_band(count, n, kN, ks_l, n_cus):
+    """Where a launch stands against the two LDS limits, and which clause decided its slices.
+    -> (band, clause): band "default" (lds <= 64 KiB: launches without an attribute), "raised" (64 KiB < lds < 160 KiB),
+    "limit" (lds == 160 KiB exactly), each with clause "grid"; or "clause" (the grid clause alone would ask for more than
+    160 KiB: the LDS clause slices further), with clause "lds"."""
+    _, _, s_grid = grid_slices(count, n, kN, n_cus)
+    _, _, slices, _, lds = vector_geometry(count, n, kN, ks_l, n_cus)
+    if slices != s_grid:
+        return "clause", "lds"
+    return ("default" if lds <= LDS_DEFAULT else "raised" if lds < LDS_LIMIT else "limit"), "grid"
+
+
+def width_for_slices(slices, n, kN, n_cus):
+    """A batch width at which the grid clause gives `slices` in {16, 4, 2, 1} - 40 rows, 2 CUs + 4, 4 CUs + 4, 8 CUs + 4 at
+    gy = 1, and as many workgroups at gy > 1 (16 slices: fewer than 40 rows where 40 have a quarter of a workgroup per CU
+    already) - checked against grid_slices."""
+    gy = (n + 1 + 255) // 256
+    count = {16: min(40, 4 * ((2 * n_cus - 1) // (8 * gy))), 4: (2 * n_cus) // gy + 4, 2: (4 * n_cus) // gy + 4, 1: (8 * n_cus + gy - 1) // gy + 4}[slices]
+    assert grid_slices(count, n, kN, n_cus)[2] == slices, (count, n, kN, n_cus, slices)
+    return count
+
+
+SWEEP = 165                                                  # tests/test_gpu_keyswitch_edges.py's width: 16 slices, mfma on the 64-bit engine
+
+
+class WideCase:
+    """One case of tests/test_gpu_keyswitch_wide.py: a context shape, the slice counts its launches are built for (the
+    batch widths follow from the CU count), and per launch what the vector-ALU form is expected to be: (band, clause) of
+    lds_band.  mfma0_only: the vector-ALU form serves these widths only under HELM_HIP_KS_MFMA=0 (the unset run takes the
+    matrix cores; the two are compared all the same)."""
+
+    def __init__(self, width, n, k, N, l, logB, slices, expect, generic=None, kinds=("random", "follow"), mfma0_only=False):
+        self.width, self.n, self.k, self.N, self.l, self.logB = width, n, k, N, l, logB
+        self.slices, self.expect, self.generic, self.kinds, self.mfma0_only = slices, expect, generic, kinds, mfma0_only
+        self.kN = k * N
+
+    def counts(self, n_cus):
+        return [SWEEP if s == "sweep" else width_for_slices(s, self.n, self.kN, n_cus) for s in self.slices]
+
+    def geometry(self, n_cus):
+        return [vector_geometry(c, self.n, self.kN, self.l, n_cus) for c in self.counts(n_cus)]
+
+    def bands(self, n_cus):
+        return [lds_band(c, self.n, self.kN, self.l, n_cus) for c in self.counts(n_cus)]
+
+    @property
+    def id(self):
+        return "w%d-n%d-k%dN%d-l%dB%d-s%s" % (self.width, self.n, self.k, self.N, self.l, self.logB,
+                                               "x".join(str(s) for s in self.slices))
+
+
+G, L = "grid", "lds"
+
+
+def wide_cases():
+    """The cases of tests/test_gpu_keyswitch_wide.py.  The uniform key goes first: under the sign-following key an even
+    level count can leave all-zero rows behind, which would hide a sliced launch whose rows were not cleared."""
+    k32 = dict(width=32, n=46, k=31, N=256)                   # k N = 7936, the largest of the 32-bit engine
+    cases = [
+        # 32-bit, ks_l = 3 (vector-ALU form only): 95,232 B unsliced
+        WideCase(l=3, logB=7, slices=(16, 2, 1), expect=[("default", G), ("default", G), ("raised", G)], **k32),
+        # ks_l = 8 on the vector-ALU form: 253,952 B unsliced - the LDS clause makes it 2 x 126,976 B; 4 slices: 63,488 B
+        WideCase(l=8, logB=4, slices=(4, 1), expect=[("default", G), ("clause", L)], mfma0_only=True, **k32),
+        # ks_l = 5: 158,720 B unsliced, 5 KiB under the limit
+        WideCase(l=5, logB=6, slices=(1,), expect=[("raised", G)], **k32),
+        # a second column chunk (gy = 2) under a raised launch
+        WideCase(32, 300, 31, 256, 3, 7, slices=(1,), expect=[("raised", G)]),
+        # k N = 5120, ks_l = 8: exactly 160 KiB on the 32-bit engine
+        WideCase(32, 46, 20, 256, 8, 4, slices=(1,), expect=[("limit", G)], mfma0_only=True),
+    ]
+    # 64-bit: the ends of the decomposition at the two new sizes, all six keys, the crafted construction at SWEEP rows
+    for N, generic in ((LARGE_IN_DIM, "large"), (N8192_IN_DIM, "n8192")):
+        for l in (1, 8):
+            for logB in (1, 7):
+                cases.append(WideCase(64, 46, 1, N, l, logB, slices=("sweep",), expect=[("default", G)], generic=generic,
+                                      kinds=KEYS, mfma0_only=True))
+    cases += [
+        # in_dim 4096, ks_l = 8: 32 KiB, exactly 64 KiB and 128 KiB at 4, 2 and 1 slices
+        WideCase(64, 46, 1, LARGE_IN_DIM, 8, 7, slices=(4, 2, 1), expect=[("default", G), ("default", G), ("raised", G)],
+                 generic="large", mfma0_only=True),
+        # in_dim 8192, ks_l = 5: exactly 163,840 B, unsliced
+        WideCase(64, 46, 1, N8192_IN_DIM, 5, 7, slices=(1,), expect=[("limit", G)], generic="n8192", mfma0_only=True),
+        # in_dim 8192, ks_l = 6: 196,608 B unsliced - the LDS clause makes it 2 x 98,304 B
+        WideCase(64, 46, 1, N8192_IN_DIM, 6, 7, slices=(1,), expect=[("clause", L)], generic="n8192", mfma0_only=True),
+    ]
+    return cases
+
+
+# Keyswitch-first gate levels (GateKsRows) in the raised band: (k, N, n, ks_l, ks_logB); k N x ks_l x 4 B = 73,728 and 102,400
+GATE_SHAPES = [(6, 1024, 16, 3, 7), (5, 1024, 16, 5, 4)]
 
 
 def padded_levels(l):
