@@ -166,6 +166,56 @@ int helm_si_client_named_params(const char *name, helm_si_params *p, double *lwe
         p->message_modulus = 8; p->carry_modulus = 8;
         *lwe_std = 1e-9;
         *glwe_std = 1e-17;
+    } else if (s == "shortint_m3c3_multibit3") {
+        // shortint_m3c3's values with grouping_factor = 3 (864 = 3 x 288 groups), for the multi-bit form of the N = 8192 kernel
+        // (HELM_SI_CREATE_N8192 | HELM_SI_CREATE_LARGE_MULTIBIT) [an approximate set, as shortint_m3c3 is: tfhe's own
+        // PARAM_MULTI_BIT_MESSAGE_3_CARRY_3_GROUP_3 values are not in the tree and not recalled.  PBS 15 x 2 loads at every
+        // grouping factor: a generated key's group sums are near 2^94 against the pair's half of 2^97.87.
+        // By the formulas of tests/test_gpu_noise.py with the multi-bit terms - per group 2^g x the key's noise through the
+        // digits, and the rounding term with 12 in place of 24 over n / g groups: blind rotation 2^-43.4 (the rounding; the
+        // key's noise through the digits is 2^-71.4, a factor 8 / 3 above the classical 2^-72.8), keyswitch 2^-22.6, modulus
+        // switch 2^-22.8, unchanged.  Failure probability per look-up: 2^-40.7 on a fresh encryption or one look-up output,
+        // and 2^-40.7 on the full-arity operand 32x + 16y + 8z + 4u + 2v + w of six look-up outputs (weight 1365 x 2^-43.4 =
+        // 2^-33.0 stays far below the keyswitch and the modulus switch) - shortint_m3c3's figures: at this decomposition the
+        // grouping costs no margin.  Predictions of the formulas, not measured here]
+        p->n = 864; p->N = 8192; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 6; p->ks_logB = 3;
+        p->message_modulus = 8; p->carry_modulus = 8;
+        p->grouping_factor = 3;
+        *lwe_std = 0.000000755;
+        *glwe_std = 0.0000000000000000002168404344971009;
+    } else if (s == "shortint_m2c3_multibit3") {
+        // shortint_m2c3's LWE side (keyswitch 8 x 3, LWE noise 4.0e-8; the security line gives 4.1e-8 at this n) with
+        // n = 1023 = 3 x 341 groups, grouping_factor = 3 and PBS 15 x 2, for the multi-bit form of the large-N kernel
+        // (HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_LARGE_MULTIBIT) [an approximate set.  The recalled 22 x 1 of shortint_m2c3
+        // cannot load in multi-bit: a generated key's group sums would be near 2^(22 + 3 + 62 + 12) = 2^99, over the pair's
+        // half of 2^97.87 (one level loads up to pbs_logB + grouping_factor = 23); 15 x 2 is at 2^93.
+        // By the formulas of tests/test_gpu_noise.py with the multi-bit terms: blind rotation 2^-44.2 (the rounding; the key's
+        // noise through the digits is 2^-72.2), keyswitch 2^-31.6, modulus switch 2^-20.6 - the dominant term, as in
+        // shortint_m2c3.  Half a box is 2^-7 at t = 32.  Failure probability per look-up: 2^-72.8 on a fresh encryption or
+        // one look-up output (9.8 standard deviations), and 2^-72.8 as well on the full-arity operand 16x + 8y + 4z + 2u + v
+        // of five look-up outputs: the weight 341 raises the blind rotation's term to 2^-35.8 only - the finer decomposition
+        // is what shortint_m2c3's comment asks for, where that operand is at 2^-21.6.  The formulas admit 15 x 2 at n = 1023,
+        // so no other decomposition was looked for.  Predictions of the formulas, not measured here]
+        p->n = 1023; p->N = 4096; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 8; p->ks_logB = 3;
+        p->carry_modulus = 8;
+        p->grouping_factor = 3;
+        *lwe_std = 0.00000004;
+        *glwe_std = 0.0000000000000000002168404344971009;
+    } else if (s == "si_toy_4096_mb2" || s == "si_toy_4096_mb3") {
+        // si_toy_4096 for the multi-bit form of the large-N kernel (HELM_SI_CREATE_LARGE_MULTIBIT): n = 12 is divisible by
+        // both grouping factors, and pbs_logB + grouping_factor = 23 is the largest a one-level key of this N loads with
+        p->grouping_factor = s.back() - '0';
+        p->n = 12; p->N = 4096; p->pbs_l = 1; p->pbs_logB = 23 - p->grouping_factor; p->ks_l = 3; p->ks_logB = 5;
+        p->carry_modulus = 8;
+        *lwe_std = 1e-9;
+        *glwe_std = 1e-17;
+    } else if (s == "si_toy_8192_mb2" || s == "si_toy_8192_mb3") {
+        // si_toy_8192 for the multi-bit form of the N = 8192 kernel: PBS 15 x 2 loads at every grouping factor
+        p->grouping_factor = s.back() - '0';
+        p->n = 12; p->N = 8192; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 3; p->ks_logB = 5;
+        p->message_modulus = 8; p->carry_modulus = 8;
+        *lwe_std = 1e-9;
+        *glwe_std = 1e-17;
     } else if (s == "si_toy_512") {
         p->n = 12; p->N = 512; p->pbs_l = 2; p->pbs_logB = 15; p->ks_l = 4; p->ks_logB = 4;
         *lwe_std = 1e-9;

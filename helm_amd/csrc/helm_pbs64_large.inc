@@ -51,6 +51,24 @@
 //     2^51, HELM_BOUND slot 4).
 // The torus arithmetic is therefore the exact negacyclic product mod 2^64 for every admitted shape
 // (tests/test_large_n_bounds.py restates these bounds with exact fractions).
+//
+// Multi-bit form (template argument GG = grouping factor 2 or 3, HELM_SI_CREATE_LARGE_MULTIBIT; GG = 0 is the classical form
+// above).  The algorithm is the one at the head of helm_pbs64_generic.inc: per group t < n / GG ONE external product,
+// acc <- (sum_S X^(e_S) GGSW_{t,S}) (x) acc with e_S = sum_{i in S} a~_i mod 2N (uniform over the workgroup, in scalar
+// registers).  The digits are those of the accumulator itself at the thread's own positions (no rotation, no difference), the
+// column sums are sum_S sum_q (d^_q . M(e_S)) . K^_{t,S}[q][c], and the lifted value REPLACES the accumulator.  No group is
+// skipped, not one whose rotations are all 0: the oracle does not skip either, and the step is not the identity on the low
+// bits.  M(e)[s] = psi^(expo(s) e), expo(s) = 2 rev(s) + 1: l64_ntt_forward has the generic kernel's Cooley-Tukey structure
+// (twiddle m + i), so position s holds the value at psi^(2 rev(s) + 1).  M is read per use from the context's table of the 2N
+// powers of psi in each field of this pair ([2][2N] doubles in global memory, written once at creation).  All 2 l digit
+// polynomials go forward once, the 16 sums stay in registers, both columns are lifted after the last digit polynomial; the
+// barriers stand where they stood (a step reads the accumulator at own positions only; the one that ends a step still orders
+// the body coefficient for the sample extract).
+// Exactness of the multi-bit form, for p1.  d^ is recentred and |M| <= p/2, so d^ M = mulmod(d^, M) is below 0.58 p; its
+// product with a key word is below (0.5 + 0.75 x 0.58 p 2^-52) p < 0.59 p.  A sum is recentred after every four products
+// (the 2^GG subsets of one digit polynomial in runs of four): <= 0.5 p + 4 x 0.59 p < 2.9 p < 2^53 = 10.28 p.  The true
+// integer coefficient is bounded by helm_si_load_bootstrap_key's group-sum rule for the key at hand (below p0 p1 / 2 / 1.001
+// with THIS pair's product), so the recentred lift is exact (tests/test_large_multibit_bounds.py restates these numbers).
 
 using L0 = FpG;
 using L1 = FpI;
@@ -109,14 +127,16 @@ __device__ __forceinline__ void l64_ntt_inverse(double *x, const double *__restr
     }
 }
 
-// bsk: [i][r][c][lev][f][N] in the transform domain (bit-reversed order), times N^-1, recentred (k_bsk_convert64_large)
-template <int LOGN>
+// bsk: [i][r][c][lev][f][N] in the transform domain (bit-reversed order), times N^-1, recentred (k_bsk_convert64_large);
+// GG > 0 (multi-bit): i = t 2^GG + S, n a multiple of GG, psi_pow the 2N powers of psi per field ([2][2N])
+template <int LOGN, int GG = 0>
 __global__ __launch_bounds__(L64_THREADS) void k_pbs64_large(const Pbs64Job *__restrict__ jobs,
                                                              const uint64_t *__restrict__ small, // rows of n+1
                                                              const uint64_t *__restrict__ luts,  // rows of N
                                                              const double *__restrict__ bsk,
                                                              const double *__restrict__ tw0, const double *__restrict__ tw1,
                                                              const double *__restrict__ twi0, const double *__restrict__ twi1,
+                                                             const double *__restrict__ psi_pow,
                                                              uint64_t *__restrict__ out, // rows of N+1
                                                              int n, int L, int logB, double p0inv_mod_p1)
 {
@@ -153,6 +173,7 @@ __global__ __launch_bounds__(L64_THREADS) void k_pbs64_large(const Pbs64Job *__r
     const uint64_t round_off = 1ull << (63 - rep);
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
     const size_t step_words = (size_t)4 * L * 2 * N; // key words of one GGSW
+    if constexpr (GG == 0) // (classical form; the multi-bit form is the else branch below)
     for (int i = 0; i < n; i++) {
         const int a = (int)MS[i];
         if (a == 0) continue; // uniform over the workgroup
@@ -217,6 +238,89 @@ __global__ __launch_bounds__(L64_THREADS) void k_pbs64_large(const Pbs64Job *__r
             }
         }
         __syncthreads(); // the next step's digits read the accumulator at rotated positions
+    }
+    // ---- multi-bit blind rotation: acc <- (sum_S X^(e_S) BSK_{t,S}) (x) acc ------------------
+    else
+    for (int t = 0; t < n / GG; t++) {
+        constexpr int SUB = 1 << GG;
+        // the group's rotations, uniform over the workgroup: scalar registers
+        int am[GG];
+#pragma unroll
+        for (int i = 0; i < GG; i++) am[i] = __builtin_amdgcn_readfirstlane((int)MS[t * GG + i]);
+        const double *key = bsk + (size_t)t * SUB * step_words;
+        double sum[2][2][PT]; // [column][field][position]: registers (every index below is a compile-time constant)
+#pragma unroll
+        for (int m = 0; m < PT; m++) sum[0][0][m] = sum[0][1][m] = sum[1][0][m] = sum[1][1][m] = 0.0;
+        for (int q = 0; q < 2 * L; q++) {
+            const int r = q >= L ? 1 : 0, lev = q - r * L;
+            // digits of the accumulator's polynomial itself at this thread's positions
+#pragma unroll
+            for (int m = 0; m < PT; m++) {
+                const int j = tid + m * L64_THREADS;
+                uint32_t state = (uint32_t)((acc[(size_t)r * N + j] + round_off) >> (64 - rep));
+                int d = 0;
+                for (int lv = L - 1; lv >= lev; lv--) d = g64_decompose_step(state, logB, half_m1);
+                buf[j] = (double)d;
+                buf[N + j] = (double)d;
+            }
+            __syncthreads();
+            l64_ntt_forward<LOGN>(buf, tw0, tw1);
+            // per subset S (one at a time): d^ M(e_S) at this thread's positions, then its products with the key words of
+            // GGSW (t, S), polynomial (r, c, lev), for both columns; recentred after every fourth subset
+#pragma unroll 1
+            for (int S = 0; S < SUB; S++) {
+                int eS = 0; // e_S = sum of the members' rotations mod 2N (bit i of S = member i)
+#pragma unroll
+                for (int i = 0; i < GG; i++) eS += (S >> i) & 1 ? am[i] : 0;
+                eS &= 2 * N - 1;
+                const double *kS = key + (size_t)S * step_words + ((size_t)(r * 2) * L + lev) * 2 * N;
+                const bool fold = (S & 3) == 3;
+#pragma unroll
+                for (int m = 0; m < PT; m++) {
+                    const int s = tid + m * L64_THREADS;
+                    double d0 = buf[s], d1 = buf[N + s];
+                    if (S) { // (M(0) = 1)
+                        const int ex = 2 * (int)(__brev((unsigned)s) >> (32 - LOGN)) + 1; // expo(s): see the head of this file
+                        const int at = (ex * eS) & (2 * N - 1);
+                        d0 = mulmod<L0>(d0, psi_pow[at]);
+                        d1 = mulmod<L1>(d1, psi_pow[2 * N + at]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const double *kc = kS + (size_t)c * L * 2 * N;
+                        double s0 = sum[c][0][m] + mulmod<L0>(d0, kc[s]), s1 = sum[c][1][m] + mulmod<L1>(d1, kc[N + s]);
+                        if (fold) {
+                            s0 = reduce<L0>(s0); // <= 0.5 p + 4 x 0.59 p before
+                            s1 = reduce<L1>(s1);
+                        }
+                        sum[c][0][m] = s0;
+                        sum[c][1][m] = s1;
+                    }
+                }
+            }
+            // (no barrier: the next digits, or the column below, overwrite this thread's own positions only)
+        }
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+#pragma unroll
+            for (int m = 0; m < PT; m++) {
+                const int s = tid + m * L64_THREADS;
+                buf[s] = reduce<L0>(sum[c][0][m]);
+                buf[N + s] = reduce<L1>(sum[c][1][m]);
+            }
+            __syncthreads();
+            l64_ntt_inverse<LOGN>(buf, twi0, twi1);
+            // CRT lift as above; the lifted value replaces the accumulator
+#pragma unroll
+            for (int m = 0; m < PT; m++) {
+                const int j = tid + m * L64_THREADS;
+                const double r0 = buf[j], r1 = buf[N + j];
+                const double tq = reduce<L1>(mulmod<L1>(r1 - r0, p0inv_mod_p1));
+                HELM_BOUND(__builtin_fabs(r0) < 0x1p51 && __builtin_fabs(tq) < 0x1p51, 4);
+                acc[(size_t)c * N + j] = (uint64_t)to_int64(r0) + L0::P_U64 * (uint64_t)to_int64(tq);
+            }
+        }
+        __syncthreads(); // orders the body coefficient for the sample extract (and the next step's digits after the lifts)
     }
 
     // ---- sample extract: every output of the job (extract_put; pad = 0: the one at coefficient 0) ----------

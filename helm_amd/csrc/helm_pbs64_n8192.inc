@@ -49,6 +49,22 @@
 // helm_si_ctx_create_ex holds below p0 p1 / 2 / 1.001 = 2^97.87 / 1.001 with this pair's product: (l, logB) = (1, 21) is at
 // 0.547 of p0 p1 / 2, (1, 22) is refused; tfhe's (2, 15) is at 2^92.  The lift then returns x exactly, as there
 // (tests/test_n8192_bounds.py restates these numbers with exact fractions).
+//
+// Multi-bit form (template argument GG = grouping factor 2 or 3, HELM_SI_CREATE_LARGE_MULTIBIT; GG = 0 is the classical form
+// above).  The algorithm is the one at the head of helm_pbs64_generic.inc, in this kernel's form (a), the columns one after
+// the other: per group t < n / GG ONE external product, acc <- (sum_S X^(e_S) GGSW_{t,S}) (x) acc, e_S = sum_{i in S} a~_i
+// mod 2N (the members' rotations live in scalar registers).  The start states (acc + round_off) >> (64 - rep) are taken at
+// the thread's own eight positions before column 0's lift replaces polynomial 0 - a multi-bit step reads no other thread's
+// position.  Per column, polynomial and level: digits, forward transform, then per subset S, ONE AT A TIME (the loop is
+// rolled: the 2^GG table values and products are never live together), d^ M(e_S) and its product with the key word of GGSW
+// (t, S), recentred after every fourth subset.  M(e)[s] = psi^((2 rev(s) + 1) e) is read per use from the context's table of
+// the 2N powers of psi per field ([2][2N] doubles in global memory).  The lifted value REPLACES the accumulator row's word.  No
+// group is skipped, not one whose rotations are all 0.  The barriers stand where they stood; (B) still orders the body
+// coefficient for the sample extract.
+// Exactness of the multi-bit form, for p1: d^ M is below 0.58 p, its product with a key word below (0.5 + 0.75 x 0.58 p
+// 2^-52) p < 0.59 p, four of them on a recentred sum <= 0.5 p + 4 x 0.59 p < 2.9 p < 2^53 = 10.28 p; the true coefficient is
+// bounded by helm_si_load_bootstrap_key's group-sum rule for the key at hand with this pair's product, so the recentred lift
+// is exact (tests/test_large_multibit_bounds.py).
 
 constexpr int N8192_LOGN = 13;
 
@@ -110,12 +126,15 @@ __device__ __forceinline__ void n8192_ntt_inverse(double *x, const double *__res
 
 // bsk: [i][r][c][lev][f][N] in the transform domain (bit-reversed order), times N^-1, recentred (k_bsk_convert64_n8192)
 // acc_rows: rows of 2N words, one per workgroup of the launch (gridDim.x rows at least)
+// GG > 0 (multi-bit): i = t 2^GG + S, n a multiple of GG, psi_pow the 2N powers of psi per field ([2][2N])
+template <int GG = 0>
 __global__ __launch_bounds__(L64_THREADS) void k_pbs64_n8192(const Pbs64Job *__restrict__ jobs,
                                                              const uint64_t *__restrict__ small, // rows of n+1
                                                              const uint64_t *__restrict__ luts,  // rows of N
                                                              const double *__restrict__ bsk,
                                                              const double *__restrict__ tw0, const double *__restrict__ tw1,
                                                              const double *__restrict__ twi0, const double *__restrict__ twi1,
+                                                             const double *__restrict__ psi_pow,
                                                              uint64_t *__restrict__ out, // rows of N+1
                                                              uint64_t *acc_rows, int n, int L, int logB, double p0inv_mod_p1)
 {
@@ -153,6 +172,7 @@ __global__ __launch_bounds__(L64_THREADS) void k_pbs64_n8192(const Pbs64Job *__r
     const uint64_t round_off = 1ull << (63 - rep);
     const uint32_t half_m1 = (1u << (logB - 1)) - 1u;
     const size_t step_words = (size_t)4 * L * 2 * N; // key words of one GGSW
+    if constexpr (GG == 0) // (classical form; the multi-bit form is the else branch below)
     for (int i = 0; i < n; i++) {
         const int a = (int)MS[i];
         if (a == 0) continue; // uniform over the workgroup
@@ -228,6 +248,98 @@ __global__ __launch_bounds__(L64_THREADS) void k_pbs64_n8192(const Pbs64Job *__r
                 const double t = reduce<L1>(mulmod<L1>(r1 - r0, p0inv_mod_p1));
                 HELM_BOUND(__builtin_fabs(r0) < 0x1p51 && __builtin_fabs(t) < 0x1p51, 4);
                 acc[(unsigned)c * N + own + m] += (uint64_t)to_int64(r0) + L0::P_U64 * (uint64_t)to_int64(t);
+            }
+        }
+        __syncthreads(); // (B)
+    }
+    // ---- multi-bit blind rotation: acc <- (sum_S X^(e_S) BSK_{t,S}) (x) acc ------------------
+    else
+    for (int t = 0; t < n / GG; t++) {
+        constexpr int SUB = 1 << GG;
+        // the group's rotations, uniform over the workgroup: scalar registers
+        int am[GG];
+#pragma unroll
+        for (int i = 0; i < GG; i++) am[i] = __builtin_amdgcn_readfirstlane((int)MS[t * GG + i]);
+        const double *key = bsk + (size_t)t * SUB * step_words;
+        // the decomposition's start states of polynomial 0 at own positions, before column 0's lift replaces it (polynomial
+        // 1 is replaced by column 1's lift, after its last use: its states are read from the row again per column)
+        uint32_t init0[PT];
+#pragma unroll
+        for (int m = 0; m < PT; m++) init0[m] = (uint32_t)((acc[own + m] + round_off) >> (64 - rep));
+#pragma unroll 1
+        for (int c = 0; c < 2; c++) {
+            double sum[2][PT]; // [field][position]: registers (every index below is a compile-time constant)
+#pragma unroll
+            for (int m = 0; m < PT; m++) sum[0][m] = sum[1][m] = 0.0;
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                uint32_t state[PT];
+#pragma unroll
+                for (int m = 0; m < PT; m++)
+                    state[m] = r == 0 ? init0[m] : (uint32_t)((acc[N + own + m] + round_off) >> (64 - rep));
+                // levels in recurrence order: the least significant level (lev = L - 1) first
+                for (int lev = L - 1; lev >= 0; lev--) {
+#pragma unroll
+                    for (int m = 0; m < PT; m++) {
+                        const int j = tid + m * L64_THREADS;
+                        const double d = (double)g64_decompose_step(state[m], logB, half_m1);
+                        buf[j] = d;
+                        buf[N + j] = d;
+                    }
+                    __syncthreads(); // (A)
+                    n8192_ntt_forward(buf, tw0, tw1);
+                    // per subset S, one at a time: d^ M(e_S) at this thread's positions, then its product with the key word
+                    // of GGSW (t, S), polynomial (r, c, lev); recentred after every fourth subset
+                    const double *kq = key + (((size_t)(r * 2 + c) * L + lev) * 2) * N;
+#pragma unroll 1
+                    for (int S = 0; S < SUB; S++) {
+                        int eS = 0; // e_S = sum of the members' rotations mod 2N (bit i of S = member i)
+#pragma unroll
+                        for (int i = 0; i < GG; i++) eS += (S >> i) & 1 ? am[i] : 0;
+                        eS &= 2 * N - 1;
+                        const double *kc = kq + (size_t)S * step_words;
+                        const bool fold = (S & 3) == 3;
+                        // (the transformed digits are read from buf again per subset: hoisted out of this loop, their 16
+                        // values would stay live beside the sums)
+                        asm volatile("" ::: "memory");
+#pragma unroll
+                        for (int m = 0; m < PT; m++) {
+                            const int s = tid + m * L64_THREADS;
+                            double d0 = buf[s], d1 = buf[N + s];
+                            if (S) { // (M(0) = 1)
+                                const int ex = 2 * (int)(__brev((unsigned)s) >> (32 - LOGN)) + 1; // expo(s)
+                                const int at = (ex * eS) & (2 * N - 1);
+                                d0 = mulmod<L0>(d0, psi_pow[at]);
+                                d1 = mulmod<L1>(d1, psi_pow[2 * N + at]);
+                            }
+                            double s0 = sum[0][m] + mulmod<L0>(d0, kc[s]), s1 = sum[1][m] + mulmod<L1>(d1, kc[N + s]);
+                            if (fold) {
+                                s0 = reduce<L0>(s0); // <= 0.5 p + 4 x 0.59 p before
+                                s1 = reduce<L1>(s1);
+                            }
+                            sum[0][m] = s0;
+                            sum[1][m] = s1;
+                        }
+                    }
+                    // (no barrier: the next digits, or the column below, overwrite this thread's own positions only)
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < PT; m++) {
+                const int s = tid + m * L64_THREADS;
+                buf[s] = reduce<L0>(sum[0][m]);
+                buf[N + s] = reduce<L1>(sum[1][m]);
+            }
+            __syncthreads();
+            n8192_ntt_inverse(buf, twi0, twi1);
+            // CRT lift as above; the lifted value replaces the accumulator row's word at own positions
+#pragma unroll
+            for (int m = 0; m < PT; m++) {
+                const int j = tid + m * L64_THREADS;
+                const double r0 = buf[j], r1 = buf[N + j];
+                const double tq = reduce<L1>(mulmod<L1>(r1 - r0, p0inv_mod_p1));
+                HELM_BOUND(__builtin_fabs(r0) < 0x1p51 && __builtin_fabs(tq) < 0x1p51, 4);
+                acc[(unsigned)c * N + own + m] = (uint64_t)to_int64(r0) + L0::P_U64 * (uint64_t)to_int64(tq);
             }
         }
         __syncthreads(); // (B)

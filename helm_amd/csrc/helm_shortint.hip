@@ -1711,10 +1711,24 @@ hipError_t launch_pbs64_large(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
         return hipSuccess;
     }
     if (ctx->logN != 12 || ctx->P.k != 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pbs64_large<12>, dim3((unsigned)count), dim3(L64_THREADS), K.large_lds, ctx->stream, jobs, small, luts,
-                       K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], out, ctx->P.n, ctx->P.pbs_l, ctx->P.pbs_logB,
-                       K.p0inv_mod_p1);
+    if (K.group > 1 && !K.psi_pow) return hipErrorInvalidValue;
+#define LARGE64_LAUNCH(GG)                                                                                                   \
+    hipLaunchKernelGGL((k_pbs64_large<12, GG>), dim3((unsigned)count), dim3(L64_THREADS), K.large_lds, ctx->stream, jobs, small, \
+                       luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.pbs_l,               \
+                       ctx->P.pbs_logB, K.p0inv_mod_p1)
+    if (K.group == 3) LARGE64_LAUNCH(3);
+    else if (K.group == 2) LARGE64_LAUNCH(2);
+    else LARGE64_LAUNCH(0);
+#undef LARGE64_LAUNCH
     return hipGetLastError();
+}
+
+// group: the multi-bit grouping factor (2 or 3), anything else: the classical form
+const void *pbs64_large_kernel(int group)
+{
+    return group == 3   ? reinterpret_cast<const void *>(k_pbs64_large<12, 3>)
+           : group == 2 ? reinterpret_cast<const void *>(k_pbs64_large<12, 2>)
+                        : reinterpret_cast<const void *>(k_pbs64_large<12, 0>);
 }
 
 // k_pbs64_n8192: k = 1, N = 8192 (helm_si_ctx_create_ex with HELM_SI_CREATE_N8192)
@@ -1734,14 +1748,28 @@ hipError_t launch_pbs64_n8192(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
     if (ctx->logN != N8192_LOGN || ctx->P.k != 1) return hipErrorInvalidValue;
     const int64_t rows = std::max(ctx->n_cus, 1); // (the rows of d_acc8192: alloc_acc8192)
     if (!ctx->d_acc8192) return hipErrorInvalidValue;
+    if (K.group > 1 && !K.psi_pow) return hipErrorInvalidValue;
+#define N8192_LAUNCH(GG)                                                                                                     \
+    hipLaunchKernelGGL(k_pbs64_n8192<GG>, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds, ctx->stream, jobs + off, small, \
+                       luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->d_acc8192, ctx->P.n,              \
+                       ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1)
     for (int64_t off = 0; off < count; off += rows) {
         const int64_t chunk = std::min(rows, count - off);
-        hipLaunchKernelGGL(k_pbs64_n8192, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds, ctx->stream, jobs + off, small,
-                           luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], out, ctx->d_acc8192, ctx->P.n, ctx->P.pbs_l,
-                           ctx->P.pbs_logB, K.p0inv_mod_p1);
+        if (K.group == 3) N8192_LAUNCH(3);
+        else if (K.group == 2) N8192_LAUNCH(2);
+        else N8192_LAUNCH(0);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
+#undef N8192_LAUNCH
     return hipSuccess;
+}
+
+// group: the multi-bit grouping factor (2 or 3), anything else: the classical form
+const void *pbs64_n8192_kernel(int group)
+{
+    return group == 3   ? reinterpret_cast<const void *>(k_pbs64_n8192<3>)
+           : group == 2 ? reinterpret_cast<const void *>(k_pbs64_n8192<2>)
+                        : reinterpret_cast<const void *>(k_pbs64_n8192<0>);
 }
 
 template <int LOGN, int GG>
@@ -2429,6 +2457,13 @@ bool si_large_domain(const helm_si_params &P)
     return P.k == 1 && P.N == 4096 && P.pbs_l >= 1 && P.grouping_factor <= 1;
 }
 
+// the multi-bit shapes the two large-N kernels take under HELM_SI_CREATE_LARGE_MULTIBIT beside the bit of their N (4096:
+// k_pbs64_large, 8192: k_pbs64_n8192): grouping_factor 2 or 3 (that it divides n is checked with n)
+bool si_large_multibit_domain(const helm_si_params &P, int N)
+{
+    return P.k == 1 && P.N == N && P.pbs_l >= 1 && P.grouping_factor >= 2 && P.grouping_factor <= 3;
+}
+
 // A context whose launches run k_pbs64_large: the inverse twiddle tables of the pair FpG / FpI, the kernel's LDS attribute
 // and its occupancy.
 int setup_large(helm_si_ctx *ctx)
@@ -2451,8 +2486,9 @@ int setup_large(helm_si_ctx *ctx)
     }
     // the attribute is the kernel's, shared by every context of the process: the layout at the largest n
     static std::atomic<bool> attr_done[64];
-    const void *kern = reinterpret_cast<const void *>(k_pbs64_large<12>);
-    HIP_TRY(lds_attr_once(attr_done, ctx->device, {kern}, Large64Lds(N, 1024).bytes));
+    const void *kern = pbs64_large_kernel(P.grouping_factor);
+    HIP_TRY(lds_attr_once(attr_done, ctx->device, {pbs64_large_kernel(0), pbs64_large_kernel(2), pbs64_large_kernel(3)},
+                          Large64Lds(N, 1024).bytes));
     K.large_lds = Large64Lds(N, P.n).bytes;
     int nb = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, L64_THREADS, K.large_lds));
@@ -2463,8 +2499,8 @@ int setup_large(helm_si_ctx *ctx)
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_si] k_pbs64_large N=%d l=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.pbs_l,
-                K.large_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.large_per_cu);
+        fprintf(stderr, "[helm_si] k_pbs64_large N=%d l=%d g=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.pbs_l,
+                P.grouping_factor > 1 ? P.grouping_factor : 1, K.large_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.large_per_cu);
     }
     return 0;
 #endif
@@ -2507,8 +2543,9 @@ int setup_n8192(helm_si_ctx *ctx)
     }
     // the attributes are the kernels', shared by every context of the process: the layout at the largest n
     static std::atomic<bool> attr_done[64], conv_done[64];
-    const void *kern = reinterpret_cast<const void *>(k_pbs64_n8192);
-    HIP_TRY(lds_attr_once(attr_done, ctx->device, {kern}, N8192Lds(1024).bytes));
+    const void *kern = pbs64_n8192_kernel(P.grouping_factor);
+    HIP_TRY(lds_attr_once(attr_done, ctx->device, {pbs64_n8192_kernel(0), pbs64_n8192_kernel(2), pbs64_n8192_kernel(3)},
+                          N8192Lds(1024).bytes));
     HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_n8192)},
                           sizeof(double) * 2 * (size_t)N));
     K.n8192_lds = N8192Lds(P.n).bytes;
@@ -2521,8 +2558,8 @@ int setup_n8192(helm_si_ctx *ctx)
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_si] k_pbs64_n8192 l=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", P.pbs_l,
-                K.n8192_lds, fa.numRegs, (size_t)fa.localSizeBytes, nb);
+        fprintf(stderr, "[helm_si] k_pbs64_n8192 l=%d g=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", P.pbs_l,
+                P.grouping_factor > 1 ? P.grouping_factor : 1, K.n8192_lds, fa.numRegs, (size_t)fa.localSizeBytes, nb);
     }
     return 0;
 #endif
@@ -2592,16 +2629,23 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     const bool large = (flags & HELM_SI_CREATE_LARGE_N) != 0 && P.N >= 4096 && !n8192;
     // HELM_SI_CREATE_PBS_KS changes no admission rule: the checks below see the flags without it
     const bool pbs_ks = (flags & HELM_SI_CREATE_PBS_KS) != 0;
+    // HELM_SI_CREATE_LARGE_MULTIBIT matters for grouping_factor > 1 at N >= 4096 only, beside the bit of that N
+    const bool large_mb_bit = (flags & HELM_SI_CREATE_LARGE_MULTIBIT) != 0;
+    const bool large_mb = large_mb_bit && (large || n8192) && P.grouping_factor > 1;
     if (flags & ~(HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC | HELM_SI_CREATE_GENERIC_MULTIBIT |
-                  HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192))
+                  HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192 | HELM_SI_CREATE_LARGE_MULTIBIT))
         return fail(HELM_ERR_INVALID, "unknown bits in flags " + std::to_string(flags) +
                                           " (HELM_SI_CREATE_ALLOW_GENERIC = 1, HELM_SI_CREATE_FORCE_GENERIC = 2, "
                                           "HELM_SI_CREATE_GENERIC_MULTIBIT = 16" +
                                           ((flags & HELM_SI_CREATE_LARGE_N) ? ", HELM_SI_CREATE_LARGE_N = 32" : "") +
                                           (pbs_ks ? ", HELM_SI_CREATE_PBS_KS = 64" : "") +
                                           ((flags & HELM_SI_CREATE_N8192) ? ", HELM_SI_CREATE_N8192 = 256" : "") +
+                                          (large_mb_bit ? ", HELM_SI_CREATE_LARGE_MULTIBIT = 1024" : "") +
                                           "; 4 and 8 are reserved)");
-    flags &= ~(HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192);
+    if (large_mb_bit && !(flags & (HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_N8192)))
+        return fail(HELM_ERR_INVALID, "flags " + std::to_string(flags) + ": HELM_SI_CREATE_LARGE_MULTIBIT goes with "
+                                          "HELM_SI_CREATE_LARGE_N and/or HELM_SI_CREATE_N8192");
+    flags &= ~(HELM_SI_CREATE_LARGE_N | HELM_SI_CREATE_PBS_KS | HELM_SI_CREATE_N8192 | HELM_SI_CREATE_LARGE_MULTIBIT);
     const bool force = (flags & HELM_SI_CREATE_FORCE_GENERIC) != 0;
     const bool multibit = (flags & HELM_SI_CREATE_GENERIC_MULTIBIT) != 0;
     if (multibit && !(flags & (HELM_SI_CREATE_ALLOW_GENERIC | HELM_SI_CREATE_FORCE_GENERIC)))
@@ -2610,11 +2654,16 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (force && P.grouping_factor > 1 && !multibit)
         return fail(HELM_ERR_INVALID, "HELM_SI_CREATE_FORCE_GENERIC: the generic kernel has no multi-bit form (grouping_factor > 1)");
     // with HELM_SI_CREATE_GENERIC_MULTIBIT a multi-bit shape is tuned only where the tuned multi-bit build serves it
-    if (large && !si_large_domain(P))
+    if (large_mb && !si_large_multibit_domain(P, large ? 4096 : 8192))
+        return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the multi-bit form of the large-N kernels: the domain under "
+                                      "HELM_SI_CREATE_LARGE_MULTIBIT is k = 1, pbs_l >= 1, grouping_factor 2 or 3 dividing n, at "
+                                      "N = 4096 beside HELM_SI_CREATE_LARGE_N and at N = 8192 beside HELM_SI_CREATE_N8192 (k > 1, "
+                                      "grouping_factor >= 4 and N >= 16384 are out of scope)");
+    if (large && !large_mb && !si_large_domain(P))
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the large-N kernel: its domain under HELM_SI_CREATE_LARGE_N is "
                                       "k = 1, N = 4096, pbs_l >= 1, grouping_factor <= 1 (k > 1 at N = 4096, multi-bit at "
                                       "N = 4096 and N = 8192 are out of scope)");
-    if (n8192 && !si_n8192_domain(P))
+    if (n8192 && !large_mb && !si_n8192_domain(P))
         return fail(HELM_ERR_INVALID, "unsupported (k,N,pbs_l) for the N = 8192 kernel: its domain under HELM_SI_CREATE_N8192 is "
                                       "k = 1, N = 8192, pbs_l >= 1, grouping_factor <= 1 (k > 1 at N = 8192, multi-bit at "
                                       "N = 8192 and N >= 16384 are out of scope)");
@@ -2644,7 +2693,7 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     const int group = P.grouping_factor > 1 ? P.grouping_factor : 1;
     if (P.grouping_factor < 0 || group > 3 || P.n % group)
         return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
-    if (group > 1 && !gen_mb && !(P.pbs_l == 1 && P.N >= 1024))
+    if (group > 1 && !gen_mb && !large_mb && !(P.pbs_l == 1 && P.N >= 1024))
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation is built for pbs_l = 1, N >= 1024 (every tfhe multi-bit set)");
     // exactness: |sum| <= (k+1) * l * N * (B/2) * 2^63 must stay below p0 * p1 / 2
     {
@@ -2706,9 +2755,10 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
         }
     }
     K.group = group;
-    if (group > 1) { // the 2N powers of psi per field: monomial products in the transform domain
+    if (group > 1) { // the 2N powers of psi per field of the context's pair: monomial products in the transform domain
         std::vector<double> pw((size_t)4 * N);
-        for (int f = 0; f < 2; f++) power_table(pw.data() + (size_t)f * 2 * N, si_psi(N, 0, f), si_modulus(0, f), 2 * N, 0);
+        const int pair = large_mb ? 2 : 0;
+        for (int f = 0; f < 2; f++) power_table(pw.data() + (size_t)f * 2 * N, si_psi(N, pair, f), si_modulus(pair, f), 2 * N, 0);
         HIP_TRY(hipMalloc(&K.psi_pow, pw.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(K.psi_pow, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -2901,12 +2951,15 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         // N = 2048, logB = 21, g = 3 stays at 0.71 of the limit); this one is sufficient for the key at hand and every input.
         // A key beyond it is refused before anything of the context is touched: the context keeps the key and state it had.
         const size_t subsets = (size_t)1 << K.group;
+        // (a large-N or N = 8192 context computes in its own pair: p0 p1 / 2 = 2^97.87)
+        const long double half = (K.large || K.n8192) ? (long double)L0::P * (long double)L1::P / 2
+                                                      : (long double)F0::P * (long double)F1::P / 2;
         const long double key_bound = key_step_bound(P, bsk_std, n_ggsw / subsets, subsets * per_ggsw);
-        if (key_bound * 1.001L >= (long double)F0::P * (long double)F1::P / 2) {
+        if (key_bound * 1.001L >= half) {
             char ratio[32];
-            snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / ((long double)F0::P * (long double)F1::P / 2));
+            snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / half);
             return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the ") +
-                                              (K.gen ? "generic" : "tuned") + " multi-bit kernel: its largest group sum is " +
+                                              (K.n8192 ? "N = 8192" : K.large ? "large-N" : K.gen ? "generic" : "tuned") + " multi-bit kernel: its largest group sum is " +
                                               ratio + " of p0 p1 / 2");
         }
     }
@@ -2916,7 +2969,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     } t_std; // freed on every return path
     HIP_TRY(hipMalloc(&t_std.p, n_words * sizeof(uint64_t)));
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
-    if (!K.bsk && (K.group == 1 || K.gen)) HIP_TRY(hipMalloc(&K.bsk, n_words * 2 * sizeof(double)));
+    if (!K.bsk && (K.group == 1 || K.gen || K.large || K.n8192)) HIP_TRY(hipMalloc(&K.bsk, n_words * 2 * sizeof(double)));
     if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && K.group == 1 && !K.gen) {
         // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
         // every k = 1 set's): the CRT pair follows the key at hand, a step being one GGSW (src is [i][lev][r][c][N]).  With the
@@ -2981,7 +3034,7 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (K.group > 1 && !K.gen && !K.expo) { // (the generic kernel derives its spectrum positions: helm_pbs64_generic.inc)
+    if (K.group > 1 && !K.gen && !K.large && !K.n8192 && !K.expo) { // (the generic and large-N kernels derive their spectrum positions)
         if (int rc = probe_spectrum_positions(ctx)) return rc;
     }
     K.have_bsk = true;

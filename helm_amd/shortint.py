@@ -116,6 +116,7 @@ SI_CREATE_GENERIC_MULTIBIT = 16
 SI_CREATE_LARGE_N = 32
 SI_CREATE_PBS_KS = 64
 SI_CREATE_N8192 = 256
+SI_CREATE_LARGE_MULTIBIT = 1024
 _ORDER_FLAGS = {"ks_pbs": 0, "pbs_ks": SI_CREATE_PBS_KS}
 _GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_FORCE_GENERIC,
                   "allow+multibit": SI_CREATE_ALLOW_GENERIC | SI_CREATE_GENERIC_MULTIBIT,
@@ -124,7 +125,10 @@ _GENERIC_FLAGS = {None: 0, "allow": SI_CREATE_ALLOW_GENERIC, "force": SI_CREATE_
                   "force+large": SI_CREATE_FORCE_GENERIC | SI_CREATE_LARGE_N,
                   "n8192": SI_CREATE_N8192, "allow+n8192": SI_CREATE_ALLOW_GENERIC | SI_CREATE_N8192,
                   "force+n8192": SI_CREATE_FORCE_GENERIC | SI_CREATE_N8192,
-                  "large+n8192": SI_CREATE_LARGE_N | SI_CREATE_N8192}
+                  "large+n8192": SI_CREATE_LARGE_N | SI_CREATE_N8192,
+                  "large+multibit": SI_CREATE_LARGE_N | SI_CREATE_LARGE_MULTIBIT,
+                  "n8192+multibit": SI_CREATE_N8192 | SI_CREATE_LARGE_MULTIBIT,
+                  "large+n8192+multibit": SI_CREATE_LARGE_N | SI_CREATE_N8192 | SI_CREATE_LARGE_MULTIBIT}
 
 
 class SiServerKey:
@@ -140,8 +144,10 @@ class SiServerKey:
     message_modulus * carry_modulus = 32 - is admitted and runs on the large-N kernel; any smaller shape behaves as without
     it.  "n8192" (alone, or as "allow+n8192" / "force+n8192" / "large+n8192") adds HELM_SI_CREATE_N8192: k = 1, N = 8192 - the
     6-bit sets, message_modulus * carry_modulus = 64, the space of a 6-input look-up table - is admitted and runs on the
-    N = 8192 kernel; any smaller shape behaves as without it, and under "large+n8192" N selects the kernel.  Lanes inherit the
-    setting.
+    N = 8192 kernel; any smaller shape behaves as without it, and under "large+n8192" N selects the kernel.
+    "large+multibit", "n8192+multibit" and "large+n8192+multibit" add HELM_SI_CREATE_LARGE_MULTIBIT to those: multi-bit shapes
+    (grouping_factor 2 or 3) at N = 4096 / N = 8192 run on the multi-bit form of the same kernels; the bootstrapping key must
+    pass the load-time capacity check of that pair of fields (include/helm_shortint.h).  Lanes inherit the setting.
 
     order: "ks_pbs" (the default: the flags are passed as without it) keeps ciphertexts under the big key, a look-up is
     keyswitch, then bootstrap; "pbs_ks" adds HELM_SI_CREATE_PBS_KS: wire rows are n + 1 words under the small key
@@ -154,6 +160,7 @@ class SiServerKey:
         if generic not in _GENERIC_FLAGS:
             raise ValueError("generic must be None, 'allow', 'force', 'allow+multibit', 'force+multibit', 'large', "
                              "'allow+large' or 'force+large', or 'n8192', 'allow+n8192', 'force+n8192' or 'large+n8192', "
+                             "or 'large+multibit', 'n8192+multibit' or 'large+n8192+multibit', "
                              f"not {generic!r}")
         self.params = client_key.params if client_key is not None else params
         self.generic = generic

@@ -86,7 +86,9 @@ enum {
     HELM_SI_CREATE_LARGE_N = 32, /* admit k = 1, N = 4096 (the 5-bit shortint sets): it runs on the large-N kernel */
     HELM_SI_CREATE_PBS_KS = 64, /* bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words under the small key */
     /* 128 is not assigned: refused as an unknown bit */
-    HELM_SI_CREATE_N8192 = 256 /* admit k = 1, N = 8192 (the 6-bit shortint sets): it runs on the N = 8192 kernel */
+    HELM_SI_CREATE_N8192 = 256, /* admit k = 1, N = 8192 (the 6-bit shortint sets): it runs on the N = 8192 kernel */
+    /* 512 is not assigned: refused as an unknown bit */
+    HELM_SI_CREATE_LARGE_MULTIBIT = 1024 /* with 32 and/or 256: multi-bit shapes at N = 4096 / 8192 run on those kernels */
 };
 /* helm_si_ctx_create with flags.  flags = 0 is helm_si_ctx_create: the same checks in the same order, the same messages.
  * With either flag, a shape no tuned build covers is admitted when it lies in the generic kernel's domain - N in {256, 512,
@@ -153,7 +155,21 @@ enum {
  * unchanged: keyswitch at in_dim = 8192, many-LUT, both look-up orders, lanes, audit, sharding.  Refused with a message that
  * names HELM_SI_CREATE_N8192: k > 1 at N = 8192, multi-bit at N = 8192, and N >= 16384.  helm_wop_ctx_create refuses a
  * PBS-side context of this class by name, and the bound-checking build refuses the class at creation.
- * Unknown flag bits (4 and 8 are reserved, 128 is not assigned): HELM_ERR_INVALID. */
+ * HELM_SI_CREATE_LARGE_MULTIBIT (only together with HELM_SI_CREATE_LARGE_N and/or HELM_SI_CREATE_N8192; alone, or beside the
+ * generic bits only, it is HELM_ERR_INVALID) opens the multi-bit form of the two kernels above: with bit 32 it admits k = 1,
+ * N = 4096, pbs_l >= 1, grouping_factor 2 or 3 dividing n on k_pbs64_large (class 2, field bits 50); with bit 256 the same at
+ * N = 8192 on k_pbs64_n8192 (class 3, round capacity = CU count); with both, N selects the kernel.  Every other check applies
+ * in the same order.  The bit changes nothing (same status, message, class and field) for grouping_factor <= 1 and for any
+ * N < 4096; HELM_SI_CREATE_PBS_KS beside it changes no admission rule, as beside every other bit.
+ * Refused with a message that names the bit: k > 1, grouping_factor >= 4 or not dividing n, N >= 16384.  helm_wop_ctx_create
+ * and the bound-checking build refuse these contexts by their class.  As for HELM_SI_CREATE_GENERIC_MULTIBIT, the
+ * creation-time capacity check stays the classical one, a necessary condition only: helm_si_load_bootstrap_key applies the
+ * group-sum rule above with the product of THIS pair, p0 p1 / 2 = 2^97.87, margin 1.001, and refuses a key beyond it with a
+ * "capacity" message that names the large-N or the N = 8192 multi-bit kernel and gives the ratio; the context keeps the key
+ * and state it had.  A uniformly random key loads when pbs_l 2^(pbs_logB + grouping_factor + 62 + log2 N) is below that:
+ * one level at N = 4096 up to pbs_logB + grouping_factor = 23, at N = 8192 up to 22; two levels of 15 bits at every grouping
+ * factor.  So N = 8192, one level of 21 bits, grouping factor 2 is admitted here and refused at load.
+ * Unknown flag bits (4 and 8 are reserved, 128 and 512 are not assigned): HELM_ERR_INVALID. */
 int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out);
 /* Which kernel runs this context's bootstraps: 0 = a tuned build, 1 = the generic kernel (k_pbs64_generic), 2 = the large-N
  * kernel (k_pbs64_large: k = 1, N = 4096 under HELM_SI_CREATE_LARGE_N, whatever generic bits stand beside it), 3 = the

@@ -72,6 +72,7 @@ pub const HELM_SI_CREATE_GENERIC_MULTIBIT: i32 = 16; // with one of the two abov
 pub const HELM_SI_CREATE_LARGE_N: i32 = 32; // admit k = 1, N = 4096 (the 5-bit shortint sets): the large-N kernel
 pub const HELM_SI_CREATE_PBS_KS: i32 = 64; // bootstrap-first order (tfhe's *_PBS_KS sets): wire rows of n + 1 words
 pub const HELM_SI_CREATE_N8192: i32 = 256; // admit k = 1, N = 8192 (the 6-bit shortint sets): the N = 8192 kernel
+pub const HELM_SI_CREATE_LARGE_MULTIBIT: i32 = 1024; // with 32 and/or 256: the multi-bit form of those two kernels
 
 // include/helm_host.h `helm_radix_kind` / `helm_radix_op`: one FheUintN operator of a level (gates.rs:306-702)
 pub const HELM_RADIX_COPY: i32 = 0;
