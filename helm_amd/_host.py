@@ -32,6 +32,8 @@ HOST_API = {
     "helm_host_pack_levels_costed": (C.c_int, [C.POINTER(C.c_int32)] * 5 + [C.POINTER(C.c_int64), C.c_int64, C.c_int64,
                                                 C.POINTER(C.c_double)] + [C.POINTER(C.c_int64)] * 3),
     "helm_host_shard_bounds": (C.c_int64, [C.POINTER(C.c_int32), C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "helm_host_wide_lut_groups": (C.c_int64, [C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "helm_host_wide_lut_group_cap": (C.c_int64, [C.c_int32]),
     "helm_host_enc_map_new": (C.c_int, [vp, C.POINTER(vp)]),
     "helm_host_enc_map_free": (None, [vp]),
     "helm_host_enc_map_insert": (C.c_int, [vp, cp, u32p]),
@@ -58,6 +60,7 @@ HOST_API = {
     "helm_host_si_circuit_evaluate_ready": (C.c_int, [vp, vp, vp]),
     "helm_host_si_circuit_decrypt_outputs": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp)]),
     "helm_host_si_circuit_set_wopbs": (C.c_int, [vp, vp, C.c_int]),
+    "helm_host_si_circuit_set_wopbs_share": (C.c_int, [vp, C.c_int]),
     "helm_host_si_circuit_add_lane": (C.c_int, [vp, vp]),
     "helm_host_si_circuit_set_lazy_carries": (C.c_int, [vp, C.c_int]),
     "helm_host_si_circuit_set_round_capacity": (C.c_int, [vp, C.c_int64]),

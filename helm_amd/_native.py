@@ -297,6 +297,9 @@ WOP_API = {
     "helm_wop_table_words": (C.c_size_t, [C.POINTER(WopParams), C.c_int32]),
     "helm_wop_make_table": (C.c_int, [C.POINTER(WopParams), C.c_int32, C.c_int32, u64p, C.c_size_t, u64p]),
     "helm_wop_eval_luts": (C.c_int, [vp, vp, i32p, C.c_int32, C.c_int32, u64p, i32p, C.c_int64]),
+    "helm_wop_eval_many_luts": (C.c_int, [vp, vp, i32p, C.c_int32, C.c_int32, u64p, i32p, C.c_int32, C.c_int64]),
+    "helm_wop_many_form": (C.c_int, [vp, C.c_int32, C.c_int32]),
+    "helm_wop_vertical_packing_many_batch": (C.c_int, [vp, u64p, C.c_int32, u64p, C.c_int32, u64p, C.c_int64]),
     "helm_wop_extract_bits_batch": (C.c_int, [vp, u64p, C.c_int32, C.c_int32, u64p, C.c_int64]),
     "helm_wop_circuit_bootstrap_batch": (C.c_int, [vp, u64p, u64p, C.c_int64]),
     "helm_wop_vertical_packing_batch": (C.c_int, [vp, u64p, C.c_int32, u64p, u64p, C.c_int64]),

@@ -490,7 +490,11 @@ int circuit_bootstrap_device(helm_wop_ctx *ctx, int64_t T, uint64_t *d_bits_rows
 
 // per gate `bits` GGSWs in d_ggsw_ntt (index 0 = least significant), tables [G][max(2^bits, N)] on the device
 // -> d_vp rows [G] (WoP big key)
-int vertical_packing_device(helm_wop_ctx *ctx, int64_t G, int bits, const uint64_t *d_tables)
+// Several tables on one input tuple (helm_wop_eval_many_luts): one job per table, job j reads the GGSWs of key
+// (key_off + j) / key_div, key_div = tables per tuple - the jobs of a tuple share its GGSWs.  The defaults are the single
+// gate's: job j reads key j.
+int vertical_packing_device(helm_wop_ctx *ctx, int64_t G, int bits, const uint64_t *d_tables, int64_t key_off = 0,
+                            int key_div = 1)
 {
     helm_si_ctx *W = ctx->wop;
     const helm_wop_params &P = ctx->P;
@@ -500,8 +504,10 @@ int vertical_packing_device(helm_wop_ctx *ctx, int64_t G, int bits, const uint64
     const size_t per_ggsw = (size_t)K1 * K1 * P.cbs_l * 2 * N; // doubles
     const size_t key_stride = per_ggsw * bits;
     const size_t half = (size_t)G * ((leaves + 1) / 2);
+    if (key_div < 1) return fail(HELM_ERR_INVALID, "vertical packing: bad key divisor");
     if (ctx->d_glwe.ensure(((size_t)G * leaves + half) * glwe) || ctx->d_vp.ensure((size_t)G * (dim + 1)))
         return fail(HELM_ERR_OOM, "WoP-PBS scratch (vertical packing)");
+    const auto key_of = [&](int64_t g) { return (int32_t)((key_off + g) / key_div); };
     JobArena A;
     // synthetic small LWE: mask word i switches to -2^i (mod 2N), body to 0: step i multiplies by X^(-2^i bit_i)
     std::vector<uint64_t> rot((size_t)nbr + 1, 0);
@@ -516,13 +522,13 @@ int vertical_packing_device(helm_wop_ctx *ctx, int64_t G, int bits, const uint64
             for (int64_t g = 0; g < G; g++)
                 for (size_t q = 0; q < rows_out; q++)
                     cj[(size_t)g * rows_out + q] = Pbs64Job{(int32_t)(g * rows_in + 2 * q + 1), (int32_t)(g * rows_in + 2 * q),
-                                                            (int32_t)(g * rows_out + q), (int32_t)g};
+                                                            (int32_t)(g * rows_out + q), key_of(g)};
             off_tree[(size_t)lev] = A.put(cj);
             rows_in = rows_out;
         }
     }
     std::vector<Pbs64Job> bj((size_t)G);
-    for (int64_t g = 0; g < G; g++) bj[(size_t)g] = Pbs64Job{0, (int32_t)g, (int32_t)g, (int32_t)g};
+    for (int64_t g = 0; g < G; g++) bj[(size_t)g] = Pbs64Job{0, (int32_t)g, (int32_t)g, key_of(g)};
     const size_t off_br = A.put(bj);
     if (ctx->d_jobs.ensure(A.host.size())) return fail(HELM_ERR_OOM, "WoP-PBS jobs");
     HIP_TRY(hipMemcpyAsync(ctx->d_jobs.p, A.host.data(), A.host.size(), hipMemcpyHostToDevice, W->stream));
@@ -551,6 +557,13 @@ int wop_upload(helm_wop_ctx *ctx, DevBuf<uint64_t> &buf, const uint64_t *host, s
     HIP_TRY(hipMemcpyAsync(buf.p, host, words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->wop->stream));
     return 0;
 }
+
+// How stage 5 serves n_out tables on one input tuple (helm_wop_many_form): 0 single - one table, the launch of a single gate;
+// 1 shared - one job per table, the jobs of a tuple read the same GGSWs.  (A packed form - the tuple's tables side by side in
+// one polynomial where n_out 2^bits <= N, one rotation, n_out sample extracts through a launch argument of k_pbs64<., 1> - was
+// built and measured at the S-box shape: 48.10 ms against the shared form's 48.27 ms per 256 outputs, inside the spreads;
+// it was deleted, DESIGN 4.8.  Value 2 stays reserved for it.)
+int wop_many_form_rule(int64_t n_out) { return n_out <= 1 ? 0 : 1; }
 
 } // namespace
 
@@ -778,6 +791,37 @@ int helm_wop_vertical_packing_batch(helm_wop_ctx *ctx, const uint64_t *ggsw, int
     return 0;
 }
 
+int helm_wop_many_form(const helm_wop_ctx *ctx, int32_t bits, int32_t n_out)
+{
+    if (!ctx) return fail(HELM_ERR_INVALID, "null ctx");
+    if (bits < 1 || bits > ctx->logN + 6 || n_out < 1) return fail(HELM_ERR_INVALID, "many_form: 1..log2(N)+6 bits, n_out >= 1");
+    return wop_many_form_rule(n_out);
+}
+
+int helm_wop_vertical_packing_many_batch(helm_wop_ctx *ctx, const uint64_t *ggsw, int32_t bits, const uint64_t *tables,
+                                         int32_t n_out, uint64_t *out_big, int64_t count)
+{
+    if (!ctx || !ggsw || !tables || !out_big || count < 0) return fail(HELM_ERR_INVALID, "bad argument");
+    if (bits < 1 || bits > ctx->logN + 6) return fail(HELM_ERR_INVALID, "vertical_packing: 1..log2(N)+6 bits");
+    if (n_out < 1 || count * n_out > INT32_MAX) return fail(HELM_ERR_INVALID, "vertical_packing: n_out >= 1, count * n_out rows must fit the row index");
+    if (count == 0) return 0;
+    helm_si_ctx *W = ctx->wop;
+    HIP_TRY(hipSetDevice(W->device));
+    const helm_wop_params &P = ctx->P;
+    const size_t per = (size_t)P.cbs_l * (P.k + 1) * (P.k + 1) * P.N, brow = (size_t)P.k * P.N + 1;
+    const size_t n_ggsw = (size_t)count * bits;
+    if (int rc = wop_upload(ctx, ctx->d_ggsw, ggsw, n_ggsw * per)) return rc;
+    if (ctx->d_ggsw_ntt.ensure(n_ggsw * per * 2)) return fail(HELM_ERR_OOM, "WoP-PBS scratch (GGSWs)");
+    HIP_TRY(launch_convert_ggsw(ctx, ctx->d_ggsw.p, ctx->d_ggsw_ntt.p, n_ggsw));
+    const size_t tw = helm_wop_table_words(&P, bits);
+    if (int rc = wop_upload(ctx, ctx->d_tables, tables, (size_t)count * n_out * tw)) return rc;
+    if (int rc = vertical_packing_device(ctx, count * n_out, bits, ctx->d_tables.p, 0, n_out)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_big, ctx->d_vp.p, (size_t)count * n_out * brow * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                           W->stream));
+    HIP_TRY(hipStreamSynchronize(W->stream));
+    return 0;
+}
+
 size_t helm_wop_table_words(const helm_wop_params *params, int32_t total_bits)
 {
     if (!params || total_bits < 0 || total_bits > 40) return 0;
@@ -818,8 +862,18 @@ int helm_wop_make_table(const helm_wop_params *params, int32_t n_blocks, int32_t
 int helm_wop_eval_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, int32_t n_inputs,
                        int32_t bits_per_block, const uint64_t *tables, const int32_t *out_idx, int64_t count)
 {
+    return helm_wop_eval_many_luts(ctx, w, in_idx, n_inputs, bits_per_block, tables, out_idx, 1, count);
+}
+
+// `count` groups of n_out tables on one input tuple each; n_out = 1 is a batch of single gates, launch for launch
+int helm_wop_eval_many_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, int32_t n_inputs,
+                            int32_t bits_per_block, const uint64_t *tables, const int32_t *out_idx, int32_t n_out,
+                            int64_t count)
+{
     if (int rc = wop_ready(ctx, true)) return rc;
     if (!w || !in_idx || !tables || !out_idx || count < 0) return fail(HELM_ERR_INVALID, "bad argument");
+    if (n_out < 1) return fail(HELM_ERR_INVALID, "WoP-PBS: n_out must be at least 1");
+    if (count * n_out > INT32_MAX) return fail(HELM_ERR_INVALID, "WoP-PBS: count * n_out outputs do not fit the row index");
     if (w->owner != ctx->pbs) return fail(HELM_ERR_INVALID, "wire table belongs to another context");
     const helm_wop_params &P = ctx->P;
     int tl = 0;
@@ -830,15 +884,20 @@ int helm_wop_eval_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_id
     if (bits > ctx->logN + 6) return fail(HELM_ERR_INVALID, "WoP-PBS: more than log2(N) + 6 index bits");
     if (count == 0) return 0;
     if (int rc = check_rows(w, in_idx, count * n_inputs, false)) return rc;
-    if (int rc = check_rows(w, out_idx, count, false)) return rc;
+    if (int rc = check_rows(w, out_idx, count * n_out, false)) return rc;
     {
         // the gates of a call are independent: the batch runs in chunks (and, sharded, in groups per rank), each writing
         // its output rows before the next reads its inputs, so an output row that is an input row of ANOTHER gate of the
         // call would make the result depend on the chunking.  Refused; evaluate dependent gates in separate calls
         // (levels).  A gate may write over one of its own inputs: its stages read them before its last one writes.
-        std::vector<std::pair<int32_t, int64_t>> outs((size_t)count);
-        for (int64_t g = 0; g < count; g++) outs[(size_t)g] = {out_idx[g], g};
+        // (A gate here is a group: its n_out outputs are written after every stage that reads its inputs.)
+        std::vector<std::pair<int32_t, int64_t>> outs((size_t)(count * n_out));
+        for (int64_t q = 0; q < count * n_out; q++) outs[(size_t)q] = {out_idx[q], q / n_out};
         std::sort(outs.begin(), outs.end());
+        if (n_out > 1) // a group's outputs leave in passes: which of two writers of a row lands last is no property of the call
+            for (size_t q = 1; q < outs.size(); q++)
+                if (outs[q].first == outs[q - 1].first)
+                    return fail(HELM_ERR_INVALID, "WoP-PBS: two outputs of the call name row " + std::to_string(outs[q].first));
         for (int64_t g = 0; g < count; g++)
             for (int q = 0; q < n_inputs; q++) {
                 const int32_t r = in_idx[g * n_inputs + q];
@@ -863,15 +922,23 @@ int helm_wop_eval_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_id
     std::vector<uint64_t> ident((size_t)S->P.message_modulus * S->P.carry_modulus), id_lut((size_t)S->P.N);
     for (size_t v = 0; v < ident.size(); v++) ident[v] = v;
     if (int rc = helm_si_make_lut(S, ident.data(), id_lut.data())) return rc;
+    // Chunks bound the GGSW scratch (~0.6 MB per bit).  A group has `bits` GGSWs, as a single gate has, so with n_out > 1 the
+    // groups run in chunks of the same size, and within a chunk stages 5 and 6 run in passes of at most `chunk` tables:
+    // d_glwe, d_vp and d_tables never grow beyond what a chunk of single-output gates needs.
+    const int64_t chunk = std::max<int64_t>(1, 16384 / bits);
+    const int form = wop_many_form_rule(n_out);
     // gates [first, first + G) of the call through stages 1-6; the result rows go to dst (rows of the PBS-side big key):
     // row out_rows[g] of the wire table, or rows 0.. of the exchange staging buffer of a sharded call
+    // (with n_out > 1 a gate is a group: stages 1-4 once, stages 5 and 6 per output; result row g * n_out + o)
     auto run_gates = [&](int64_t first, int64_t G, uint64_t *dst, const int32_t *out_rows) -> int {
         if (G == 0) return 0;
         const int64_t R = G * n_inputs, T = G * bits;
         if (ctx->d_clean.ensure((size_t)R * (dimS + 1)) || ctx->d_wbig.ensure((size_t)R * (dimW + 1)) ||
             ctx->d_bits.ensure((size_t)T * (P.n + 1)))
             return fail(HELM_ERR_OOM, "WoP-PBS scratch");
-        if (int rc = wop_upload(ctx, ctx->d_tables, tables + (size_t)first * tw, (size_t)G * tw)) return rc;
+        if (form == 0) {
+            if (int rc = wop_upload(ctx, ctx->d_tables, tables + (size_t)first * tw, (size_t)G * tw)) return rc;
+        }
         // 1: cleaning bootstrap, PBS side (row r = gate g, input q)
         std::vector<Ks64Job> ks((size_t)R);
         std::vector<Pbs64Job> pj((size_t)R);
@@ -909,52 +976,70 @@ int helm_wop_eval_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_id
         }
         // 4: one GGSW per bit
         if (int rc = circuit_bootstrap_device(ctx, T, ctx->d_bits.p, true)) return rc;
-        // 5: table look-up
-        if (int rc = vertical_packing_device(ctx, G, bits, ctx->d_tables.p)) return rc;
-        // 6: back to the PBS side
-        ks.resize((size_t)G);
-        pj.resize((size_t)G);
-        for (int64_t g = 0; g < G; g++) {
-            ks[(size_t)g] = Ks64Job{(int32_t)g, (int32_t)g};
-            pj[(size_t)g] = Pbs64Job{(int32_t)g, 0, out_rows ? out_rows[g] : (int32_t)g, 0};
-        }
-        {
+        // 5 and 6 on result rows [r0, r0 + n) of the chunk, n rows in d_vp: back to the PBS side
+        auto way_back = [&](int64_t r0, int64_t n) -> int {
+            ks.resize((size_t)n);
+            pj.resize((size_t)n);
+            for (int64_t g = 0; g < n; g++) {
+                ks[(size_t)g] = Ks64Job{(int32_t)g, (int32_t)g};
+                pj[(size_t)g] = Pbs64Job{(int32_t)g, 0, out_rows ? out_rows[r0 + g] : (int32_t)(r0 + g), 0};
+            }
             WopTimed tm(ctx, 7);
             if (int rc = apply_luts_device(S, ctx->d_vp.p, dst, ks, pj, id_lut.data(), 1, &ctx->k_to_pbs)) return rc;
-            ctx->tacc.bootstraps += G;
+            ctx->tacc.bootstraps += n;
+            return 0;
+        };
+        if (form == 0) {
+            // 5: table look-up
+            if (int rc = vertical_packing_device(ctx, G, bits, ctx->d_tables.p)) return rc;
+            // 6: back to the PBS side
+            if (int rc = way_back(0, G)) return rc;
+        } else {
+            // shared: one job per table, the jobs of a group read the group's GGSWs; passes of at most `chunk` tables
+            for (int64_t r0 = 0; r0 < G * n_out; r0 += chunk) {
+                const int64_t n = std::min(chunk, G * n_out - r0);
+                if (r0) HIP_TRY(hipStreamSynchronize(S->stream)); // d_tables, d_vp and the job arrays of the last pass
+                if (int rc = wop_upload(ctx, ctx->d_tables, tables + ((size_t)first * n_out + r0) * tw, (size_t)n * tw)) return rc;
+                if (int rc = vertical_packing_device(ctx, n, bits, ctx->d_tables.p, r0, n_out)) return rc;
+                if (int rc = way_back(r0, n)) return rc;
+            }
         }
         HIP_TRY(hipStreamSynchronize(S->stream)); // the scratch of this chunk is reused by the next
-        ctx->tacc.gates += G;
+        ctx->tacc.gates += G * n_out;
         return 0;
     };
-    // chunks bound the GGSW scratch (~0.6 MB per bit)
-    const int64_t chunk = std::max<int64_t>(1, 16384 / bits);
     if (S->x_on && count >= S->x_min) {
         // Sharded (helm_si_set_exchange on the PBS side): the gates of a round are split into `world` contiguous chunks,
         // this rank evaluates its chunk - every stage locally, the keys are replicated - into the staging buffer, the
         // caller's all-gather brings every rank's result rows and they are scattered into the table: identical
         // ciphertexts to the unsharded call.  Every rank makes the same calls, also one whose chunk is empty.
-        const int64_t world = S->x_world;
+        // With n_out > 1 the call is cut by group: a rank's slot carries its groups' n_out result rows each (so a round takes
+        // x_cap / n_out groups per rank, as apply_many_luts_sharded does) and gathered row i n_out + o is output o of group
+        // base + i.
+        const int64_t world = S->x_world, cap = S->x_cap / n_out;
+        if (cap < 1)
+            return fail(HELM_ERR_INVALID, "WoP-PBS: n_out = " + std::to_string(n_out) + " exceeds the exchange's capacity_rows = " +
+                                              std::to_string(S->x_cap) + " (one group's outputs do not fit a rank's slot)");
         for (int64_t base = 0; base < count;) {
-            const int64_t per = std::min({count - base, S->x_cap * world, chunk * world});
+            const int64_t per = std::min({count - base, cap * world, chunk * world});
             const int64_t rows = (per + world - 1) / world;
             const int64_t lo = std::min(base + per, base + S->x_rank * rows), hi = std::min(base + per, lo + rows);
-            if (int rc = run_gates(lo, hi - lo, S->x_slot(rows), nullptr)) return rc;
-            if (int rc = si_exchange(S, rows)) return rc;
+            if (int rc = run_gates(lo, hi - lo, S->x_slot(rows * n_out), nullptr)) return rc;
+            if (int rc = si_exchange(S, rows * n_out)) return rc;
             if (int rc = drain(S)) return rc;
-            if (int rc = upload(S, S->d_idx2, out_idx + base, (size_t)per)) return rc;
-            hipLaunchKernelGGL(k_rows64, dim3((unsigned)per), dim3(256), 0, S->stream, S->x_gather, (const int32_t *)nullptr,
-                               w->d, S->d_idx2.p, dimS);
+            if (int rc = upload(S, S->d_idx2, out_idx + base * n_out, (size_t)(per * n_out))) return rc;
+            hipLaunchKernelGGL(k_rows64, dim3((unsigned)(per * n_out)), dim3(256), 0, S->stream, S->x_gather,
+                               (const int32_t *)nullptr, w->d, S->d_idx2.p, dimS);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(S->stream));
             S->x_batches++;
-            S->x_rows += rows * world;
+            S->x_rows += rows * n_out * world;
             base += per;
         }
         return 0;
     }
     for (int64_t base = 0; base < count; base += chunk)
-        if (int rc = run_gates(base, std::min(chunk, count - base), w->d, out_idx + base)) return rc;
+        if (int rc = run_gates(base, std::min(chunk, count - base), w->d, out_idx + base * n_out)) return rc;
     return 0;
 }
 

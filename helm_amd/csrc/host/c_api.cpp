@@ -269,6 +269,17 @@ int64_t helm_host_shard_bounds(const int32_t *opcode, int64_t count, int world, 
     return helm_shard::chunk_bounds(opcode, count, world, bounds);
 }
 
+int64_t helm_host_wide_lut_groups(const int32_t *in_idx, int64_t count, int32_t n_inputs, int64_t cap, int64_t *group_of)
+{
+    if ((!in_idx && count > 0) || (!group_of && count > 0) || count < 0 || n_inputs < 1 || cap < 1) {
+        g_err = "wide_lut_groups: bad argument";
+        return -1;
+    }
+    return helm_wide_share::group_gates(in_idx, count, n_inputs, cap, group_of);
+}
+
+int64_t helm_host_wide_lut_group_cap(int32_t bits) { return helm_wide_share::group_cap(bits); }
+
 int helm_host_enc_map_new(helm_hip_ctx *server_key, helm_enc_map **out)
 {
     return guard([&] {
@@ -394,6 +405,14 @@ int helm_host_si_circuit_set_wopbs(helm_si_circuit *c, helm_wop_ctx *wop, int bi
         return -1;
     }
     return guard([&] { c->lut->set_wide_lut_key(wop, bits_per_block); });
+}
+int helm_host_si_circuit_set_wopbs_share(helm_si_circuit *c, int on)
+{
+    if (!c || !c->lut) {
+        g_err = "set_wopbs_share: not a LUT-mode circuit";
+        return -1;
+    }
+    return guard([&] { c->lut->set_wide_lut_share(on != 0); });
 }
 int helm_host_si_circuit_add_lane(helm_si_circuit *c, helm_si_ctx *lane)
 {

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../many_lut_rule.h"
+#include "../wide_share_rule.h"
 #include "../../../include/helm_client.h"
 #include "../../../include/helm_wopbs.h"
 #include "../../../include/helm_hip.h"
@@ -346,6 +347,9 @@ class LutCircuit : public EvalCircuit<SiEncWireMap> {
     // Gate::evaluate_encrypted_high_precision_lut (gates.rs:721-742): LUT gates whose index does not fit one block
     // (more inputs than log2(message_modulus * carry_modulus)) go through the WoP-PBS path once a key is set
     void set_wide_lut_key(helm_wop_ctx *wop, int bits_per_block);
+    // wide gates of a level on the same input wires in the same order share cleaning, bit extraction and circuit bootstrap
+    // (helm_wop_eval_many_luts; the groups are helm_wide_share::group_gates'); pbs_per_cycle() counts what runs
+    void set_wide_lut_share(bool on) { wop_share_ = on; memo_.valid = false; }
     // The reference prints `PBS time: {} us` for every LUT gate (gates.rs:293-302); here that is one line per LUT gate
     // carrying its level's time, which costs one host synchronisation per level.  set_timing_lines(false) drops the
     // lines AND the per-level synchronisation: the host then prepares the next level while the GPU runs this one.
@@ -359,6 +363,7 @@ class LutCircuit : public EvalCircuit<SiEncWireMap> {
     helm_si_ctx *server_key_;
     helm_wop_ctx *wop_ = nullptr;
     int wop_bits_per_block_ = 1;
+    bool wop_share_ = false;
     bool timing_lines_ = true;
     bool many_lut_ = false;
     Circuit circuit_;

@@ -390,8 +390,9 @@ std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap 
                     si_ok(helm_wop_make_table(&W, m, wop_bits_per_block_, g.get_lut_const()->data(),
                                               g.get_lut_const()->size(), wg.tables.data() + wg.tables.size() - words),
                           "wop_make_table");
-                    // cleaning + bit removal + circuit bootstraps + the final one
-                    pbs_count_ += m + m * (wop_bits_per_block_ - 1) + (int64_t)m * wop_bits_per_block_ * W.cbs_l + 1;
+                    // cleaning + bit removal + circuit bootstraps + the final one (shared: counted per group below)
+                    if (!wop_share_)
+                        pbs_count_ += m + m * (wop_bits_per_block_ - 1) + (int64_t)m * wop_bits_per_block_ * W.cbs_l + 1;
                     continue;
                 }
                 if (ins.size() > 6) throw Panic("LUT with more than 6 inputs does not fit the truth-table word");
@@ -424,10 +425,46 @@ std::unique_ptr<SiEncWireMap> LutCircuit::evaluate_encrypted(const SiEncWireMap 
         }
         const auto level_start = std::chrono::steady_clock::now();
         // wide gates first: they read the level's inputs before a state copy of the same level overwrites one
-        for (auto &wk : wide)
-            si_ok(helm_wop_eval_luts(wop_, eval_values->table(), wk.second.in.data(), wk.first, wop_bits_per_block_,
-                                     wk.second.tables.data(), wk.second.out.data(), (int64_t)wk.second.out.size()),
-                  "wop_eval_luts");
+        for (auto &wk : wide) {
+            if (!wop_share_) {
+                si_ok(helm_wop_eval_luts(wop_, eval_values->table(), wk.second.in.data(), wk.first, wop_bits_per_block_,
+                                         wk.second.tables.data(), wk.second.out.data(), (int64_t)wk.second.out.size()),
+                      "wop_eval_luts");
+                continue;
+            }
+            // gates on the same input rows in the same order form a group (helm_wide_share); groups of one size share a call
+            const int m = wk.first;
+            const Wide &wg = wk.second;
+            const int64_t n_gates = (int64_t)wg.out.size();
+            const size_t words = wg.tables.size() / (size_t)n_gates;
+            helm_wop_params W{};
+            si_ok(helm_wop_get_params(wop_, &W), "wop_get_params");
+            std::vector<int64_t> group_of((size_t)n_gates);
+            const int64_t n_groups = helm_wide_share::group_gates(wg.in.data(), n_gates, m,
+                                                                  helm_wide_share::group_cap(m * wop_bits_per_block_), group_of.data());
+            std::vector<std::vector<int64_t>> members((size_t)n_groups);
+            for (int64_t g = 0; g < n_gates; g++) members[(size_t)group_of[(size_t)g]].push_back(g);
+            std::map<size_t, std::vector<int64_t>> by_size; // n_out -> groups, in order
+            for (int64_t q = 0; q < n_groups; q++) by_size[members[(size_t)q].size()].push_back(q);
+            for (auto &bs : by_size) {
+                const size_t n_out = bs.first;
+                std::vector<int32_t> g_in, g_out;
+                std::vector<uint64_t> g_tab;
+                for (int64_t q : bs.second) {
+                    const int64_t first = members[(size_t)q][0];
+                    g_in.insert(g_in.end(), wg.in.begin() + first * m, wg.in.begin() + (first + 1) * m);
+                    for (int64_t g : members[(size_t)q]) {
+                        g_out.push_back(wg.out[(size_t)g]);
+                        g_tab.insert(g_tab.end(), wg.tables.begin() + (size_t)g * words, wg.tables.begin() + (size_t)(g + 1) * words);
+                    }
+                }
+                si_ok(helm_wop_eval_many_luts(wop_, eval_values->table(), g_in.data(), m, wop_bits_per_block_, g_tab.data(),
+                                              g_out.data(), (int32_t)n_out, (int64_t)bs.second.size()),
+                      "wop_eval_many_luts");
+                // per group: cleaning + bit removal + circuit bootstraps once; per output: the final one
+                pbs_count_ += (int64_t)bs.second.size() * (m + m * (wop_bits_per_block_ - 1) + (int64_t)m * wop_bits_per_block_ * W.cbs_l + (int64_t)n_out);
+            }
+        }
         if (!arity.empty())
             si_ok(helm_si_eval_lut_level(server_key_, eval_values->table(), arity.data(), in_idx.data(), max_in,
                                          table.data(), out.data(), (int64_t)arity.size()),

@@ -133,6 +133,40 @@ class WopServerKey:
         hip_check(hip.helm_wop_eval_luts(self._h, wires._h, nv.as_i32p(in_idx), n_inputs, bits_per_block,
                                          nv.as_u64p(tables), nv.as_i32p(out_idx), count))
 
+    def many_form(self, bits, n_out):
+        """How n_out tables on one input tuple of `bits` index bits are served: 0 single (n_out = 1), 1 shared."""
+        form = hip.helm_wop_many_form(self._h, bits, n_out)
+        if form < 0:
+            hip_check(form)
+        return form
+
+    def eval_many_luts(self, wires, in_idx, truth_tables, out_idx, bits_per_block=None):
+        """Groups of wide gates on one input tuple each: the front stages once per group, one look-up per output.
+        in_idx [count][n_inputs] rows of `wires` (first input = most significant), truth_tables [count][n_out][2^n_inputs]
+        (or [n_out][...] for every group), out_idx [count][n_out]."""
+        in_idx = np.ascontiguousarray(np.atleast_2d(in_idx), dtype=np.int32)
+        count, n_inputs = in_idx.shape
+        out_idx = np.ascontiguousarray(out_idx, dtype=np.int32)
+        if out_idx.ndim != 2:
+            out_idx = out_idx.reshape(count, -1)
+        n_out = out_idx.shape[1]
+        if bits_per_block is None:
+            bits_per_block = (self.params.message_modulus * self.params.carry_modulus).bit_length() - 1
+        truth_tables = np.asarray(truth_tables, dtype=np.uint64)
+        if truth_tables.ndim == 2:
+            truth_tables = np.broadcast_to(truth_tables, (count,) + truth_tables.shape)
+        assert truth_tables.shape[:2] == (count, n_out)
+        made = {}
+        tables = np.empty((count, n_out, self.table_words(n_inputs * bits_per_block)), dtype=np.uint64)
+        for g in range(count):
+            for o in range(n_out):
+                key = truth_tables[g, o].tobytes()
+                if key not in made:
+                    made[key] = make_table(self.params, n_inputs, bits_per_block, truth_tables[g, o])
+                tables[g, o] = made[key]
+        hip_check(hip.helm_wop_eval_many_luts(self._h, wires._h, nv.as_i32p(in_idx), n_inputs, bits_per_block,
+                                              nv.as_u64p(tables), nv.as_i32p(out_idx), n_out, count))
+
     # ---- stage primitives (tests) --------------------------------------------------------------------------
     def extract_bits(self, big, delta_log, nb):
         big = np.ascontiguousarray(np.atleast_2d(big), dtype=np.uint64)
@@ -156,6 +190,18 @@ class WopServerKey:
         out = np.zeros((count, self.dim + 1), dtype=np.uint64)
         hip_check(hip.helm_wop_vertical_packing_batch(self._h, nv.as_u64p(ggsw), bits, nv.as_u64p(tables), nv.as_u64p(out),
                                                       count))
+        return out
+
+    def vertical_packing_many(self, ggsw, tables, n_out):
+        """ggsw [count][bits][cbs_l][k+1][(k+1) N]; tables [count][n_out][table_words] -> [count][n_out][k N + 1], in the
+        form many_form(bits, n_out) names."""
+        ggsw = np.ascontiguousarray(ggsw, dtype=np.uint64)
+        count, bits = ggsw.shape[0], ggsw.shape[1]
+        tables = np.ascontiguousarray(tables, dtype=np.uint64).reshape(count, n_out, -1)
+        assert tables.shape[2] == self.table_words(bits)
+        out = np.zeros((count, n_out, self.dim + 1), dtype=np.uint64)
+        hip_check(hip.helm_wop_vertical_packing_many_batch(self._h, nv.as_u64p(ggsw), bits, nv.as_u64p(tables), n_out,
+                                                           nv.as_u64p(out), count))
         return out
 
     def timing(self, reset=False):

@@ -92,6 +92,16 @@ int helm_host_pack_levels_costed(const int32_t *opcode, const int32_t *in0, cons
  * returns the largest chunk (rows of one rank's slot in the all-gather), -1 on bad arguments. */
 int64_t helm_host_shard_bounds(const int32_t *opcode, int64_t count, int world, int64_t *bounds);
 
+/* Which wide LUT gates of a level share their front stages (helm_amd/csrc/wide_share_rule.h; what a LutCircuit with
+ * helm_host_si_circuit_set_wopbs_share on hands to helm_wop_eval_many_luts): gates whose input rows are equal IN THE SAME
+ * ORDER form one group, of at most `cap` gates (a full group is closed and the next such gate opens another); permuted
+ * inputs do not group.  in_idx [count][n_inputs]; group_of[g] = the group of gate g, groups numbered by their first gate,
+ * a group's gates in the order of the call.  Returns the number of groups, -1 on bad arguments.
+ * helm_host_wide_lut_group_cap(bits): the cap a LutCircuit uses at `bits` index bits = the tables one pass of the engine's
+ * chunk holds, max(1, 16384 / bits); 0 for bits < 1. */
+int64_t helm_host_wide_lut_groups(const int32_t *in_idx, int64_t count, int32_t n_inputs, int64_t cap, int64_t *group_of);
+int64_t helm_host_wide_lut_group_cap(int32_t bits);
+
 /* encrypted wire maps */
 int helm_host_enc_map_new(helm_hip_ctx *server_key, helm_enc_map **out);
 void helm_host_enc_map_free(helm_enc_map *m);
@@ -159,6 +169,11 @@ int helm_host_si_circuit_decrypt_outputs(helm_si_circuit *c, const helm_si_enc_m
  * through the WoP-PBS path of include/helm_wopbs.h - Gate::evaluate_encrypted_high_precision_lut (gates.rs:721-742),
  * which the reference defines but never calls.  wop = NULL switches it off again. */
 int helm_host_si_circuit_set_wopbs(helm_si_circuit *c, helm_wop_ctx *wop, int bits_per_block);
+/* on != 0 (default off): the wide gates of a level that read the same wires in the same order form one group
+ * (helm_host_wide_lut_groups) and go out through helm_wop_eval_many_luts - cleaning, bit extraction and circuit bootstrap
+ * once per group, one look-up and one bootstrap back per gate; groups of equal (inputs, size) share a call.  The same values
+ * on every wire; pbs_per_cycle counts what runs.  Off: one helm_wop_eval_luts call per input count, as before. */
+int helm_host_si_circuit_set_wopbs_share(helm_si_circuit *c, int on);
 /* Arithmetic mode: one more lane (helm_si_ctx_fork of the circuit's server key).  Sub-circuits that share no wire are
  * then evaluated concurrently, one lane each, instead of meeting at every level boundary; identical ciphertexts.
  * lane = NULL removes all lanes.  helm_host_si_circuit_pbs_rounds_per_cycle() then reports the longest lane. */

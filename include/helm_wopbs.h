@@ -106,6 +106,27 @@ int helm_wop_make_table(const helm_wop_params *params, int32_t n_blocks, int32_t
 int helm_wop_eval_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, int32_t n_inputs,
                        int32_t bits_per_block, const uint64_t *tables, const int32_t *out_idx, int64_t count);
 
+/* Several tables on one input tuple: `count` groups, each with n_inputs input rows and n_out tables - the wide gates of a
+ * level that read the same wires in the same order (the eight output bits of an S-box).  Stages 1-4 (cleaning, keyswitch,
+ * bit extraction, circuit bootstrap) depend on the inputs alone and run once per group; stage 5 (vertical packing) and stage
+ * 6 (the way back) run once per output.
+ * in_idx [count][n_inputs];  tables [count][n_out][helm_wop_table_words(n_inputs * bits_per_block)];  out_idx [count][n_out].
+ * Limits as helm_wop_eval_luts; n_out >= 1 and count * n_out must fit int32_t.  n_out = 1 is helm_wop_eval_luts, launch for
+ * launch.  An output row that is an input row of ANOTHER group is refused as there; two outputs naming one row are refused; a
+ * group may write over its own inputs.  Groups run in chunks of max(1, 16384 / bits) and the outputs of a chunk in passes of
+ * at most that many tables, so the scratch is that of a chunk of single gates.
+ * Stage 5 is the shared form: one vertical packing per table, the tables of a group reading the group's GGSWs.  The rows
+ * are those of n_out separate helm_wop_eval_luts calls on the same inputs, word for word.
+ * Multi-GPU: cut by group; a rank's slot carries n_out rows per group, so a round takes capacity_rows / n_out groups per
+ * rank (n_out above capacity_rows is refused); identical ciphertexts to the unsharded call. */
+int helm_wop_eval_many_luts(helm_wop_ctx *ctx, helm_si_wires *w, const int32_t *in_idx, int32_t n_inputs,
+                            int32_t bits_per_block, const uint64_t *tables, const int32_t *out_idx, int32_t n_out,
+                            int64_t count);
+/* the form helm_wop_eval_many_luts and helm_wop_vertical_packing_many_batch take at `bits` index bits and n_out tables:
+ * 0 = single (n_out = 1), 1 = shared; negative helm_status on a bad argument.  (2 is reserved for a packed form - all tables
+ * of a group in one polynomial - which was measured no faster than the shared form and is not built: DESIGN.md 4.8.) */
+int helm_wop_many_form(const helm_wop_ctx *ctx, int32_t bits, int32_t n_out);
+
 /* Stage primitives on host buffers (tests).
  * extract_bits: in_big count x (k*N+1) under the WoP big key -> out_small count x nb x (n+1), bit 0 of a row =
  *   least significant extracted bit (position delta_log), each encrypting bit * 2^63.
@@ -117,12 +138,17 @@ int helm_wop_extract_bits_batch(helm_wop_ctx *ctx, const uint64_t *in_big, int32
 int helm_wop_circuit_bootstrap_batch(helm_wop_ctx *ctx, const uint64_t *in_small, uint64_t *ggsw_out, int64_t count);
 int helm_wop_vertical_packing_batch(helm_wop_ctx *ctx, const uint64_t *ggsw, int32_t bits, const uint64_t *tables,
                                     uint64_t *out_big, int64_t count);
+/* vertical_packing_many: stage 5 of helm_wop_eval_many_luts, in the form helm_wop_many_form names: ggsw count x bits x
+ *   [cbs_l][k+1][k+1][N], tables count x n_out x helm_wop_table_words(bits) -> out_big count x n_out x (k*N+1). */
+int helm_wop_vertical_packing_many_batch(helm_wop_ctx *ctx, const uint64_t *ggsw, int32_t bits, const uint64_t *tables,
+                                         int32_t n_out, uint64_t *out_big, int64_t count);
 
 typedef struct {
     double clean_ms, to_wopbs_ms, extract_ms, cbs_pbs_ms, pfpks_ms, convert_ms, packing_ms, to_pbs_ms;
     int64_t gates, bootstraps;
 } helm_wop_timing;
-/* accumulated over helm_wop_eval_luts calls since the last reset (HIP events; the call synchronises) */
+/* accumulated over helm_wop_eval_luts / helm_wop_eval_many_luts calls since the last reset (HIP events; the call
+ * synchronises); gates counts outputs, bootstraps the bootstraps that ran (a group's front stages once) */
 int helm_wop_get_timing(helm_wop_ctx *ctx, helm_wop_timing *out, int reset);
 
 /* ---- client side (CPU): WopbsKey::new_wopbs_key's key material ------------------------------------

@@ -258,6 +258,14 @@ extern "C" {
                                truth_len: usize, table_out: *mut u64) -> c_int;
     pub fn helm_wop_eval_luts(ctx: *mut helm_wop_ctx, w: *mut helm_si_wires, in_idx: *const i32, n_inputs: i32,
                               bits_per_block: i32, tables: *const u64, out_idx: *const i32, count: i64) -> c_int;
+    // groups of n_out tables on one input tuple: the front stages once per group, one look-up per output
+    pub fn helm_wop_eval_many_luts(ctx: *mut helm_wop_ctx, w: *mut helm_si_wires, in_idx: *const i32, n_inputs: i32,
+                                   bits_per_block: i32, tables: *const u64, out_idx: *const i32, n_out: i32, count: i64) -> c_int;
+    pub fn helm_wop_many_form(ctx: *const helm_wop_ctx, bits: i32, n_out: i32) -> c_int; // 0 single, 1 shared
+    // include/helm_host.h: which wide gates of a level form a group (equal input rows in the same order, at most cap)
+    pub fn helm_host_wide_lut_groups(in_idx: *const i32, count: i64, n_inputs: i32, cap: i64, group_of: *mut i64) -> i64;
+    pub fn helm_host_wide_lut_group_cap(bits: i32) -> i64;
+    pub fn helm_host_si_circuit_set_wopbs_share(c: *mut helm_si_circuit, on: c_int) -> c_int;
     pub fn helm_keys_levels64_reverse(blocks: usize, levels: i32, row_words: usize, src: *const u64, dst: *mut u64,
                                       n_words: usize) -> c_int;
 }

@@ -24,9 +24,29 @@ pub struct HipLutCircuit<'a> {
     row_words: usize, // helm_si_wire_words: k N + 1, or n + 1 in the bootstrap-first order
     /// same-cycle memo (gates.rs:55-59, 288-292): the cycle whose outputs the table holds
     evaluated_cycle: Option<usize>,
+    /// `Gate::evaluate_encrypted_high_precision_lut` (gates.rs:721-742): with a key, LUT gates with more inputs than one
+    /// block's index bits go through the WoP-PBS path; `wide_share`: those on the same inputs share its front stages
+    wopbs: Option<crate::wopbs::HipWopbsKey>,
+    wide_share: bool,
 }
 
 impl<'a> HipLutCircuit<'a> {
+    /// LUT gates whose index does not fit one block go through `key` (created beside this circuit's context).
+    /// The wide route of this file (this setter, `set_wide_lut_share`, the wide / narrow split of `evaluate_encrypted`) is
+    /// NOT COMPILED and not run by any test, like the rest of the shim; the host library's LutCircuit is the tested form
+    /// of the same dispatch (helm_host_si_circuit_set_wopbs / _set_wopbs_share, tests/test_gpu_wop_many.py).
+    pub fn set_wide_lut_key(&mut self, key: Option<crate::wopbs::HipWopbsKey>) {
+        self.wopbs = key;
+        self.evaluated_cycle = None;
+    }
+
+    /// Wide gates of a level on the same input wires in the same order run cleaning, bit extraction and circuit bootstrap
+    /// once (helm_wop_eval_many_luts).  Default off; same values on every wire.
+    pub fn set_wide_lut_share(&mut self, on: bool) {
+        self.wide_share = on;
+        self.evaluated_cycle = None;
+    }
+
     /// `LutCircuit::new(client_key, server_key, circuit)` (circuit.rs:393-406) with the server key replaced by an engine
     /// context holding the same key material in the standard domain (keys.rs::standard_keys64).
     pub fn new(client_key: ClientKey, keys: &crate::keys::StandardKeys64, circuit: Circuit<'a>, device_id: i32) -> Self {
@@ -46,7 +66,7 @@ impl<'a> HipLutCircuit<'a> {
         check(unsafe { sys::helm_si_load_keyswitch_key(ctx, keys.ksk.as_ptr(), keys.ksk.len()) });
         let row_words = unsafe { sys::helm_si_wire_words(ctx) } as usize;
         HipLutCircuit { circuit, client_key, ctx, wires: std::ptr::null_mut(), row_of: HashMap::new(), row_words,
-                        evaluated_cycle: None }
+                        evaluated_cycle: None, wopbs: None, wide_share: false }
     }
 
     /// Gates of a level on the same inputs share one blind rotation (helm_si_set_level_many_lut): a full adder's sum and
@@ -128,10 +148,34 @@ impl<'a> EvalCircuit<DeviceWire> for HipLutCircuit<'a> {
         let total_levels = self.circuit.level_map.len();
         let mut levels: Vec<_> = self.circuit.level_map.iter().collect();
         levels.sort_by_key(|(l, _)| **l);
+        // index bits one block holds: gates::lut() packs sum in_i << (arity-1-i) into a single block
+        let t = (self.client_key.parameters.message_modulus().0 * self.client_key.parameters.carry_modulus().0) as usize; // [RECALLED]
+        let capacity = (usize::BITS - 1 - t.leading_zeros()) as usize;
         for (level, gates) in levels {
-            let max_in = gates.iter().map(|g| g.get_input_wires().len()).max().unwrap_or(1).max(1);
+            let is_wide = |g: &helm::gates::Gate| self.wopbs.is_some() && matches!(g.get_gate_type(), GateType::Lut)
+                && g.get_input_wires().len() > capacity;
+            // wide gates first, one call per input count: they read the level's inputs before a copy of the level writes one
+            let mut wide: std::collections::BTreeMap<usize, (Vec<i32>, Vec<&[u64]>, Vec<i32>)> = Default::default();
+            for g in gates.iter().filter(|g| is_wide(g)) {
+                let ins = g.get_input_wires();
+                let e = wide.entry(ins.len()).or_default();
+                e.0.extend(ins.iter().map(|w| self.row_of[w]));
+                e.1.push(g.get_lut_const().as_ref().expect("Lut const not provided").as_slice());
+                e.2.push(self.row_of[&g.get_output_wire()]);
+            }
+            if let Some(key) = self.wopbs.as_ref() {
+                for (m, (in_rows, consts, out_rows)) in wide.iter() {
+                    if self.wide_share {
+                        key.high_precision_lut_level_shared(self.wires, in_rows, *m as i32, consts, out_rows);
+                    } else {
+                        key.high_precision_lut_level(self.wires, in_rows, *m as i32, consts, out_rows);
+                    }
+                }
+            }
+            let narrow: Vec<_> = gates.iter().filter(|g| !is_wide(g)).collect();
+            let max_in = narrow.iter().map(|g| g.get_input_wires().len()).max().unwrap_or(1).max(1);
             let (mut arity, mut in_idx, mut table, mut out) = (vec![], vec![], vec![], vec![]);
-            for g in gates {
+            for g in narrow {
                 let ins = g.get_input_wires();
                 let mut slot = vec![-1i32; max_in];
                 for (q, w) in ins.iter().enumerate() { slot[q] = self.row_of[w]; }
@@ -148,8 +192,10 @@ impl<'a> EvalCircuit<DeviceWire> for HipLutCircuit<'a> {
                     _ => { arity.push(0); table.push(0); } // evaluate_encrypted_dff: clone of the first input
                 }
             }
-            check(unsafe { sys::helm_si_eval_lut_level(self.ctx, self.wires, arity.as_ptr(), in_idx.as_ptr(), max_in as i32,
-                                                       table.as_ptr(), out.as_ptr(), arity.len() as i64) });
+            if !arity.is_empty() { // a level of wide gates only has no narrow call
+                check(unsafe { sys::helm_si_eval_lut_level(self.ctx, self.wires, arity.as_ptr(), in_idx.as_ptr(), max_in as i32,
+                                                           table.as_ptr(), out.as_ptr(), arity.len() as i64) });
+            }
             println!("  Evaluated gates in level [{}/{}]", level, total_levels);
         }
         check(unsafe { sys::helm_si_sync(self.ctx) });

@@ -77,6 +77,43 @@ impl HipWopbsKey {
         check(unsafe { sys::helm_wop_eval_luts(self.ctx, wires, in_rows.as_ptr(), n_inputs, self.bits_per_block,
                                                tables.as_ptr(), out_rows.as_ptr(), out_rows.len() as i64) }, "helm_wop_eval_luts");
     }
+
+    /// The same level with the gates that read the same rows in the same order grouped (`helm_host_wide_lut_groups`):
+    /// cleaning, bit extraction and circuit bootstrap once per group, one look-up and one bootstrap back per gate
+    /// (`helm_wop_eval_many_luts`); groups of one size share a call.  Same values on every wire.
+    pub fn high_precision_lut_level_shared(&self, wires: *mut sys::helm_si_wires, in_rows: &[i32], n_inputs: i32,
+                                           lut_consts: &[&[u64]], out_rows: &[i32]) {
+        let m = n_inputs as usize;
+        let words = unsafe { sys::helm_wop_table_words(&self.params, n_inputs * self.bits_per_block) };
+        let mut group_of = vec![0i64; out_rows.len()];
+        let cap = unsafe { sys::helm_host_wide_lut_group_cap(n_inputs * self.bits_per_block) };
+        let n_groups = unsafe { sys::helm_host_wide_lut_groups(in_rows.as_ptr(), out_rows.len() as i64, n_inputs, cap,
+                                                               group_of.as_mut_ptr()) };
+        assert!(n_groups >= 0, "helm_host_wide_lut_groups");
+        let mut members: Vec<Vec<usize>> = vec![vec![]; n_groups as usize];
+        for (g, q) in group_of.iter().enumerate() { members[*q as usize].push(g); }
+        let mut by_size: std::collections::BTreeMap<usize, Vec<usize>> = Default::default();
+        for (q, mem) in members.iter().enumerate() { by_size.entry(mem.len()).or_default().push(q); }
+        for (n_out, groups) in by_size {
+            let (mut g_in, mut g_out) = (vec![], vec![]);
+            let mut tables = vec![0u64; words * n_out * groups.len()];
+            let mut t = 0usize;
+            for q in groups.iter() {
+                let first = members[*q][0];
+                g_in.extend_from_slice(&in_rows[first * m..(first + 1) * m]);
+                for g in members[*q].iter() {
+                    g_out.push(out_rows[*g]);
+                    check(unsafe { sys::helm_wop_make_table(&self.params, n_inputs, self.bits_per_block, lut_consts[*g].as_ptr(),
+                                                            lut_consts[*g].len(), tables[t * words..].as_mut_ptr()) },
+                          "helm_wop_make_table");
+                    t += 1;
+                }
+            }
+            check(unsafe { sys::helm_wop_eval_many_luts(self.ctx, wires, g_in.as_ptr(), n_inputs, self.bits_per_block,
+                                                        tables.as_ptr(), g_out.as_ptr(), n_out as i32, groups.len() as i64) },
+                  "helm_wop_eval_many_luts");
+        }
+    }
 }
 
 impl Drop for HipWopbsKey {
