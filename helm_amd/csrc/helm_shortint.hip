@@ -1422,7 +1422,7 @@ struct SiKeyState {
     size_t large_lds = 0;                 // LDS bytes per workgroup (Large64Lds)
     int large_per_cu = 1;                 // resident workgroups per CU
     // helm_si_ctx_create_ex under HELM_SI_CREATE_N8192 at N = 8192: k_pbs64_n8192 runs every bootstrap launch, in the same pair
-    // and key layout as the large-N class (k_bsk_convert64_n8192), one workgroup per CU
+    // and key layout as the large-N class (k_bsk_convert64_large<13>), one workgroup per CU
     bool n8192 = false;
     size_t n8192_lds = 0;                 // LDS bytes per workgroup (N8192Lds)
     uint64_t *ksk = nullptr;
@@ -1698,6 +1698,19 @@ namespace {
 // k_pbs64_generic: k, pbs_l and pbs_logB at run time (helm_si_ctx_create_ex)
 #include "helm_pbs64_generic.inc"
 
+// what the two large-N kernels share: the pair FpG / FpI, the transforms, the pieces of a step, the key conversion
+#include "helm_pbs64_large_core.inc"
+
+// The run-time grouping factor as the kernels' compile-time GG: f(std::integral_constant<int, GG>) with GG = 3 or 2 for the
+// multi-bit forms, 0 (the classical form) for anything else.
+template <class F>
+auto with_group(int group, F &&f)
+{
+    if (group == 3) return f(std::integral_constant<int, 3>{});
+    if (group == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
+}
+
 // k_pbs64_large: k = 1, N = 4096 (helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N)
 #include "helm_pbs64_large.inc"
 
@@ -1712,23 +1725,18 @@ hipError_t launch_pbs64_large(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
     }
     if (ctx->logN != 12 || ctx->P.k != 1) return hipErrorInvalidValue;
     if (K.group > 1 && !K.psi_pow) return hipErrorInvalidValue;
-#define LARGE64_LAUNCH(GG)                                                                                                   \
-    hipLaunchKernelGGL((k_pbs64_large<12, GG>), dim3((unsigned)count), dim3(L64_THREADS), K.large_lds, ctx->stream, jobs, small, \
-                       luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.pbs_l,               \
-                       ctx->P.pbs_logB, K.p0inv_mod_p1)
-    if (K.group == 3) LARGE64_LAUNCH(3);
-    else if (K.group == 2) LARGE64_LAUNCH(2);
-    else LARGE64_LAUNCH(0);
-#undef LARGE64_LAUNCH
+    with_group(K.group, [&](auto g) {
+        hipLaunchKernelGGL((k_pbs64_large<12, decltype(g)::value>), dim3((unsigned)count), dim3(L64_THREADS), K.large_lds,
+                           ctx->stream, jobs, small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n,
+                           ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1);
+    });
     return hipGetLastError();
 }
 
 // group: the multi-bit grouping factor (2 or 3), anything else: the classical form
 const void *pbs64_large_kernel(int group)
 {
-    return group == 3   ? reinterpret_cast<const void *>(k_pbs64_large<12, 3>)
-           : group == 2 ? reinterpret_cast<const void *>(k_pbs64_large<12, 2>)
-                        : reinterpret_cast<const void *>(k_pbs64_large<12, 0>);
+    return with_group(group, [](auto g) { return reinterpret_cast<const void *>(k_pbs64_large<12, decltype(g)::value>); });
 }
 
 // k_pbs64_n8192: k = 1, N = 8192 (helm_si_ctx_create_ex with HELM_SI_CREATE_N8192)
@@ -1749,27 +1757,22 @@ hipError_t launch_pbs64_n8192(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
     const int64_t rows = std::max(ctx->n_cus, 1); // (the rows of d_acc8192: alloc_acc8192)
     if (!ctx->d_acc8192) return hipErrorInvalidValue;
     if (K.group > 1 && !K.psi_pow) return hipErrorInvalidValue;
-#define N8192_LAUNCH(GG)                                                                                                     \
-    hipLaunchKernelGGL(k_pbs64_n8192<GG>, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds, ctx->stream, jobs + off, small, \
-                       luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->d_acc8192, ctx->P.n,              \
-                       ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1)
     for (int64_t off = 0; off < count; off += rows) {
         const int64_t chunk = std::min(rows, count - off);
-        if (K.group == 3) N8192_LAUNCH(3);
-        else if (K.group == 2) N8192_LAUNCH(2);
-        else N8192_LAUNCH(0);
+        with_group(K.group, [&](auto g) {
+            hipLaunchKernelGGL(k_pbs64_n8192<decltype(g)::value>, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds,
+                               ctx->stream, jobs + off, small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out,
+                               ctx->d_acc8192, ctx->P.n, ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1);
+        });
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
-#undef N8192_LAUNCH
     return hipSuccess;
 }
 
 // group: the multi-bit grouping factor (2 or 3), anything else: the classical form
 const void *pbs64_n8192_kernel(int group)
 {
-    return group == 3   ? reinterpret_cast<const void *>(k_pbs64_n8192<3>)
-           : group == 2 ? reinterpret_cast<const void *>(k_pbs64_n8192<2>)
-                        : reinterpret_cast<const void *>(k_pbs64_n8192<0>);
+    return with_group(group, [](auto g) { return reinterpret_cast<const void *>(k_pbs64_n8192<decltype(g)::value>); });
 }
 
 template <int LOGN, int GG>
@@ -1792,9 +1795,9 @@ hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_
         *per_cu = ctx->keys->gen_per_cu;
         return hipSuccess;
     }
-    if (ctx->keys->group == 3) return launch_pbs64_generic_g<LOGN, 3>(ctx, jobs, count, small, luts, out);
-    if (ctx->keys->group == 2) return launch_pbs64_generic_g<LOGN, 2>(ctx, jobs, count, small, luts, out);
-    return launch_pbs64_generic_g<LOGN, 0>(ctx, jobs, count, small, luts, out);
+    return with_group(ctx->keys->group, [&](auto g) {
+        return launch_pbs64_generic_g<LOGN, decltype(g)::value>(ctx, jobs, count, small, luts, out);
+    });
 }
 
 hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
@@ -1821,7 +1824,7 @@ const void *pbs64_generic_kernel_g(int logN)
 // group: the multi-bit grouping factor (2 or 3), anything else: the classical form
 const void *pbs64_generic_kernel(int logN, int group)
 {
-    return group == 3 ? pbs64_generic_kernel_g<3>(logN) : group == 2 ? pbs64_generic_kernel_g<2>(logN) : pbs64_generic_kernel_g<0>(logN);
+    return with_group(group, [&](auto g) { return pbs64_generic_kernel_g<decltype(g)::value>(logN); });
 }
 
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
@@ -2464,16 +2467,14 @@ bool si_large_multibit_domain(const helm_si_params &P, int N)
     return P.k == 1 && P.N == N && P.pbs_l >= 1 && P.grouping_factor >= 2 && P.grouping_factor <= 3;
 }
 
-// A context whose launches run k_pbs64_large: the inverse twiddle tables of the pair FpG / FpI, the kernel's LDS attribute
-// and its occupancy.
-int setup_large(helm_si_ctx *ctx)
+#ifndef HELM_CHECK_BOUNDS
+// What a context of either large-N kernel sets up (name: the kernel's, shape: what its verbose line says beside it): the
+// inverse twiddle tables of the pair FpG / FpI; the kernel's dynamic-LDS attribute, which is the kernel's and shared by every
+// context of the process, so it is set once per device over the three instantiations (kernel(0), kernel(2), kernel(3)) at
+// lds_max, the layout at the largest n; the workgroups per CU of this context's instantiation at its own layout of lds bytes.
+int setup_large_class(helm_si_ctx *ctx, const char *name, const char *shape, const void *(*kernel)(int),
+                      std::atomic<bool> (&attr_done)[64], size_t lds_max, size_t lds, int *per_cu)
 {
-#ifdef HELM_CHECK_BOUNDS
-    // as setup_generic: the bound-checking build runs the tuned kernels only, and refuses before anything is launched
-    (void)ctx;
-    return fail(HELM_ERR_STATE, "the large-N kernel is not available in the bound-checking build (libhelm_hip_check.so): "
-                                "use the regular library for HELM_SI_CREATE_LARGE_N contexts");
-#else
     SiKeyState &K = *ctx->keys;
     const helm_si_params &P = ctx->P;
     const int N = P.N, logN = ctx->logN;
@@ -2484,24 +2485,40 @@ int setup_large(helm_si_ctx *ctx)
         if (!K.twi[f]) HIP_TRY(hipMalloc(&K.twi[f], sizeof(double) * N));
         HIP_TRY(hipMemcpy(K.twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     }
-    // the attribute is the kernel's, shared by every context of the process: the layout at the largest n
-    static std::atomic<bool> attr_done[64];
-    const void *kern = pbs64_large_kernel(P.grouping_factor);
-    HIP_TRY(lds_attr_once(attr_done, ctx->device, {pbs64_large_kernel(0), pbs64_large_kernel(2), pbs64_large_kernel(3)},
-                          Large64Lds(N, 1024).bytes));
-    K.large_lds = Large64Lds(N, P.n).bytes;
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, L64_THREADS, K.large_lds));
-    if (nb < 1)
-        return fail(HELM_ERR_INVALID, "k_pbs64_large: no workgroup of " + std::to_string(K.large_lds) + " B LDS fits a CU");
-    K.large_per_cu = nb;
-    K.large = true;
+    const void *kern = kernel(P.grouping_factor);
+    HIP_TRY(lds_attr_once(attr_done, ctx->device, {kernel(0), kernel(2), kernel(3)}, lds_max));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, L64_THREADS, lds));
+    if (*per_cu < 1)
+        return fail(HELM_ERR_INVALID, std::string(name) + ": no workgroup of " + std::to_string(lds) + " B LDS fits a CU");
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_si] k_pbs64_large N=%d l=%d g=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.pbs_l,
-                P.grouping_factor > 1 ? P.grouping_factor : 1, K.large_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.large_per_cu);
+        fprintf(stderr, "[helm_si] %s%s l=%d g=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", name, shape, P.pbs_l,
+                P.grouping_factor > 1 ? P.grouping_factor : 1, lds, fa.numRegs, (size_t)fa.localSizeBytes, *per_cu);
     }
+    return 0;
+}
+#endif
+
+// A context whose launches run k_pbs64_large: setup_large_class and the dynamic-LDS limit of its key conversion.
+int setup_large(helm_si_ctx *ctx)
+{
+#ifdef HELM_CHECK_BOUNDS
+    // as setup_generic: the bound-checking build runs the tuned kernels only, and refuses before anything is launched
+    (void)ctx;
+    return fail(HELM_ERR_STATE, "the large-N kernel is not available in the bound-checking build (libhelm_hip_check.so): "
+                                "use the regular library for HELM_SI_CREATE_LARGE_N contexts");
+#else
+    SiKeyState &K = *ctx->keys;
+    const int N = ctx->P.N;
+    static std::atomic<bool> attr_done[64], conv_done[64];
+    K.large_lds = Large64Lds(N, ctx->P.n).bytes;
+    if (int rc = setup_large_class(ctx, "k_pbs64_large", " N=4096", pbs64_large_kernel, attr_done, Large64Lds(N, 1024).bytes,
+                                   K.large_lds, &K.large_per_cu))
+        return rc;
+    HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_large<12>)},
+                          sizeof(double) * 2 * (size_t)N));
+    K.large = true;
     return 0;
 #endif
 }
@@ -2521,8 +2538,8 @@ int alloc_acc8192(helm_si_ctx *ctx)
     return 0;
 }
 
-// A context whose launches run k_pbs64_n8192: the inverse twiddle tables of the pair FpG / FpI and the dynamic-LDS limits of
-// the kernel and of its key conversion.
+// A context whose launches run k_pbs64_n8192: setup_large_class, the dynamic-LDS limit of its key conversion and its
+// accumulator rows.
 int setup_n8192(helm_si_ctx *ctx)
 {
 #ifdef HELM_CHECK_BOUNDS
@@ -2532,35 +2549,15 @@ int setup_n8192(helm_si_ctx *ctx)
                                 "use the regular library for HELM_SI_CREATE_N8192 contexts");
 #else
     SiKeyState &K = *ctx->keys;
-    const helm_si_params &P = ctx->P;
-    const int N = P.N, logN = ctx->logN;
-    for (int f = 0; f < 2; f++) {
-        const uint64_t p = si_modulus(2, f);
-        std::vector<double> ti(N);
-        power_table(ti.data(), powmod_u64(si_psi(N, 2, f), p - 2, p), p, N, logN);
-        if (!K.twi[f]) HIP_TRY(hipMalloc(&K.twi[f], sizeof(double) * N));
-        HIP_TRY(hipMemcpy(K.twi[f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-    }
-    // the attributes are the kernels', shared by every context of the process: the layout at the largest n
     static std::atomic<bool> attr_done[64], conv_done[64];
-    const void *kern = pbs64_n8192_kernel(P.grouping_factor);
-    HIP_TRY(lds_attr_once(attr_done, ctx->device, {pbs64_n8192_kernel(0), pbs64_n8192_kernel(2), pbs64_n8192_kernel(3)},
-                          N8192Lds(1024).bytes));
-    HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_n8192)},
-                          sizeof(double) * 2 * (size_t)N));
-    K.n8192_lds = N8192Lds(P.n).bytes;
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, L64_THREADS, K.n8192_lds));
-    if (nb < 1)
-        return fail(HELM_ERR_INVALID, "k_pbs64_n8192: no workgroup of " + std::to_string(K.n8192_lds) + " B LDS fits a CU");
+    K.n8192_lds = N8192Lds(ctx->P.n).bytes;
+    int nb = 0; // (one workgroup per CU: launch_pbs64_n8192)
+    if (int rc = setup_large_class(ctx, "k_pbs64_n8192", "", pbs64_n8192_kernel, attr_done, N8192Lds(1024).bytes, K.n8192_lds, &nb))
+        return rc;
+    HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_large<N8192_LOGN>)},
+                          sizeof(double) * 2 * (size_t)ctx->P.N));
     if (int rc = alloc_acc8192(ctx)) return rc;
     K.n8192 = true;
-    if (getenv("HELM_HIP_VERBOSE")) {
-        hipFuncAttributes fa{};
-        (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_si] k_pbs64_n8192 l=%d g=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", P.pbs_l,
-                P.grouping_factor > 1 ? P.grouping_factor : 1, K.n8192_lds, fa.numRegs, (size_t)fa.localSizeBytes, nb);
-    }
     return 0;
 #endif
 }
@@ -2987,13 +2984,10 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (K.n8192) { // the same layout and pair at N = 8192, through dynamic LDS (k_bsk_convert64_n8192)
-        hipLaunchKernelGGL(k_bsk_convert64_n8192, dim3((unsigned)polys), dim3(L64_THREADS), sizeof(double) * 2 * (size_t)P.N,
-                           ctx->stream, d_std, K.bsk, K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1,
-                           P.pbs_l);
-    } else if (K.large) { // the generic layout in the pair FpG / FpI (k_bsk_convert64_large)
-        hipLaunchKernelGGL(k_bsk_convert64_large<12>, dim3((unsigned)polys), dim3(L64_THREADS), 0, ctx->stream, d_std, K.bsk,
-                           K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l);
+    if (K.n8192 || K.large) { // the generic layout in the pair FpG / FpI, the two-field buffer in dynamic LDS
+        const auto conv = K.n8192 ? k_bsk_convert64_large<N8192_LOGN> : k_bsk_convert64_large<12>;
+        hipLaunchKernelGGL(conv, dim3((unsigned)polys), dim3(L64_THREADS), sizeof(double) * 2 * (size_t)P.N, ctx->stream, d_std,
+                           K.bsk, K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l);
     } else if (K.gen) {
         // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
 #define GEN64_CONVERT(LN)                                                                                                 \

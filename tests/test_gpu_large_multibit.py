@@ -1,5 +1,5 @@
 """The multi-bit form of the two large-N blind-rotate kernels of the 64-bit engine (k_pbs64_large<12, g>,
-k_pbs64_n8192<g>; helm_amd/csrc/helm_pbs64_large.inc, helm_pbs64_n8192.inc), reached through
+k_pbs64_n8192<g>; helm_amd/csrc/helm_pbs64_large_core.inc, helm_pbs64_large.inc, helm_pbs64_n8192.inc), reached through
 SiServerKey(generic="large+multibit" | "n8192+multibit" | "large+n8192+multibit") = helm_si_ctx_create_ex with
 HELM_SI_CREATE_LARGE_MULTIBIT.  n stays at 12 (4 or 6 group steps) and the batches small.  Every comparison is word for word
 against oracle.Oracle64(..., use_ntt=True); tests/many_lut.py, tests/pbs_first.py and tests/saturation_mb.py are imported as

@@ -1,5 +1,5 @@
-"""The large-N blind-rotate kernel of the 64-bit engine (k_pbs64_large, helm_amd/csrc/helm_pbs64_large.inc): k = 1,
-N = 4096, reached through SiServerKey(generic="large") = helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N.  N = 4096 is the
+"""The large-N blind-rotate kernel of the 64-bit engine (k_pbs64_large, helm_amd/csrc/helm_pbs64_large.inc over
+helm_pbs64_large_core.inc): k = 1, N = 4096, reached through SiServerKey(generic="large") = helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N.  N = 4096 is the
 smallest size at which the kernel exists, so n stays at 12 and the batches small.  Every comparison is word for word against
 oracle.Oracle64(..., use_ntt=True); tests/many_lut.py and tests/saturation.py are imported as they are."""
 import json

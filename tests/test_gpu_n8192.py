@@ -1,5 +1,5 @@
-"""The N = 8192 blind-rotate kernel of the 64-bit engine (k_pbs64_n8192, helm_amd/csrc/helm_pbs64_n8192.inc): k = 1,
-N = 8192, reached through SiServerKey(generic="n8192") = helm_si_ctx_create_ex with HELM_SI_CREATE_N8192.  n stays at 12
+"""The N = 8192 blind-rotate kernel of the 64-bit engine (k_pbs64_n8192, helm_amd/csrc/helm_pbs64_n8192.inc over
+helm_pbs64_large_core.inc): k = 1, N = 8192, reached through SiServerKey(generic="n8192") = helm_si_ctx_create_ex with HELM_SI_CREATE_N8192.  n stays at 12
 (every case is 12 rotation steps) and the batches small.  Every comparison is word for word against
 oracle.Oracle64(..., use_ntt=True); tests/many_lut.py, tests/saturation.py and tests/pbs_first.py are imported as they are.
 

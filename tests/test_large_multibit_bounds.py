@@ -56,17 +56,26 @@ def test_the_product_chain(p):
 def test_the_source_recentres_after_every_fourth_subset():
     """A tripwire on the kernels' text, as tests/test_large_n_bounds.py has one: the subset loop's recentring interval, the
     replacing lift, the group's rotations in scalar registers, the reduced subset sum and the exponent of a position."""
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for name, lift in (("helm_pbs64_large.inc", "acc[(size_t)c*N+j]=(uint64_t)to_int64(r0)+L0::P_U64*(uint64_t)to_int64(tq);"),
-                       ("helm_pbs64_n8192.inc", "acc[(unsigned)c*N+own+m]=(uint64_t)to_int64(r0)+L0::P_U64*(uint64_t)to_int64(tq);")):
-        src = re.sub(r"\s+", "", open(os.path.join(root, "helm_amd", "csrc", name)).read())
-        assert src.count("constboolfold=(S&3)==%d;" % (FOLD - 1)) == 1
-        assert src.count(lift) == 1
+    core, large, n8192 = LB.kernel_sources()
+    together = core + large + n8192
+    # the subset term and the lift stand in the shared core (helm_pbs64_large_core.inc): ONCE in the three files together
+    for stmt in ("constboolfold=(S&3)==%d;" % (FOLD - 1), "eS&=2*N-1;",
+                 "constintex=2*(int)(__brev((unsigned)s)>>(32-LOGN))+1;",
+                 "returnreduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));", "constdoublet=l64_quotient(r0,r1,p0inv_mod_p1);",
+                 "HELM_BOUND(__builtin_fabs(r0)<0x1p51&&__builtin_fabs(t)<0x1p51,4);",
+                 "constuint64_tx=(uint64_t)to_int64(r0)+L0::P_U64*(uint64_t)to_int64(t);",
+                 "uint64_t&w=acc.own(c,m);w=REPLACE?x:w+x;"):
+        assert together.count(stmt) == 1 and stmt in core, stmt
+    assert together.count("HELM_BOUND(") == 1 and together.count("l64_quotient(") == 2   # (its definition and its one use)
+    # the own word of each kernel's accumulator view, which the lift writes
+    assert "returnp[(size_t)r*N+(int)threadIdx.x+m*L64_THREADS];" in core and "return(p+(size_t)r*N)[base+m];" in core
+    # per kernel: the replacing lift, the group's rotations in scalar registers, the rolled subset loop
+    for src, lift, term in ((large, "l64_column_back<LOGN,true>(acc,c,buf,sum[c],twi0,twi1,p0inv_mod_p1);",
+                             "l64_subset_term<LOGN,GG>(sum,buf,kS,(size_t)L*2*N,psi_pow,am,S);"),
+                            (n8192, "l64_column_back<LOGN,true>(acc,c,buf,sum[0],twi0,twi1,p0inv_mod_p1);",
+                             "l64_subset_term<LOGN,GG>(sum,buf,kq+(size_t)S*step_words,0,psi_pow,am,S);")):
+        assert src.count(lift) == 1 and src.count(term) == 1
         assert src.count("am[i]=__builtin_amdgcn_readfirstlane((int)MS[t*GG+i]);") == 1
-        assert src.count("eS&=2*N-1;") == 1
-        assert src.count("constintex=2*(int)(__brev((unsigned)s)>>(32-LOGN))+1;") == 1
-        assert src.count("tq=reduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));") == 1
         assert src.count("#pragmaunroll1for(intS=0;S<SUB;S++)") == 1
 
 
@@ -172,7 +181,7 @@ def _rev(x, bits):
 
 
 def forward_model(x, psi, p):
-    """l64_ntt_forward / n8192_ntt_forward in exact integers mod p: natural order in, bit-reversed out; stage s has m = 2^s
+    """l64_ntt_forward (helm_pbs64_large_core.inc) in exact integers mod p: natural order in, bit-reversed out; stage s has m = 2^s
     blocks of 2 t = N / m values, block i multiplies its upper half by table entry m + i of the bit-reversed powers of psi
     (power_table: power i stands at index rev(i))."""
     N = len(x)

@@ -1,5 +1,5 @@
 """Admission of multi-bit blind rotation (grouping_factor 2 or 3) at k = 1, N = 4096 and N = 8192 under
-HELM_SI_CREATE_LARGE_MULTIBIT = 1024 (include/helm_shortint.h, helm_amd/csrc/helm_pbs64_large.inc, helm_pbs64_n8192.inc).  The
+HELM_SI_CREATE_LARGE_MULTIBIT = 1024 (include/helm_shortint.h, helm_amd/csrc/helm_pbs64_large_core.inc, helm_pbs64_large.inc, helm_pbs64_n8192.inc).  The
 bit goes with bit 32 and/or bit 256; it matters for grouping_factor > 1 at N >= 4096 only; without it every call is what it
 was, byte for byte.  Parameter checks come before the device lookup, so no GPU is needed."""
 import os

@@ -1,5 +1,6 @@
 """Worst-case magnitudes of the large-N blind-rotate kernel's fp64 arithmetic (k_pbs64_large,
-helm_amd/csrc/helm_pbs64_large.inc), with exact fractions, for its pair L0 = FpG = 5072^4 + 1, L1 = FpI = 5440^4 + 1.
+helm_amd/csrc/helm_pbs64_large.inc over the shared helm_pbs64_large_core.inc), with exact fractions, for its pair
+L0 = FpG = 5072^4 + 1, L1 = FpI = 5440^4 + 1.
 
 Every value in the kernel is an integer held in a double: exactness needs |v| < 2^53 at every addition and at the inputs of
 mulmod and reduce (helm_amd/csrc/ntt_fp64.h).  The kernel recentres every value a transform stage stores, so the bounds do
@@ -117,16 +118,27 @@ def test_the_roots_of_unity():
 
 
 def test_the_source_states_the_interval_and_the_pair():
-    """A tripwire on the kernel's text, nothing more (white space is ignored; it asks whoever edits these lines to look at
-    the bounds above): the pair, the recentring interval of the column sums, the recentring when a column is written back
+    """A tripwire on the text of the kernel and of the core it shares with k_pbs64_n8192, nothing more (white space is
+    ignored; it asks whoever edits these lines to look at the bounds above): the pair, the recentring interval of the column sums, the recentring when a column is written back
     and the recentred quotient of the lift.  That the kernel computes exactly AT these bounds is pinned on the device, by
     the saturating case of tests/test_gpu_large_n.py."""
+    core, src, n8192 = kernel_sources()
+    together = core + src + n8192
+    # what the shared core (helm_pbs64_large_core.inc) holds stands ONCE in the three files taken together
+    for stmt in ("usingL0=FpG;", "usingL1=FpI;", "s0=reduce<L0>(s0);", "s1=reduce<L1>(s1);",
+                 "buf[s]=reduce<L0>(sum[0][m]);", "buf[N+s]=reduce<L1>(sum[1][m]);",
+                 "returnreduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));",            # l64_quotient's body: the recentred quotient
+                 "constdoublet=l64_quotient(r0,r1,p0inv_mod_p1);"):
+        assert together.count(stmt) == 1 and stmt in core, stmt
+    assert "constboolfold=(q&3)==%d;" % (FOLD - 1) in src      # FOLD = 4
+    assert "l64_products<LOGN>(sum[c],buf,key+(((size_t)(r*2+c)*L+lev)*2)*N,q==0,fold);" in src
+    assert src.count("l64_column_back<LOGN,false>(acc,c,buf,sum[c],twi0,twi1,p0inv_mod_p1);") == 1
+
+
+def kernel_sources():
+    """The text of the shared core and of the two kernel files, white space removed."""
     import os
     import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = re.sub(r"\s+", "", open(os.path.join(root, "helm_amd", "csrc", "helm_pbs64_large.inc")).read())
-    assert "usingL0=FpG;" in src and "usingL1=FpI;" in src
-    assert "constboolfold=(q&3)==%d;" % (FOLD - 1) in src      # FOLD = 4
-    assert "s0=reduce<L0>(s0);" in src and "s1=reduce<L1>(s1);" in src
-    assert "buf[s]=reduce<L0>(sum[c][0][m]);" in src and "buf[N+s]=reduce<L1>(sum[c][1][m]);" in src
-    assert "t=reduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));" in src
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "helm_amd", "csrc")
+    return [re.sub(r"\s+", "", open(os.path.join(csrc, name)).read())
+            for name in ("helm_pbs64_large_core.inc", "helm_pbs64_large.inc", "helm_pbs64_n8192.inc")]

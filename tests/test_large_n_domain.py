@@ -1,5 +1,5 @@
 """Admission of the large-N shape (k = 1, N = 4096: the 5-bit shortint sets) under HELM_SI_CREATE_LARGE_N = 32
-(include/helm_shortint.h, helm_amd/csrc/helm_pbs64_large.inc).  The bit may stand alone or beside the generic bits; it
+(include/helm_shortint.h, helm_amd/csrc/helm_pbs64_large_core.inc, helm_pbs64_large.inc).  The bit may stand alone or beside the generic bits; it
 matters at N >= 4096 only; without it every call is what it was.  Parameter checks come before the device lookup, so no GPU
 is needed."""
 import ctypes as C

@@ -1,10 +1,9 @@
 """What changes for the fp64 arithmetic of the N = 8192 blind-rotate kernel (k_pbs64_n8192,
-helm_amd/csrc/helm_pbs64_n8192.inc) against the large-N kernel, with exact fractions.  The per-value bounds of
+helm_amd/csrc/helm_pbs64_n8192.inc over the shared helm_pbs64_large_core.inc) against the large-N kernel, with exact fractions.  The per-value bounds of
 tests/test_large_n_bounds.py (recentred stage outputs, products below 0.58 p, at most FOUR products between two recentrings
 of a column sum, the lift's ranges) hold for any N in the same pair L0 = FpG = 5072^4 + 1, L1 = FpI = 5440^4 + 1 and are
 imported from there; what depends on N is restated here: the capacity, the roots of unity, the LDS layout."""
 import os
-import re
 import sys
 from fractions import Fraction as Fr
 
@@ -72,24 +71,28 @@ def test_the_lds_layout_fits_a_cu():
     assert lds(12) == 131104
     assert lds(1024) + 8 * 2 * N > 160 * 1024
     assert 2 * N <= 1 << 16                                            # the switched values fit the u16 `ms` array
-    src = re.sub(r"\s+", "", open(os.path.join(ROOT, "helm_amd", "csrc", "helm_pbs64_n8192.inc")).read())
-    assert "ms=buf+sizeof(double)*2*((size_t)1<<N8192_LOGN);" in src
-    assert "bytes=(ms+sizeof(uint16_t)*((size_t)n+1)+15)/16*16;" in src
-    assert "constexprintN8192_LOGN=13;" in src
+    core = LB.kernel_sources()[0]                                      # N8192Lds stands in the shared core
+    assert "ms=buf+sizeof(double)*2*((size_t)1<<N8192_LOGN);" in core
+    assert "bytes=(ms+sizeof(uint16_t)*((size_t)n+1)+15)/16*16;" in core
+    assert "constexprintN8192_LOGN=13;" in core
 
 
 def test_the_source_states_the_interval_and_the_pair():
-    """A tripwire on the kernel's text, as in the large-N test: the pair (shared with helm_pbs64_large.inc, which is included
-    first), the recentring interval of the column sums in recurrence order, the recentring when a column is written back,
-    the recentred quotient of the lift, and the skip of a zero rotation, uniform over the workgroup."""
-    large = re.sub(r"\s+", "", open(os.path.join(ROOT, "helm_amd", "csrc", "helm_pbs64_large.inc")).read())
-    assert "usingL0=FpG;" in large and "usingL1=FpI;" in large
-    src = re.sub(r"\s+", "", open(os.path.join(ROOT, "helm_amd", "csrc", "helm_pbs64_n8192.inc")).read())
+    """A tripwire on the kernel's text, as in the large-N test: the pair, the recentring of a sum, the recentring when a
+    column is written back and the recentred quotient of the lift (all in helm_pbs64_large_core.inc, which is included
+    first: once in the three files taken together), the recentring interval of the column sums in recurrence order, and
+    the skip of a zero rotation, uniform over the workgroup."""
+    core, large, src = LB.kernel_sources()
+    together = core + large + src
+    for stmt in ("usingL0=FpG;", "usingL1=FpI;", "s0=reduce<L0>(s0);", "s1=reduce<L1>(s1);",
+                 "buf[s]=reduce<L0>(sum[0][m]);", "buf[N+s]=reduce<L1>(sum[1][m]);",
+                 "returnreduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));", "constdoublet=l64_quotient(r0,r1,p0inv_mod_p1);"):
+        assert together.count(stmt) == 1 and stmt in core, stmt
     assert "constboolfold=(products&3)==%d;" % (LB.FOLD - 1) in src
     assert "for(intlev=L-1;lev>=0;lev--){" in src
-    assert "s0=reduce<L0>(s0);" in src and "s1=reduce<L1>(s1);" in src
-    assert "buf[s]=reduce<L0>(sum[0][m]);" in src and "buf[N+s]=reduce<L1>(sum[1][m]);" in src
-    assert "t=reduce<L1>(mulmod<L1>(r1-r0,p0inv_mod_p1));" in src
+    assert "l64_products<LOGN>(sum,buf,key+(((size_t)(r*2+c)*L+lev)*2)*N,false,fold);" in src
+    assert src.count("l64_column_back<LOGN,false>(acc,c,buf,sum,twi0,twi1,p0inv_mod_p1);") == 1
     assert "if(a==0)continue;" in src
     main = open(os.path.join(ROOT, "helm_amd", "csrc", "helm_shortint.hip")).read()
-    assert main.index('#include "helm_pbs64_large.inc"') < main.index('#include "helm_pbs64_n8192.inc"')
+    assert (main.index('#include "helm_pbs64_large_core.inc"') < main.index('#include "helm_pbs64_large.inc"')
+            < main.index('#include "helm_pbs64_n8192.inc"'))

@@ -1,5 +1,5 @@
 """Admission of k = 1, N = 8192 (the 6-bit shortint sets) under HELM_SI_CREATE_N8192 = 256 (include/helm_shortint.h,
-helm_amd/csrc/helm_pbs64_n8192.inc).  The bit may stand alone or beside bits 1, 2, 16, 32 and 64; it matters at N = 8192
+helm_amd/csrc/helm_pbs64_large_core.inc, helm_pbs64_n8192.inc).  The bit may stand alone or beside bits 1, 2, 16, 32 and 64; it matters at N = 8192
 only; without it every call is what it was, byte for byte.  Parameter checks come before the device lookup, so no GPU is
 needed."""
 import ctypes as C
