@@ -1391,10 +1391,28 @@ struct helm_si_wires {
     int64_t n_rows;
 };
 
+// Which bootstrap kernel a context runs: decided once, by si_admit() from (params, flags), and only read afterwards (the
+// setup of the class at creation, convert_bootstrap_key and launch_pbs64 switch on it; the table of forms is at
+// convert_bootstrap_key and in DESIGN.md 4.4.3).
+enum SiClass { SI_TUNED = 0, SI_GENERIC = 1, SI_LARGE = 2, SI_N8192 = 3 }; // the values helm_si_kernel_class returns
+enum SiForm {
+    SI_NO_FORM,  // classes 1 to 3: one kernel each
+    SI_WIDE,     // k_pbs64: N = 512 at k = 1, two levels with wide digits, HELM_SI_SPLIT=0
+    SI_SPLIT,    // k_pbs64s<., false>: k = 1, N >= 1024, grouping 1
+    SI_SPLIT_MB, // k_pbs64s<., true>: grouping > 1
+    SI_K         // k_pbs64k: k = 2 or 3
+};
+struct SiKernelForm {
+    SiClass cls = SI_TUNED;
+    SiForm form = SI_WIDE; // of class 0
+    bool split_key() const { return form == SI_SPLIT || form == SI_SPLIT_MB; } // reads bsk_split through tw_sub
+};
+
 // What a key load decides: the tables of the CRT pair, the keys in their device layouts and the settings that go with them.
 // A primary context owns one (helm_si_ctx::own_keys); a lane holds its primary's, so a key loaded into the primary - which
 // may move the pair and rewrite every table - is what each lane launches with from then on.
 struct SiKeyState {
+    SiKernelForm run;            // helm_si_ctx_create_ex: what every bootstrap launch of the context and its lanes runs
     double *tw[2] = {nullptr, nullptr};
     double n_inv[2] = {0, 0}, two32[2] = {0, 0};
     double p0inv_mod_p1 = 0;
@@ -1407,24 +1425,11 @@ struct SiKeyState {
     int group = 1;               // multi-bit grouping factor (1: classical blind rotation)
     uint16_t *expo = nullptr;    // multi-bit: exponent of the evaluation point per spectrum position [2 halves][N/2]
     double *psi_pow = nullptr;   // multi-bit: psi^t, t < 2N, per field
-    bool use_split = false;
-    // helm_si_ctx_create_ex: k_pbs64_generic runs every bootstrap launch (a shape no tuned build covers, admitted under
-    // HELM_SI_CREATE_ALLOW_GENERIC, or any shape under HELM_SI_CREATE_FORCE_GENERIC): always the 49-bit pair, its own key
-    // layout (k_bsk_convert64_generic), no split key
-    bool gen = false;
-    int gen_d = 1;                        // digit polynomials per batch (tp_batch, tp_fit)
-    size_t gen_lds = 0;                   // LDS bytes per workgroup (TwoPrimeLds<uint64_t>)
-    int gen_per_cu = 1;                   // resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
-    double *twi[2] = {nullptr, nullptr};  // bit-reversed powers of psi^-1 per field (the generic kernel's inverse transforms)
-    // helm_si_ctx_create_ex under HELM_SI_CREATE_LARGE_N at N = 4096: k_pbs64_large runs every bootstrap launch, in the pair
-    // FpG / FpI (pair 2), with the generic key layout (k_bsk_convert64_large) and the inverse tables above
-    bool large = false;
-    size_t large_lds = 0;                 // LDS bytes per workgroup (Large64Lds)
-    int large_per_cu = 1;                 // resident workgroups per CU
-    // helm_si_ctx_create_ex under HELM_SI_CREATE_N8192 at N = 8192: k_pbs64_n8192 runs every bootstrap launch, in the same pair
-    // and key layout as the large-N class (k_bsk_convert64_large<13>), one workgroup per CU
-    bool n8192 = false;
-    size_t n8192_lds = 0;                 // LDS bytes per workgroup (N8192Lds)
+    // classes 1 to 3 (setup_generic, setup_large, setup_n8192): the launch sizing of the class's kernel and its inverse tables
+    size_t lds = 0;                       // LDS bytes per workgroup (TwoPrimeLds<uint64_t>, Large64Lds, N8192Lds)
+    int per_cu = 1;                       // resident workgroups per CU at lds (class 3: 1, launch_pbs64_n8192)
+    int gen_d = 1;                        // class 1: digit polynomials per batch (tp_batch, tp_fit)
+    double *twi[2] = {nullptr, nullptr};  // bit-reversed powers of psi^-1 per field (the kernels' inverse transforms)
     uint64_t *ksk = nullptr;
     int8_t *ksk_planes = nullptr; // matrix-core keyswitch: eight byte planes as signed bytes, B-fragment order
     int ks_kchunks = 0, ks_ctiles = 0, ks_mfma = 1; // HELM_HIP_KS_MFMA=0: the vector-ALU keyswitch for every launch
@@ -1658,19 +1663,32 @@ hipError_t launch_pbs64s_c(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count
     return hipGetLastError();
 }
 
+// The run-time grouping factor as the kernels' compile-time GG: f(std::integral_constant<int, GG>) with GG = 3 or 2 for the
+// multi-bit forms, 0 (the classical form) for anything else.
+template <class F>
+auto with_group(int group, F &&f)
+{
+    if (group == 3) return f(std::integral_constant<int, 3>{});
+    if (group == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
+}
+
+// The run-time logN as the kernels' compile-time LOGN: f(std::integral_constant<int, LOGN>) for LO <= logN <= HI - the call
+// site names the range, so it instantiates the kernels of that range and no other - and `outside` for any other logN.
+template <int LO, int HI, class R, class F>
+R with_logn(int logN, R outside, F &&f)
+{
+    if (logN == LO) return f(std::integral_constant<int, LO>{});
+    if constexpr (LO < HI) return with_logn<LO + 1, HI>(logN, outside, f);
+    else return outside;
+}
 // Two translation units from this one source (Makefile).  The compiler's max-ILP scheduling strategy
 // (-mllvm -amdgpu-sched-strategy=max-ilp; there is no per-function switch) is worth +3.7 % on k_pbs64k and +2.0 % on the
 // multi-bit k_pbs64s, and costs the classical k_pbs64s 0.8 % and its two-level build 1.8 % (same box, alternating,
 // identical ciphertexts: profiles/r03/si_kernel_experiments.txt (15)).  So the launchers of the first two are compiled a
 // second time with -DHELM_SI_TU=1 under that strategy - nothing else of the file is - and the main unit
 // (-DHELM_SI_SPLIT_TU=1), which instantiates none of their kernels, calls them through this one function.  Without the two
-// macros the file is a single unit that holds the function itself.
-
-// does a (tuned) context launch one of the max-ILP unit's kernels?  The shapes helm_si_tu1_launch_pbs64 lists.
-bool si_ilp_shape(const helm_si_ctx *ctx)
-{
-    return ctx->P.k == 3 || ctx->P.k == 2 || (ctx->keys->use_split && ctx->keys->group > 1);
-}
+// macros the file is a single unit that holds the function itself.  It serves the forms SI_K and SI_SPLIT_MB.
 } // namespace
 __attribute__((visibility("hidden"))) hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs, int64_t count,
                                                                         const uint64_t *small, const uint64_t *luts,
@@ -1680,15 +1698,17 @@ hipError_t helm_si_tu1_launch_pbs64(helm_si_ctx *ctx, const void *jobs_v, int64_
                                     const uint64_t *luts, uint64_t *out, int *per_cu)
 {
     const Pbs64Job *jobs = static_cast<const Pbs64Job *>(jobs_v);
-    const helm_si_params &P = ctx->P;
-    if (P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (P.k == 2 && ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (P.k == 2) return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->keys->use_split && ctx->keys->group > 1) {
-        if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, true>(ctx, jobs, count, small, luts, out, per_cu);
-        if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11>, true>(ctx, jobs, count, small, luts, out, per_cu);
+    switch (ctx->keys->run.form) {
+    case SI_K: // (k, N) = (3, 512), (2, 512), (2, 1024): si_supported
+        if (ctx->P.k == 3) return launch_pbs64k_c<Pbs64kCfg<9, 3>>(ctx, jobs, count, small, luts, out, per_cu);
+        if (ctx->logN == 10) return launch_pbs64k_c<Pbs64kCfg<10, 2>>(ctx, jobs, count, small, luts, out, per_cu);
+        return launch_pbs64k_c<Pbs64kCfg<9, 2>>(ctx, jobs, count, small, luts, out, per_cu);
+    case SI_SPLIT_MB:
+        return with_logn<10, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+            return launch_pbs64s_c<Pbs64sCfg<decltype(ln)::value>, true>(ctx, jobs, count, small, luts, out, per_cu);
+        });
+    default: return hipErrorInvalidValue;
     }
-    return hipErrorInvalidValue;
 }
 #endif
 #if HELM_SI_TU == 0 // ==== everything below: the main unit only ===============================================
@@ -1701,32 +1721,18 @@ namespace {
 // what the two large-N kernels share: the pair FpG / FpI, the transforms, the pieces of a step, the key conversion
 #include "helm_pbs64_large_core.inc"
 
-// The run-time grouping factor as the kernels' compile-time GG: f(std::integral_constant<int, GG>) with GG = 3 or 2 for the
-// multi-bit forms, 0 (the classical form) for anything else.
-template <class F>
-auto with_group(int group, F &&f)
-{
-    if (group == 3) return f(std::integral_constant<int, 3>{});
-    if (group == 2) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 0>{});
-}
-
 // k_pbs64_large: k = 1, N = 4096 (helm_si_ctx_create_ex with HELM_SI_CREATE_LARGE_N)
 #include "helm_pbs64_large.inc"
 
 hipError_t launch_pbs64_large(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
-                              const uint64_t *luts, uint64_t *out, int *per_cu)
+                              const uint64_t *luts, uint64_t *out)
 {
     // (the dynamic LDS attribute is set by helm_si_ctx_create_ex: setup_large)
     const SiKeyState &K = *ctx->keys;
-    if (per_cu) {
-        *per_cu = K.large_per_cu;
-        return hipSuccess;
-    }
     if (ctx->logN != 12 || ctx->P.k != 1) return hipErrorInvalidValue;
     if (K.group > 1 && !K.psi_pow) return hipErrorInvalidValue;
     with_group(K.group, [&](auto g) {
-        hipLaunchKernelGGL((k_pbs64_large<12, decltype(g)::value>), dim3((unsigned)count), dim3(L64_THREADS), K.large_lds,
+        hipLaunchKernelGGL((k_pbs64_large<12, decltype(g)::value>), dim3((unsigned)count), dim3(L64_THREADS), K.lds,
                            ctx->stream, jobs, small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n,
                            ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1);
     });
@@ -1745,14 +1751,10 @@ const void *pbs64_large_kernel(int group)
 // The kernel's accumulator rows are indexed by blockIdx.x, so a launch is at most as wide as the context's row buffer: one
 // round (a workgroup per CU).  A wider batch goes out in chunks of a round, one after the other on the context's stream.
 hipError_t launch_pbs64_n8192(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
-                              const uint64_t *luts, uint64_t *out, int *per_cu)
+                              const uint64_t *luts, uint64_t *out)
 {
     // (the dynamic LDS attribute is set by helm_si_ctx_create_ex: setup_n8192)
     const SiKeyState &K = *ctx->keys;
-    if (per_cu) {
-        *per_cu = 1;
-        return hipSuccess;
-    }
     if (ctx->logN != N8192_LOGN || ctx->P.k != 1) return hipErrorInvalidValue;
     const int64_t rows = std::max(ctx->n_cus, 1); // (the rows of d_acc8192: alloc_acc8192)
     if (!ctx->d_acc8192) return hipErrorInvalidValue;
@@ -1760,7 +1762,7 @@ hipError_t launch_pbs64_n8192(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t co
     for (int64_t off = 0; off < count; off += rows) {
         const int64_t chunk = std::min(rows, count - off);
         with_group(K.group, [&](auto g) {
-            hipLaunchKernelGGL(k_pbs64_n8192<decltype(g)::value>, dim3((unsigned)chunk), dim3(L64_THREADS), K.n8192_lds,
+            hipLaunchKernelGGL(k_pbs64_n8192<decltype(g)::value>, dim3((unsigned)chunk), dim3(L64_THREADS), K.lds,
                                ctx->stream, jobs + off, small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out,
                                ctx->d_acc8192, ctx->P.n, ctx->P.pbs_l, ctx->P.pbs_logB, K.p0inv_mod_p1);
         });
@@ -1775,79 +1777,67 @@ const void *pbs64_n8192_kernel(int group)
     return with_group(group, [](auto g) { return reinterpret_cast<const void *>(k_pbs64_n8192<decltype(g)::value>); });
 }
 
-template <int LOGN, int GG>
-hipError_t launch_pbs64_generic_g(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
-                                  const uint64_t *luts, uint64_t *out)
-{
-    const SiKeyState &K = *ctx->keys;
-    hipLaunchKernelGGL((k_pbs64_generic<LOGN, GG>), dim3((unsigned)count), dim3(TP_THREADS), K.gen_lds, ctx->stream, jobs,
-                       small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0], K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.k,
-                       ctx->P.pbs_l, ctx->P.pbs_logB, K.gen_d, K.p0inv_mod_p1);
-    return hipGetLastError();
-}
-
-template <int LOGN>
-hipError_t launch_pbs64_generic_t(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
-                                  const uint64_t *luts, uint64_t *out, int *per_cu)
+hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
+                                const uint64_t *luts, uint64_t *out)
 {
     // (the dynamic LDS attribute is set by helm_si_ctx_create_ex, at the largest layout of this N)
-    if (per_cu) {
-        *per_cu = ctx->keys->gen_per_cu;
-        return hipSuccess;
-    }
-    return with_group(ctx->keys->group, [&](auto g) {
-        return launch_pbs64_generic_g<LOGN, decltype(g)::value>(ctx, jobs, count, small, luts, out);
+    const SiKeyState &K = *ctx->keys;
+    return with_logn<8, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+        with_group(K.group, [&](auto g) {
+            hipLaunchKernelGGL((k_pbs64_generic<decltype(ln)::value, decltype(g)::value>), dim3((unsigned)count),
+                               dim3(TP_THREADS), K.lds, ctx->stream, jobs, small, luts, K.bsk, K.tw[0], K.tw[1], K.twi[0],
+                               K.twi[1], K.psi_pow, out, ctx->P.n, ctx->P.k, ctx->P.pbs_l, ctx->P.pbs_logB, K.gen_d,
+                               K.p0inv_mod_p1);
+        });
+        return hipGetLastError();
     });
-}
-
-hipError_t launch_pbs64_generic(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
-                                const uint64_t *luts, uint64_t *out, int *per_cu)
-{
-    switch (ctx->logN) {
-    case 8: return launch_pbs64_generic_t<8>(ctx, jobs, count, small, luts, out, per_cu);
-    case 9: return launch_pbs64_generic_t<9>(ctx, jobs, count, small, luts, out, per_cu);
-    case 10: return launch_pbs64_generic_t<10>(ctx, jobs, count, small, luts, out, per_cu);
-    case 11: return launch_pbs64_generic_t<11>(ctx, jobs, count, small, luts, out, per_cu);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int GG>
-const void *pbs64_generic_kernel_g(int logN)
-{
-    return logN == 8    ? reinterpret_cast<const void *>(k_pbs64_generic<8, GG>)
-           : logN == 9  ? reinterpret_cast<const void *>(k_pbs64_generic<9, GG>)
-           : logN == 10 ? reinterpret_cast<const void *>(k_pbs64_generic<10, GG>)
-                        : reinterpret_cast<const void *>(k_pbs64_generic<11, GG>);
 }
 
 // group: the multi-bit grouping factor (2 or 3), anything else: the classical form
 const void *pbs64_generic_kernel(int logN, int group)
 {
-    return with_group(group, [&](auto g) { return pbs64_generic_kernel_g<decltype(g)::value>(logN); });
+    return with_logn<8, 11>(logN, (const void *)nullptr, [&](auto ln) {
+        return with_group(group, [](auto g) {
+            return reinterpret_cast<const void *>(k_pbs64_generic<decltype(ln)::value, decltype(g)::value>);
+        });
+    });
 }
 
+// per_cu: not a launch but the question helm_si_round_capacity asks - how many workgroups of the context's kernel a CU holds
+// (classes 1 to 3: what their setup stored; a tuned form: the occupancy of the build it would launch)
 hipError_t launch_pbs64(helm_si_ctx *ctx, const Pbs64Job *jobs, int64_t count, const uint64_t *small,
                         const uint64_t *luts, uint64_t *out, int *per_cu = nullptr)
 {
-    if (ctx->keys->n8192) return launch_pbs64_n8192(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->keys->large) return launch_pbs64_large(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->keys->gen) return launch_pbs64_generic(ctx, jobs, count, small, luts, out, per_cu);
-    const helm_si_params &P = ctx->P;
-    if (si_ilp_shape(ctx)) return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu);
-    if (ctx->keys->use_split) {
-        if (P.pbs_l == 1) {
-            if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10>, false>(ctx, jobs, count, small, luts, out, per_cu);
-            if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11>, false>(ctx, jobs, count, small, luts, out, per_cu);
-        } else {
-            if (ctx->logN == 10) return launch_pbs64s_c<Pbs64sCfg<10, 2>, false>(ctx, jobs, count, small, luts, out, per_cu);
-            if (ctx->logN == 11) return launch_pbs64s_c<Pbs64sCfg<11, 2>, false>(ctx, jobs, count, small, luts, out, per_cu);
-        }
+    const SiKeyState &K = *ctx->keys;
+    if (per_cu && K.run.cls != SI_TUNED) {
+        *per_cu = K.per_cu;
+        return hipSuccess;
     }
-#define PBS64_CASE(LN, LV) \
-    if (ctx->logN == LN && P.pbs_l == LV) return launch_pbs64_c<Pbs64Cfg<LN, LV>>(ctx, jobs, count, small, luts, out, nullptr, -1, 0, 0, 0, per_cu);
-    PBS64_CASE(9, 1) PBS64_CASE(9, 2) PBS64_CASE(10, 1) PBS64_CASE(10, 2) PBS64_CASE(11, 1) PBS64_CASE(11, 2)
-#undef PBS64_CASE
+    switch (K.run.cls) {
+    case SI_N8192: return launch_pbs64_n8192(ctx, jobs, count, small, luts, out);
+    case SI_LARGE: return launch_pbs64_large(ctx, jobs, count, small, luts, out);
+    case SI_GENERIC: return launch_pbs64_generic(ctx, jobs, count, small, luts, out);
+    case SI_TUNED: break;
+    }
+    switch (K.run.form) {
+    case SI_K:
+    case SI_SPLIT_MB: return helm_si_tu1_launch_pbs64(ctx, jobs, count, small, luts, out, per_cu); // the max-ILP unit's
+    case SI_SPLIT: // (one or two levels: si_supported)
+        if (ctx->P.pbs_l == 1)
+            return with_logn<10, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+                return launch_pbs64s_c<Pbs64sCfg<decltype(ln)::value>, false>(ctx, jobs, count, small, luts, out, per_cu);
+            });
+        return with_logn<10, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+            return launch_pbs64s_c<Pbs64sCfg<decltype(ln)::value, 2>, false>(ctx, jobs, count, small, luts, out, per_cu);
+        });
+    case SI_WIDE:
+        return with_logn<9, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+            constexpr int LN = decltype(ln)::value;
+            return ctx->P.pbs_l == 1 ? launch_pbs64_c<Pbs64Cfg<LN, 1>>(ctx, jobs, count, small, luts, out, nullptr, -1, 0, 0, 0, per_cu)
+                                     : launch_pbs64_c<Pbs64Cfg<LN, 2>>(ctx, jobs, count, small, luts, out, nullptr, -1, 0, 0, 0, per_cu);
+        });
+    case SI_NO_FORM: break;
+    }
     return hipErrorInvalidValue;
 }
 
@@ -2132,6 +2122,21 @@ int apply_many_luts_stage(helm_si_ctx *ctx, const uint64_t *src, const int32_t *
     return apply_luts_device(ctx, src, ctx->d_stage.p, ks, pbs, luts, n_luts);
 }
 
+// `polys` polynomials of K1 x K1 x l GGSW rows at `src` into k_pbs64s' half-transform order at `dst`, both fields of the 49-bit pair,
+// scaled by n_inv per field (the split key of a context, and the probe below)
+void launch_convert64s(helm_si_ctx *ctx, const uint64_t *src, double *dst, size_t polys, const double (&n_inv)[2], int K1, int l)
+{
+    const SiKeyState &K = *ctx->keys;
+    with_logn<10, 11>(ctx->logN, false, [&](auto ln) {
+        constexpr int LN = decltype(ln)::value;
+        hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, src, dst, K.tw[0],
+                           K.tw_sub, n_inv[0], K.two32[0], K1, 0, l);
+        hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, src, dst, K.tw[1],
+                           K.tw_sub + ctx->P.N, n_inv[1], K.two32[1], K1, 1, l);
+        return true;
+    });
+}
+
 // Multi-bit: which power of psi is the evaluation point of each spectrum position, in the order the key
 // words (and the transform outputs of k_pbs64s) are held?  Transform the polynomial X through the key
 // conversion kernel (one "key" of one polynomial) and look the values up among the powers of psi.
@@ -2152,15 +2157,7 @@ int probe_spectrum_positions(helm_si_ctx *ctx)
     double *d_out = static_cast<double *>(t_out.p);
     HIP_TRY(hipMemcpy(d_x, xpoly.data(), sizeof(uint64_t) * N, hipMemcpyHostToDevice));
     // one polynomial, K1 = 1: blocks (poly 0, half h) write d_out[(f * 2 + h) * N/2 ...] scaled by 1 (n_inv = 1)
-#define PROBE(LN)                                                                                                        \
-    if (ctx->logN == LN) {                                                                                              \
-        hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, K.tw[0],           \
-                           K.tw_sub, 1.0, K.two32[0], 1, 0, 1);                                                          \
-        hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3(2), dim3(64), 0, ctx->stream, d_x, d_out, K.tw[1],           \
-                           K.tw_sub + (size_t)2 * H, 1.0, K.two32[1], 1, 1, 1);                                          \
-    }
-    PROBE(10) PROBE(11)
-#undef PROBE
+    launch_convert64s(ctx, d_x, d_out, 1, {1.0, 1.0}, 1, 1);
     HIP_TRY(hipGetLastError());
     std::vector<double> val((size_t)4 * H), pw((size_t)4 * N);
     HIP_TRY(hipMemcpyAsync(val.data(), d_out, sizeof(double) * 4 * H, hipMemcpyDeviceToHost, ctx->stream));
@@ -2442,14 +2439,13 @@ int setup_generic(helm_si_ctx *ctx)
     if (fit.per_cu < 1)
         return fail(HELM_ERR_INVALID, "k_pbs64_generic: no workgroup of " + std::to_string(fit.lds) + " B LDS fits a CU for this shape");
     K.gen_d = fit.d;
-    K.gen_lds = fit.lds;
-    K.gen_per_cu = fit.per_cu;
-    K.gen = true;
+    K.lds = fit.lds;
+    K.per_cu = fit.per_cu;
     if (getenv("HELM_HIP_VERBOSE")) {
         hipFuncAttributes fa{};
         (void)hipFuncGetAttributes(&fa, kern);
         fprintf(stderr, "[helm_si] k_pbs64_generic N=%d k=%d l=%d g=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n",
-                N, P.k, P.pbs_l, group, K.gen_d, K.gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, K.gen_per_cu);
+                N, P.k, P.pbs_l, group, K.gen_d, K.lds, fa.numRegs, (size_t)fa.localSizeBytes, K.per_cu);
     }
     return 0;
 }
@@ -2512,13 +2508,12 @@ int setup_large(helm_si_ctx *ctx)
     SiKeyState &K = *ctx->keys;
     const int N = ctx->P.N;
     static std::atomic<bool> attr_done[64], conv_done[64];
-    K.large_lds = Large64Lds(N, ctx->P.n).bytes;
+    K.lds = Large64Lds(N, ctx->P.n).bytes;
     if (int rc = setup_large_class(ctx, "k_pbs64_large", " N=4096", pbs64_large_kernel, attr_done, Large64Lds(N, 1024).bytes,
-                                   K.large_lds, &K.large_per_cu))
+                                   K.lds, &K.per_cu))
         return rc;
     HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_large<12>)},
                           sizeof(double) * 2 * (size_t)N));
-    K.large = true;
     return 0;
 #endif
 }
@@ -2550,16 +2545,27 @@ int setup_n8192(helm_si_ctx *ctx)
 #else
     SiKeyState &K = *ctx->keys;
     static std::atomic<bool> attr_done[64], conv_done[64];
-    K.n8192_lds = N8192Lds(ctx->P.n).bytes;
-    int nb = 0; // (one workgroup per CU: launch_pbs64_n8192)
-    if (int rc = setup_large_class(ctx, "k_pbs64_n8192", "", pbs64_n8192_kernel, attr_done, N8192Lds(1024).bytes, K.n8192_lds, &nb))
+    K.lds = N8192Lds(ctx->P.n).bytes;
+    if (int rc = setup_large_class(ctx, "k_pbs64_n8192", "", pbs64_n8192_kernel, attr_done, N8192Lds(1024).bytes, K.lds, &K.per_cu))
         return rc;
+    K.per_cu = 1; // (whatever fits: a launch is one workgroup per CU, launch_pbs64_n8192)
     HIP_TRY(lds_attr_once(conv_done, ctx->device, {reinterpret_cast<const void *>(k_bsk_convert64_large<N8192_LOGN>)},
                           sizeof(double) * 2 * (size_t)ctx->P.N));
-    if (int rc = alloc_acc8192(ctx)) return rc;
-    K.n8192 = true;
-    return 0;
+    return alloc_acc8192(ctx);
 #endif
+}
+
+// What a new context sets up for its kernel: the tables of its pair and what its class adds to them (a tuned form: nothing)
+int setup_class(helm_si_ctx *ctx, int pair)
+{
+    if (int rc = setup_pair_tables(ctx, pair)) return rc;
+    switch (ctx->keys->run.cls) {
+    case SI_GENERIC: return setup_generic(ctx);
+    case SI_LARGE: return setup_large(ctx);
+    case SI_N8192: return setup_n8192(ctx);
+    case SI_TUNED: break;
+    }
+    return 0;
 }
 
 // The step bound of a bootstrapping key: the exact integer coefficient of one blind-rotation step is at most B/2 x the largest
@@ -2606,20 +2612,85 @@ int begin_key_load(helm_si_ctx *ctx, const char *what)
     return 0;
 }
 
-} // namespace
-
-extern "C" {
-
-int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx **out)
+// A bootstrapping key in standard form (d_std: `polys` polynomials on the device, [i][lev][r][c][N]) into the layout(s) the
+// context's kernel reads, in the fields of the pair its tables hold.  Buffers are allocated by the first key and refilled by
+// every later one.
+//
+//   class     form      kernel               fills                      conversion kernel(s)                    pair
+//   tuned     wide      k_pbs64              bsk                        k_bsk_convert64 per field               0
+//   tuned     split     k_pbs64s<., false>   bsk and bsk_split          k_bsk_convert64, k_bsk_convert64s       0
+//   tuned     split mb  k_pbs64s<., true>    bsk_split (expo: probed    k_bsk_convert64s                        0
+//                                            once, after the first key)
+//   tuned     k         k_pbs64k             bsk                        k_bsk_convert64 per field               0; N = 512: 0 or 1,
+//                                                                                                               after the key at hand
+//   generic             k_pbs64_generic      bsk, [i][r][c][lev][f][N]  k_bsk_convert64_generic, both fields    0
+//   large-N             k_pbs64_large        bsk, the same layout       k_bsk_convert64_large<12>               2
+//   N = 8192            k_pbs64_n8192        bsk, the same layout       k_bsk_convert64_large<13>               2
+int convert_bootstrap_key(helm_si_ctx *ctx, const uint64_t *d_std, size_t n_words, size_t polys)
 {
-    return helm_si_ctx_create_ex(device_id, params, 0, out);
+    SiKeyState &K = *ctx->keys;
+    const helm_si_params &P = ctx->P;
+    const int K1 = P.k + 1;
+    // [i][r][c][lev][f][N], bit-reversed transform order, both fields in one launch
+    const auto both_fields = [&](auto kern, unsigned threads, size_t lds) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)polys), dim3(threads), lds, ctx->stream, d_std, K.bsk, K.tw[0], K.tw[1],
+                           K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], K1, P.pbs_l);
+    };
+    if (!K.bsk && K.run.form != SI_SPLIT_MB) HIP_TRY(hipMalloc(&K.bsk, n_words * 2 * sizeof(double)));
+    if (!K.bsk_split && K.run.split_key()) HIP_TRY(hipMalloc(&K.bsk_split, n_words * 2 * sizeof(double)));
+    switch (K.run.cls) {
+    case SI_N8192: both_fields(k_bsk_convert64_large<N8192_LOGN>, L64_THREADS, sizeof(double) * 2 * (size_t)P.N); break; // (the two-
+    case SI_LARGE: both_fields(k_bsk_convert64_large<12>, L64_THREADS, sizeof(double) * 2 * (size_t)P.N); break; // field buffer in LDS)
+    case SI_GENERIC:
+        with_logn<8, 11>(ctx->logN, false, [&](auto ln) {
+            both_fields(k_bsk_convert64_generic<decltype(ln)::value>, TP_THREADS, 0);
+            return true;
+        });
+        break;
+    case SI_TUNED: break; // by its form, below
+    }
+    // the lane order of k_pbs64 and k_pbs64k, one launch per field (pair 1 is built for N = 512 only)
+    const auto wide = [&] {
+        const auto fields = [&](auto kern0, auto kern1) {
+            hipLaunchKernelGGL(kern0, dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[0], K.n_inv[0],
+                               K.two32[0], K1, P.pbs_l, 0);
+            hipLaunchKernelGGL(kern1, dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[1], K.n_inv[1],
+                               K.two32[1], K1, P.pbs_l, 1);
+            return true;
+        };
+        if (K.pair == 1) fields(k_bsk_convert64<J0, 9>, k_bsk_convert64<J1, 9>);
+        else with_logn<9, 11>(ctx->logN, false, [&](auto ln) {
+            return fields(k_bsk_convert64<F0, decltype(ln)::value>, k_bsk_convert64<F1, decltype(ln)::value>);
+        });
+    };
+    // the half-transform order of k_pbs64s
+    const auto split = [&] { launch_convert64s(ctx, d_std, K.bsk_split, polys, K.n_inv, K1, P.pbs_l); };
+    switch (K.run.form) {
+    case SI_WIDE:
+    case SI_K: wide(); break;
+    case SI_SPLIT: wide(), split(); break;
+    case SI_SPLIT_MB: split(); break;
+    case SI_NO_FORM: break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
-int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out)
+// What a class has of its own beside its kernel, by SiClass: the CRT pair its context is created in (0: FpG / FpG2, 2:
+// FpG / FpI; an SI_K context may move to pair 1 with a key, helm_si_load_bootstrap_key), the capacity p0 p1 / 2 of that pair
+// (pair 2: 2^97.87), its name in the key-capacity error and in helm_wop_ctx_create's refusal.
+struct SiClassFacts { int pair; long double half; const char *noun, *wop; };
+constexpr long double SI_HALF_F = (long double)F0::P * F1::P / 2, SI_HALF_L = (long double)L0::P * L1::P / 2;
+constexpr SiClassFacts SI_CLASS[4] = {
+    {0, SI_HALF_F, "tuned", nullptr},
+    {0, SI_HALF_F, "generic", "generic bootstrap kernel (helm_si_kernel_class 1)"},
+    {2, SI_HALF_L, "large-N", "large-N bootstrap kernel (helm_si_kernel_class 2)"},
+    {2, SI_HALF_L, "N = 8192", "N = 8192 bootstrap kernel (HELM_SI_CREATE_N8192, helm_si_kernel_class 3)"}};
+
+// helm_si_ctx_create_ex, the half without a device: whether (params, flags) is admitted and, if so, what the context runs
+// (*run), its order (helm_si_pbs_order) and its grouping factor (1: classical blind rotation)
+int si_admit(const helm_si_params &P, int flags, SiKernelForm *run, int *order_out, int *group_out)
 {
-    if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    const helm_si_params &P = *params;
     // HELM_SI_CREATE_LARGE_N matters at N >= 4096 only: below, the call is the same call without the bit
     // HELM_SI_CREATE_N8192 matters at N >= 8192 only, in the same way; beside HELM_SI_CREATE_LARGE_N, N selects the kernel
     const bool n8192 = (flags & HELM_SI_CREATE_N8192) != 0 && P.N >= 8192;
@@ -2692,16 +2763,44 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
         return fail(HELM_ERR_INVALID, "grouping_factor must be 0..3 and divide n");
     if (group > 1 && !gen_mb && !large_mb && !(P.pbs_l == 1 && P.N >= 1024))
         return fail(HELM_ERR_INVALID, "multi-bit blind rotation is built for pbs_l = 1, N >= 1024 (every tfhe multi-bit set)");
-    // exactness: |sum| <= (k+1) * l * N * (B/2) * 2^63 must stay below p0 * p1 / 2
+    run->cls = n8192 ? SI_N8192 : large ? SI_LARGE : run_generic ? SI_GENERIC : SI_TUNED;
+    // exactness: |sum| <= (k+1) * l * N * (B/2) * 2^63 must stay below p0 * p1 / 2 of the class's pair
     {
         const long double bound = (long double)(P.k + 1) * P.pbs_l * P.N * (long double)(1ull << (P.pbs_logB - 1)) *
                                   9223372036854775808.0L;
-        // (a large-N context computes in its own pair: p0 p1 / 2 = 2^97.87)
-        const long double half = (large || n8192) ? (long double)L0::P * (long double)L1::P / 2 : (long double)F0::P * (long double)F1::P / 2;
-        if (bound * 1.001L >= half) return fail(HELM_ERR_INVALID, "parameter set exceeds the two-prime NTT capacity");
+        if (bound * 1.001L >= SI_CLASS[run->cls].half) return fail(HELM_ERR_INVALID, "parameter set exceeds the two-prime NTT capacity");
         // per-field operands: digits must be far below p
         if ((double)(1ull << (P.pbs_logB - 1)) * 4 >= F1::P / 2) return fail(HELM_ERR_INVALID, "pbs_logB too large");
     }
+    // The tuned form.  The eight-wave kernel (split transforms) where it exists: k = 1, N >= 1024, one level or two with
+    // digits of at most 15 bits, unless HELM_SI_SPLIT=0; its multi-bit build for every tuned multi-bit shape (k = 1,
+    // pbs_l = 1, N >= 1024: the checks above).
+    const char *split_env = getenv("HELM_SI_SPLIT");
+    const bool split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && P.N >= 1024 && P.k == 1 &&
+                       !(split_env && atoi(split_env) == 0);
+    run->form = run->cls != SI_TUNED ? SI_NO_FORM : P.k >= 2 ? SI_K : group > 1 ? SI_SPLIT_MB : split ? SI_SPLIT : SI_WIDE;
+    *order_out = pbs_ks ? 0 : 1;
+    *group_out = group;
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int helm_si_ctx_create(int device_id, const helm_si_params *params, helm_si_ctx **out)
+{
+    return helm_si_ctx_create_ex(device_id, params, 0, out);
+}
+
+int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags, helm_si_ctx **out)
+{
+    if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const helm_si_params &P = *params;
+    SiKernelForm run;
+    int order = 1, group = 1;
+    if (int rc = si_admit(P, flags, &run, &order, &group)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(HELM_ERR_NO_DEVICE, "no HIP device visible (this engine has no CPU fallback)");
@@ -2715,10 +2814,10 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     if (!ctx) return fail(HELM_ERR_OOM, "ctx");
     ctx->device = device_id;
     ctx->P = P;
-    ctx->order = pbs_ks ? 0 : 1;
+    ctx->order = order;
     ctx->n_cus = prop.multiProcessorCount;
     while ((1 << ctx->logN) < P.N) ctx->logN++;
-    ctx->delta = (1ull << 63) / (uint64_t)t;
+    ctx->delta = (1ull << 63) / (uint64_t)(P.message_modulus * P.carry_modulus);
     ctx->own_keys.reset(new (std::nothrow) SiKeyState());
     ctx->keys = ctx->own_keys.get();
     if (!ctx->keys) {
@@ -2728,44 +2827,22 @@ int helm_si_ctx_create_ex(int device_id, const helm_si_params *params, int flags
     SiKeyState &K = *ctx->keys;
     HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
-    const int N = P.N;
-    if (int rc = setup_pair_tables(ctx, (large || n8192) ? 2 : 0)) {
+    const int N = P.N, pair = SI_CLASS[run.cls].pair;
+    K.run = run;
+    K.group = group;
+    if (int rc = setup_class(ctx, pair)) {
         (void)helm_si_ctx_destroy(ctx);
         return rc;
     }
-    if (large) {
-        if (int rc = setup_large(ctx)) {
-            (void)helm_si_ctx_destroy(ctx);
-            return rc;
-        }
-    }
-    if (n8192) {
-        if (int rc = setup_n8192(ctx)) {
-            (void)helm_si_ctx_destroy(ctx);
-            return rc;
-        }
-    }
-    if (run_generic) {
-        if (int rc = setup_generic(ctx)) {
-            (void)helm_si_ctx_destroy(ctx);
-            return rc;
-        }
-    }
-    K.group = group;
-    if (group > 1) { // the 2N powers of psi per field of the context's pair: monomial products in the transform domain
+    if (K.group > 1) { // the 2N powers of psi per field of the context's pair: monomial products in the transform domain
         std::vector<double> pw((size_t)4 * N);
-        const int pair = large_mb ? 2 : 0;
         for (int f = 0; f < 2; f++) power_table(pw.data() + (size_t)f * 2 * N, si_psi(N, pair, f), si_modulus(pair, f), 2 * N, 0);
         HIP_TRY(hipMalloc(&K.psi_pow, pw.size() * sizeof(double)));
         HIP_TRY(hipMemcpy(K.psi_pow, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    // eight-wave kernel (split transforms) where it exists: N >= 1024, one or two levels (HELM_SI_SPLIT=0: off)
     static_assert(Pbs64sCfg<11, 2>::BYTES <= 160 * 1024, "k_pbs64s<11, 2> must fit the LDS of a CU");
-    K.use_split = ((P.pbs_l == 1 && P.pbs_logB <= 24) || (P.pbs_l == 2 && P.pbs_logB <= 15)) && N >= 1024 && P.k == 1;
     if (const char *v = getenv("HELM_HIP_KS_MFMA")) K.ks_mfma = atoi(v);
-    if (const char *v = getenv("HELM_SI_SPLIT")) K.use_split = (K.use_split && atoi(v) != 0) || group > 1;
-    if (K.gen || K.large || K.n8192) K.use_split = false; // (a generic or large-N context reads one key layout, multi-bit too)
-    if (K.use_split) {
+    if (K.run.split_key()) { // the half-transform tables of k_pbs64s and its key conversion
         // half h of field f, stage with m' groups, group i': full table entry 2m' + h m' + i'
         std::vector<double> sub((size_t)4 * (N / 2), 0.0), full(N);
         for (int f = 0; f < 2; f++) {
@@ -2807,7 +2884,7 @@ int helm_si_ctx_fork(helm_si_ctx *primary, helm_si_ctx **out)
         return fail(HELM_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
     }
     ctx->stream = ctx->own_stream;
-    if (primary->keys->n8192) { // a lane launches on its own stream: accumulator rows of its own
+    if (primary->keys->run.cls == SI_N8192) { // a lane launches on its own stream: accumulator rows of its own
         if (int rc = alloc_acc8192(ctx)) {
             (void)hipStreamDestroy(ctx->own_stream);
             delete ctx;
@@ -2890,7 +2967,7 @@ int64_t helm_si_wire_words(const helm_si_ctx *ctx)
 int helm_si_kernel_class(const helm_si_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->keys->n8192 ? 3 : ctx->keys->large ? 2 : ctx->keys->gen ? 1 : 0;
+    return ctx->keys->run.cls;
 }
 
 int helm_si_set_stream(helm_si_ctx *ctx, void *hip_stream)
@@ -2948,16 +3025,13 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         // N = 2048, logB = 21, g = 3 stays at 0.71 of the limit); this one is sufficient for the key at hand and every input.
         // A key beyond it is refused before anything of the context is touched: the context keeps the key and state it had.
         const size_t subsets = (size_t)1 << K.group;
-        // (a large-N or N = 8192 context computes in its own pair: p0 p1 / 2 = 2^97.87)
-        const long double half = (K.large || K.n8192) ? (long double)L0::P * (long double)L1::P / 2
-                                                      : (long double)F0::P * (long double)F1::P / 2;
+        const SiClassFacts &C = SI_CLASS[K.run.cls]; // (the capacity of the pair the class computes in)
         const long double key_bound = key_step_bound(P, bsk_std, n_ggsw / subsets, subsets * per_ggsw);
-        if (key_bound * 1.001L >= half) {
+        if (key_bound * 1.001L >= C.half) {
             char ratio[32];
-            snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / half);
-            return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the ") +
-                                              (K.n8192 ? "N = 8192" : K.large ? "large-N" : K.gen ? "generic" : "tuned") + " multi-bit kernel: its largest group sum is " +
-                                              ratio + " of p0 p1 / 2");
+            snprintf(ratio, sizeof ratio, "%.3Lf", key_bound / C.half);
+            return fail(HELM_ERR_INVALID, std::string("bootstrapping key exceeds the two-prime NTT capacity of the ") + C.noun +
+                                              " multi-bit kernel: its largest group sum is " + ratio + " of p0 p1 / 2");
         }
     }
     struct Tmp {
@@ -2966,10 +3040,9 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
     } t_std; // freed on every return path
     HIP_TRY(hipMalloc(&t_std.p, n_words * sizeof(uint64_t)));
     uint64_t *d_std = static_cast<uint64_t *>(t_std.p);
-    if (!K.bsk && (K.group == 1 || K.gen || K.large || K.n8192)) HIP_TRY(hipMalloc(&K.bsk, n_words * 2 * sizeof(double)));
-    if (P.k >= 2 && P.N == 512 && P.pbs_l == 1 && K.group == 1 && !K.gen) {
-        // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts through CONV below, as
-        // every k = 1 set's): the CRT pair follows the key at hand, a step being one GGSW (src is [i][lev][r][c][N]).  With the
+    if (K.run.form == SI_K && P.N == 512) {
+        // k_pbs64k contexts at N = 512 (N = 1024 is built for the 49-bit pair only: its key converts as every k = 1 set's):
+        // the CRT pair follows the key at hand, a step being one GGSW (src is [i][lev][r][c][N]).  With the
         // step bound below p p' / 2 of the 46-bit pair (and with digits of at most 17 bits, whose products with b^3 stay exact
         // doubles): FpJ / FpJ2, whose headroom drops stage 2's modular multiplications and most recentrings (ntt_fp64.h);
         // otherwise the 49-bit pair.  HELM_SI_FIELD=49 keeps the 49-bit pair.
@@ -2984,51 +3057,9 @@ int helm_si_load_bootstrap_key(helm_si_ctx *ctx, const uint64_t *bsk_std, size_t
         }
     }
     HIP_TRY(hipMemcpyAsync(d_std, bsk_std, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (K.n8192 || K.large) { // the generic layout in the pair FpG / FpI, the two-field buffer in dynamic LDS
-        const auto conv = K.n8192 ? k_bsk_convert64_large<N8192_LOGN> : k_bsk_convert64_large<12>;
-        hipLaunchKernelGGL(conv, dim3((unsigned)polys), dim3(L64_THREADS), sizeof(double) * 2 * (size_t)P.N, ctx->stream, d_std,
-                           K.bsk, K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l);
-    } else if (K.gen) {
-        // the generic kernel's layout: [i][r][c][lev][f][N], bit-reversed transform order, both fields (k_bsk_convert64_generic)
-#define GEN64_CONVERT(LN)                                                                                                 \
-    hipLaunchKernelGGL(k_bsk_convert64_generic<LN>, dim3((unsigned)polys), dim3(TP_THREADS), 0, ctx->stream, d_std, K.bsk,   \
-                       K.tw[0], K.tw[1], K.n_inv[0], K.n_inv[1], K.two32[0], K.two32[1], (int)K1, P.pbs_l)
-        if (ctx->logN == 8) GEN64_CONVERT(8);
-        else if (ctx->logN == 9) GEN64_CONVERT(9);
-        else if (ctx->logN == 10) GEN64_CONVERT(10);
-        else GEN64_CONVERT(11);
-#undef GEN64_CONVERT
-    } else if (K.pair == 1) { // (N = 512 only)
-        hipLaunchKernelGGL((k_bsk_convert64<J0, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[0],
-                           K.n_inv[0], K.two32[0], (int)K1, P.pbs_l, 0);
-        hipLaunchKernelGGL((k_bsk_convert64<J1, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, K.tw[1],
-                           K.n_inv[1], K.two32[1], (int)K1, P.pbs_l, 1);
-    }
-#define CONV(LN)                                                                                                     \
-    if (ctx->logN == LN && K.group == 1 && !K.pair && !K.gen) {                                                      \
-        hipLaunchKernelGGL((k_bsk_convert64<F0, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, \
-                           K.tw[0], K.n_inv[0], K.two32[0], (int)K1, P.pbs_l, 0);                                    \
-        hipLaunchKernelGGL((k_bsk_convert64<F1, LN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std, K.bsk, \
-                           K.tw[1], K.n_inv[1], K.two32[1], (int)K1, P.pbs_l, 1);                                    \
-    }
-    CONV(9) CONV(10) CONV(11)
-#undef CONV
-    if (K.use_split) {
-        if (!K.bsk_split) HIP_TRY(hipMalloc(&K.bsk_split, n_words * 2 * sizeof(double)));
-#define CONVS(LN)                                                                                                       \
-    if (ctx->logN == LN) {                                                                                              \
-        hipLaunchKernelGGL((k_bsk_convert64s<F0, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, d_std,     \
-                           K.bsk_split, K.tw[0], K.tw_sub, K.n_inv[0], K.two32[0], (int)K1, 0, P.pbs_l);                 \
-        hipLaunchKernelGGL((k_bsk_convert64s<F1, LN>), dim3((unsigned)(polys * 2)), dim3(64), 0, ctx->stream, d_std,     \
-                           K.bsk_split, K.tw[1], K.tw_sub + (size_t)2 * (P.N / 2), K.n_inv[1], K.two32[1], (int)K1, 1,   \
-                           P.pbs_l);                                                                                     \
-    }
-        CONVS(10) CONVS(11)
-#undef CONVS
-    }
-    HIP_TRY(hipGetLastError());
+    if (int rc = convert_bootstrap_key(ctx, d_std, n_words, polys)) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (K.group > 1 && !K.gen && !K.large && !K.n8192 && !K.expo) { // (the generic and large-N kernels derive their spectrum positions)
+    if (K.run.form == SI_SPLIT_MB && !K.expo) { // once per context (the generic and large-N kernels derive their spectrum positions)
         if (int rc = probe_spectrum_positions(ctx)) return rc;
     }
     K.have_bsk = true;

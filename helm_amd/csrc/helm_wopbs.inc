@@ -578,15 +578,9 @@ int helm_wop_ctx_create(helm_si_ctx *pbs_side, const helm_wop_params *params, he
         return fail(HELM_ERR_INVALID, "WoP-PBS: circuit-bootstrap levels must be 2 or 3 (built variants), cbs_logB * cbs_l <= 31");
     if (P.pfks_l < 1 || P.pfks_l > 4 || P.pfks_logB < 2 || P.pfks_logB > 30 || P.pfks_logB * P.pfks_l > 63)
         return fail(HELM_ERR_INVALID, "WoP-PBS: bad packing-keyswitch decomposition (pfks_l <= 4, pfks_logB <= 30)");
-    if (pbs_side->keys->n8192)
-        return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context runs the N = 8192 bootstrap kernel (HELM_SI_CREATE_N8192, "
-                                      "helm_si_kernel_class 3); the WoP path is built for the tuned kernels only");
-    if (pbs_side->keys->large)
-        return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context runs the large-N bootstrap kernel (helm_si_kernel_class 2); "
-                                      "the WoP path is built for the tuned kernels only");
-    if (pbs_side->keys->gen)
-        return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context runs the generic bootstrap kernel (helm_si_kernel_class 1); "
-                                      "the WoP path is built for the tuned kernels only");
+    if (pbs_side->keys->run.cls != SI_TUNED)
+        return fail(HELM_ERR_INVALID, std::string("WoP-PBS: the PBS-side context runs the ") + SI_CLASS[pbs_side->keys->run.cls].wop +
+                                          "; the WoP path is built for the tuned kernels only");
     if (pbs_side->order == 0)
         return fail(HELM_ERR_INVALID, "WoP-PBS: the PBS-side context was created with HELM_SI_CREATE_PBS_KS (helm_si_pbs_order 0: "
                                       "wire rows of n + 1 words); the WoP path's bit extraction, circuit bootstrap and result rows "
