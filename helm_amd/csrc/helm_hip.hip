@@ -16,6 +16,7 @@
 #include "ntt_fp64.h"
 #include "shard_rule.h"
 #include "keyswitch.h"
+#include "with_logn.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -2008,6 +2009,83 @@ struct LevelPlan {
 
 } // namespace
 
+// The tuned builds (kernel class 0), listed once for both translation units: the shapes, and per shape the lazy field that
+// may serve it besides the 51-bit FpH (49: FpG at N = 512, chosen from the parameter set; 50: FpI at N = 1024, chosen per
+// loaded key) - ten (field, LOGN, K, L) forms, the only ones a tuned kernel is instantiated for.
+struct TunedShape {
+    int N, k, pbs_l, lazy;
+    bool trio; // a build with three bootstraps per workgroup exists: k_pbs_trio | k_pbs_tri10
+};
+constexpr TunedShape TUNED[] = {{512, 2, 3, 49, true},   {512, 1, 3, 49, false},  {512, 1, 2, 49, false},
+                                {1024, 1, 3, 50, true},  {1024, 1, 2, 50, true}};
+constexpr int N_TUNED = (int)(sizeof(TUNED) / sizeof(TUNED[0]));
+// index of a shape in TUNED, or -1: the shape has no tuned build
+static inline int tuned_shape(const helm_hip_params &P)
+{
+    for (int i = 0; i < N_TUNED; i++)
+        if (P.N == TUNED[i].N && P.k == TUNED[i].k && P.pbs_l == TUNED[i].pbs_l) return i;
+    return -1;
+}
+// field id of the engine context -> field type of the boolean kernels
+template <int ID> struct BoolField;
+template <> struct BoolField<49> { using type = FpG; };
+template <> struct BoolField<50> { using type = FpI; };
+template <> struct BoolField<51> { using type = FpH; };
+template <typename F_, int LOGN_, int K_, int L_> struct TunedForm {
+    using F = F_;
+    static constexpr int LOGN = LOGN_, K = K_, L = L_;
+};
+// f(TunedForm<F, LOGN, K, L>) for row `shape` of TUNED in `field` (the row's lazy field, or 51), `outside` for anything else:
+// a call site instantiates what it names for the ten forms and no other.
+template <int I = 0, class R, class Fn>
+R with_tuned(int shape, int field, R outside, Fn &&f)
+{
+    if constexpr (I < N_TUNED) {
+        constexpr TunedShape S = TUNED[I];
+        constexpr int LOGN = S.N == 512 ? 9 : 10;
+        static_assert(S.N == 1 << LOGN, "tuned builds exist at N = 512 and N = 1024");
+        if (shape == I) {
+            if (field == S.lazy) return f(TunedForm<typename BoolField<S.lazy>::type, LOGN, S.k, S.pbs_l>{});
+            if (field == 51) return f(TunedForm<FpH, LOGN, S.k, S.pbs_l>{});
+            return outside;
+        }
+        return with_tuned<I + 1>(shape, field, outside, f);
+    } else return outside;
+}
+
+// Which bootstrap kernel a context runs and how: decided once, by bool_admit() from (params, flags, environment), and only
+// read afterwards.  The class's setup step fills (d, lds, per_cu) once the device is chosen; helm_hip_load_bootstrap_key
+// moves `field` between 50 and 51 for a tuned N = 1024 context; nothing else writes the record.
+enum BoolClass { BOOL_TUNED = 0, BOOL_GENERIC = 1, BOOL_CRT = 2 }; // the values helm_hip_kernel_class returns
+enum BoolBuild { // the builds of the tuned class, by their HELM_HIP_PBS_VARIANT numbers
+    BUILD_WIDE = 4,     // k_pbs_wide
+    BUILD_LOCKSTEP = 5, // k_pbs
+    BUILD_DUO = 6,      // k_pbs_duo, the two bootstraps of a workgroup in step
+    BUILD_DUO_STAG = 7, // k_pbs_duo staggered by half a step
+    BUILD_TRI10_2 = 8,  // (N = 1024) k_pbs_tri10's waves, two bootstraps per workgroup
+    BUILD_TRIO = 9      // k_pbs_trio (N = 512, k = 2) | k_pbs_tri10 (N = 1024)
+};
+struct BoolForm {
+    BoolClass cls = BOOL_TUNED; // of the shape: 1 no tuned build covers it, 2 beyond the single-prime capacity bound
+    BoolClass run = BOOL_TUNED; // what runs every launch: cls, or k_pbs_generic under HELM_HIP_PBS_VARIANT=10 (FpH, its own
+                                // key layout), or k_pbs_crt under HELM_HIP_CREATE_FORCE_CRT (FpG x FpG2, its own key layout)
+    int shape = -1;             // row of TUNED, when the shape has a tuned build
+    int field = 51;             // 51: FpH, 49: FpG, 50: FpI (both lazy) - all with short eighth roots of unity -, 98: the CRT pair
+    int variant = 0;            // HELM_HIP_PBS_VARIANT: 0 = by launch size, or one BoolBuild for every launch (10: see `run`)
+    // the builds launch_pbs_f's size dispatch gives a remainder of <= 1, <= 2 and <= 3 bootstraps per CU (BUILD_LOCKSTEP: no
+    // build of that size, or switched off):
+    //   [1] N = 512 (HELM_HIP_DUO): 2 k_pbs_duo staggered, 1 in step, 0 none.  N = 1024 (HELM_HIP_DUO1024): 3 k_pbs_tri10's waves,
+    //       two bootstraps per workgroup (round 6: 512 bootstraps of helm_cuda 5.11 -> 4.41 ms, profiles/r06/ab_tri10.jsonl);
+    //       1 / 2 k_pbs_duo's compact layout in step / staggered (round 5: 5.50 - 5.55 / 5.75 ms in the 51-bit field, the
+    //       two-wave build of rounds 1-4 6.04); 0 none
+    //   [2] k_pbs_trio / k_pbs_tri10 where the shape has one (HELM_HIP_TRIO=0: a partial lockstep round, round 3's choice)
+    int rem[3] = {BUILD_WIDE, BUILD_LOCKSTEP, BUILD_LOCKSTEP};
+    // classes 1 and 2 (setup_generic, setup_crt): the launch sizing of the class's kernel
+    int d = 1;      // digit polynomials per batch (gen_batch | tp_batch, tp_fit)
+    size_t lds = 0; // LDS bytes per workgroup (GenLds | TwoPrimeLds<uint32_t>)
+    int per_cu = 1; // resident workgroups per CU at lds
+};
+
 struct helm_hip_wires {
     helm_hip_ctx *owner;
     uint32_t *d;
@@ -2032,27 +2110,9 @@ struct helm_hip_ctx {
     DevBuf<uint32_t> d_ksbody;
     uint32_t *tv_bool = nullptr; // one row: all +1/8
     bool have_bsk = false, have_ksk = false;
-    int field = 51; // 51: FpH, 49: FpG (lazy) - both with short eighth roots of unity -, chosen from the parameter set
+    BoolForm form;           // which kernel runs the launches, and how: bool_admit's answer
     int n_cus = 256;
     int clock_probe = 0;     // HELM_HIP_CLOCK_PROBE: print the in-kernel clock of every k_pbs launch
-    int pbs_variant = 0;     // 0 = by launch size, 4 wide, 5 lockstep, 6 duo (the two bootstraps of a workgroup in step), 7 duo
-                             // staggered, 9 trio (HELM_HIP_PBS_VARIANT; 1, 2, 3, 8 named builds retired in round 6: refused)
-    int duo_build = 2;       // the two-per-CU build the size dispatch uses at N = 512: 1 k_pbs_duo in step, 2 staggered, 0 none (HELM_HIP_DUO)
-    int duo1024 = 3;         // N = 1024: more than one and at most two bootstraps per CU (HELM_HIP_DUO1024): 3 k_pbs_tri10's waves, two
-                             // bootstraps per workgroup (round 6: 512 bootstraps of helm_cuda 5.11 -> 4.41 ms, profiles/r06/ab_tri10.jsonl);
-                             // 1 / 2 k_pbs_duo's compact layout in step / staggered (round 5: 5.50 - 5.55 / 5.75 ms in the 51-bit field, the
-                             // two-wave build of rounds 1-4 6.04); 0: a lockstep round
-    int trio = 1;            // remainders of two to three bootstraps per CU on k_pbs_trio (HELM_HIP_TRIO=0: a partial lockstep round, round 3's choice)
-    bool generic = false;    // the shape has no tuned build: k_pbs_generic serves it (helm_hip_kernel_class)
-    bool gen_path = false;   // k_pbs_generic runs every launch (generic shape, or HELM_HIP_PBS_VARIANT=10): FpH, its own key layout
-    int gen_d = 1;           // k_pbs_generic: digit polynomials per batch (gen_batch)
-    size_t gen_lds = 0;      // k_pbs_generic: LDS bytes per workgroup (GenLds)
-    int gen_per_cu = 1;      // k_pbs_generic: resident workgroups per CU at gen_lds (hipOccupancyMaxActiveBlocksPerMultiprocessor)
-    bool crt_class = false;  // the shape is beyond the single-prime capacity bound: only k_pbs_crt serves it (kernel class 2)
-    bool crt_path = false;   // k_pbs_crt runs every launch (a class-2 shape, or HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout
-    int crt_d = 1;           // k_pbs_crt: digit polynomials per batch (tp_batch, tp_fit)
-    size_t crt_lds = 0;      // k_pbs_crt: LDS bytes per workgroup (TwoPrimeLds<uint32_t>)
-    int crt_per_cu = 1;      // k_pbs_crt: resident workgroups per CU at crt_lds
     double *crt_tw[4] = {nullptr, nullptr, nullptr, nullptr}; // k_pbs_crt: forward tables of FpG, FpG2, then the inverse ones
     double crt_n_inv[2] = {0, 0}, crt_p0inv = 0;              // 1/N in each field, p0^-1 mod p1
     // per-call scratch
@@ -2231,42 +2291,6 @@ struct TimedScope {
     }
 };
 
-template <typename C>
-static hipError_t launch_pbs_v(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                               const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = k_pbs<C>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern),
-                                                               64 * (C::K + 1) * C::NB, C::BYTES);
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs (lockstep) TW=%d NB=%d: LDS %zu B, regs %d, scratch %zu B, max %d workgroups/CU\n",
-                    C::TW, C::NB, (size_t)C::BYTES, fa.numRegs, (size_t)fa.localSizeBytes, nb);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * (C::K + 1) * C::NB), C::BYTES,
-                       ctx->stream, jobs, wires, raw, tvs, ctx->bsk, ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n,
-                       ctx->P.pbs_logB, ctx->clock_probe | (count >= (int64_t)C::NB * ctx->n_cus ? 2 : 0), (int)count);
-    hipError_t e = hipGetLastError();
-    print_stamps(ctx, C::K + 1, "k_pbs: work | bar1 | sum | bar2 | inverse | publish");
-    if (e == hipSuccess && (ctx->clock_probe & 1)) {
-        unsigned long long v[4];
-        (void)hipStreamSynchronize(ctx->stream);
-        if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_clock_probe), sizeof(v)) == hipSuccess && v[3] > v[1])
-            fprintf(stderr, "[helm_hip] k_pbs x%lld: in-kernel clock %.3f GHz (%.3f ms of blind rotation)\n",
-                    (long long)count, (double)(v[2] - v[0]) / (double)(v[3] - v[1]) * 0.1, (double)(v[3] - v[1]) * 1e-5);
-    }
-    return e;
-}
-
 static void print_stamps(helm_hip_ctx *ctx, int waves, const char *what)
 {
 #ifdef HELM_WIDE_STAMPS
@@ -2287,158 +2311,113 @@ static void print_stamps(helm_hip_ctx *ctx, int waves, const char *what)
 #endif
 }
 
+// One launch of a tuned kernel, C its configuration (one type per kernel instantiation): the dynamic-LDS attribute once per
+// kernel and device with the HELM_HIP_VERBOSE line, the launch with C::BYTES of LDS on the context's stream, the stamps.
+template <typename C, typename Kern, typename... Args>
+static hipError_t launch_tuned(helm_hip_ctx *ctx, Kern kern, const char *name, dim3 grid, dim3 block, int stamp_waves,
+                               const char *legend, Args... args)
+{
+    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
+    if (!attr_done[ctx->device & 63]) {
+        const void *fn = reinterpret_cast<const void *>(kern);
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
+        if (e != hipSuccess) return e;
+        attr_done[ctx->device & 63] = true;
+        if (getenv("HELM_HIP_VERBOSE")) {
+            int nb = -1;
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block.x, C::BYTES);
+            hipFuncAttributes fa{};
+            (void)hipFuncGetAttributes(&fa, fn);
+            fprintf(stderr, "[helm_hip] %s: %u waves, LDS %zu B, regs %d, scratch %zu B, max %d workgroups/CU\n", name, block.x / 64,
+                    (size_t)C::BYTES, fa.numRegs, (size_t)fa.localSizeBytes, nb);
+        }
+    }
+    hipLaunchKernelGGL(kern, grid, block, C::BYTES, ctx->stream, args...);
+    const hipError_t e = hipGetLastError();
+    print_stamps(ctx, stamp_waves, legend);
+    return e;
+}
+
+template <typename C>
+static hipError_t launch_pbs_v(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                               const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+{
+    hipError_t e = launch_tuned<C>(ctx, k_pbs<C>, "k_pbs (lockstep)", dim3((unsigned)((count + C::NB - 1) / C::NB)),
+                                   dim3(64 * (C::K + 1) * C::NB), C::K + 1, "k_pbs: work | bar1 | sum | bar2 | inverse | publish", jobs,
+                                   wires, raw, tvs, ctx->bsk, ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n, ctx->P.pbs_logB,
+                                   ctx->clock_probe | (count >= (int64_t)C::NB * ctx->n_cus ? 2 : 0), (int)count);
+    if (e == hipSuccess && (ctx->clock_probe & 1)) {
+        unsigned long long v[4];
+        (void)hipStreamSynchronize(ctx->stream);
+        if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_clock_probe), sizeof(v)) == hipSuccess && v[3] > v[1])
+            fprintf(stderr, "[helm_hip] k_pbs x%lld: in-kernel clock %.3f GHz (%.3f ms of blind rotation)\n",
+                    (long long)count, (double)(v[2] - v[0]) / (double)(v[3] - v[1]) * 0.1, (double)(v[3] - v[1]) * 1e-5);
+    }
+    return e;
+}
+
 template <typename C>
 static hipError_t launch_pbs_wide(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                                   const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = k_pbs_wide<C>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs_wide: %d waves, LDS %zu B, regs %d, scratch %zu B\n", C::NW, (size_t)C::BYTES,
-                    fa.numRegs, (size_t)fa.localSizeBytes);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires, raw, tvs, ctx->bsk,
-                       ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB);
-    print_stamps(ctx, C::NW, "wide: prep | fwd | products | bar1 | inverse | bar2");
-    return hipGetLastError();
+    return launch_tuned<C>(ctx, k_pbs_wide<C>, "k_pbs_wide", dim3((unsigned)count), dim3(64 * C::NW), C::NW,
+                           "wide: prep | fwd | products | bar1 | inverse | bar2", jobs, wires, raw, tvs, ctx->bsk, ctx->tw_fwd,
+                           out_big, ctx->P.n, ctx->P.pbs_logB);
 }
 
 template <typename C>
 static hipError_t launch_pbs_duo(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                                  const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = k_pbs_duo<C>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), 64 * C::NW, C::BYTES);
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs_duo%s: %d waves, LDS %zu B, regs %d, scratch %zu B, max %d workgroups/CU\n",
-                    C::STAG ? " (staggered)" : "", C::NW, (size_t)C::BYTES, fa.numRegs, (size_t)fa.localSizeBytes, nb);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires,
-                       raw, tvs, ctx->bsk, ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
-    print_stamps(ctx, C::NW, "duo: forward | barriers | inverse | - | - | -");
-    return hipGetLastError();
+    return launch_tuned<C>(ctx, k_pbs_duo<C>, C::STAG ? "k_pbs_duo (staggered)" : "k_pbs_duo",
+                           dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::NW,
+                           "duo: forward | barriers | inverse | - | - | -", jobs, wires, raw, tvs, ctx->bsk, ctx->tw_fwd, out_big,
+                           ctx->P.n, ctx->P.pbs_logB, (int)count);
 }
 
 template <typename C>
 static hipError_t launch_pbs_trio(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                                   const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = k_pbs_trio<C>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs_trio: %d waves, LDS %zu B, regs %d, scratch %zu B\n", C::NW, (size_t)C::BYTES,
-                    fa.numRegs, (size_t)fa.localSizeBytes);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires,
-                       raw, tvs, ctx->bsk, ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
-    print_stamps(ctx, C::NW, "trio: rotate+publish | bar A | forward work | bar B (helper: B+C) | sums + bar C | inverse + lift");
-    return hipGetLastError();
+    return launch_tuned<C>(ctx, k_pbs_trio<C>, "k_pbs_trio", dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::NW,
+                           "trio: rotate+publish | bar A | forward work | bar B (helper: B+C) | sums + bar C | inverse + lift", jobs,
+                           wires, raw, tvs, ctx->bsk, ctx->tw_fwd, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
 }
 
 template <typename C>
 static hipError_t launch_pbs_tri10(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                                    const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
-    static std::atomic<bool> attr_done[64]; // (rank threads of one process launch concurrently)
-    auto kern = k_pbs_tri10<C>;
-    if (!attr_done[ctx->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs_tri10: %d waves, LDS %zu B, regs %d, scratch %zu B\n", C::NW, (size_t)C::BYTES,
-                    fa.numRegs, (size_t)fa.localSizeBytes);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::BYTES, ctx->stream, jobs, wires,
-                       raw, tvs, ctx->bsk, ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
-    print_stamps(ctx, C::NW, "tri10: forward work | bar 1 | sum + inverse half | bar 2 | join + lift | bar 3");
-    return hipGetLastError();
+    return launch_tuned<C>(ctx, k_pbs_tri10<C>, "k_pbs_tri10", dim3((unsigned)((count + C::NB - 1) / C::NB)), dim3(64 * C::NW), C::NW,
+                           "tri10: forward work | bar 1 | sum + inverse half | bar 2 | join + lift | bar 3", jobs, wires, raw, tvs,
+                           ctx->bsk, ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n, ctx->P.pbs_logB, (int)count);
 }
 
 // Two translation units from this one source (Makefile): the whole file is compiled under the compiler's max-ILP scheduling
 // strategy (-mllvm -amdgpu-sched-strategy=max-ilp: +1.9 % on the lockstep k_pbs, same box, alternating, identical
 // ciphertexts), except k_pbs_wide, which that strategy slows down by 0.9 % and which is therefore compiled a second time
 // with -DHELM_HIP_TU=1 under the default strategy - that unit holds this launcher and nothing else of the host side.
-// build: 0 = k_pbs_wide, 1 = k_pbs_duo with the two bootstraps of a workgroup in step, 2 = k_pbs_duo staggered
-__attribute__((visibility("hidden"))) hipError_t helm_hip_tu1_launch_wide(helm_hip_ctx *ctx, int build, int field, int logn, int k,
-                                                                        int l, const PbsJob *jobs, int64_t count,
-                                                                        const uint32_t *wires, const uint32_t *raw,
+// build: BUILD_WIDE, BUILD_DUO or BUILD_DUO_STAG (at N = 1024 k_pbs_duo has its compact LDS layout, DuoCfg::COMPACT), of the
+// context's tuned form
+__attribute__((visibility("hidden"))) hipError_t helm_hip_tu1_launch_wide(helm_hip_ctx *ctx, int build, const PbsJob *jobs,
+                                                                        int64_t count, const uint32_t *wires, const uint32_t *raw,
                                                                         const uint32_t *tvs, uint32_t *out_big);
-// field id of the engine context -> field type of the boolean kernels (49: the lazy FpG)
-template <int ID> struct BoolField;
-template <> struct BoolField<49> { using type = FpG; };
-template <> struct BoolField<50> { using type = FpI; }; // N = 1024, lazy, chosen per loaded key (helm_hip_load_bootstrap_key)
-template <> struct BoolField<51> { using type = FpH; };
-template <typename F> constexpr int bool_field_id() { return std::is_same<F, FpG>::value ? 49 : std::is_same<F, FpI>::value ? 50 : 51; }
-#if HELM_HIP_TU == 1
-hipError_t helm_hip_tu1_launch_wide(helm_hip_ctx *ctx, int build, int field, int logn, int k, int l, const PbsJob *jobs, int64_t count,
-                                    const uint32_t *wires, const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
+#if !HELM_HIP_SPLIT_TU // (that unit, and a build of the file as a single unit)
+hipError_t helm_hip_tu1_launch_wide(helm_hip_ctx *ctx, int build, const PbsJob *jobs, int64_t count, const uint32_t *wires,
+                                    const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
-#define WIDE_CASE(FB, LN, KK, LL)                                                                                        \
-    if (field == FB && logn == LN && k == KK && l == LL) {                                                               \
-        if (build == 1) return launch_pbs_duo<DuoCfg<BoolField<FB>::type, LN, KK, LL, false>>(ctx, jobs, count, wires, raw, tvs, out_big); \
-        if (build == 2) return launch_pbs_duo<DuoCfg<BoolField<FB>::type, LN, KK, LL, true>>(ctx, jobs, count, wires, raw, tvs, out_big); \
-        return launch_pbs_wide<WideCfg<BoolField<FB>::type, LN, KK, LL>>(ctx, jobs, count, wires, raw, tvs, out_big);                  \
-    }
-    WIDE_CASE(49, 9, 2, 3) WIDE_CASE(49, 9, 1, 3) WIDE_CASE(49, 9, 1, 2)
-    WIDE_CASE(51, 9, 2, 3) WIDE_CASE(51, 9, 1, 3) WIDE_CASE(51, 9, 1, 2)
-#undef WIDE_CASE
-    // N = 1024: the wide build, and (round 5) k_pbs_duo in its compact LDS layout (DuoCfg::COMPACT: 153.6 KB for two bootstraps)
-#define WIDE1024_CASE(FB, LL)                                                                                               \
-    if (field == FB && logn == 10 && k == 1 && l == LL) {                                                                    \
-        if (build == 1) return launch_pbs_duo<DuoCfg<BoolField<FB>::type, 10, 1, LL, false>>(ctx, jobs, count, wires, raw, tvs, out_big); \
-        if (build == 2) return launch_pbs_duo<DuoCfg<BoolField<FB>::type, 10, 1, LL, true>>(ctx, jobs, count, wires, raw, tvs, out_big);  \
-        if (build == 0) return launch_pbs_wide<WideCfg<BoolField<FB>::type, 10, 1, LL>>(ctx, jobs, count, wires, raw, tvs, out_big);      \
-    }
-    WIDE1024_CASE(51, 3) WIDE1024_CASE(51, 2) WIDE1024_CASE(50, 3) WIDE1024_CASE(50, 2)
-#undef WIDE1024_CASE
-    return hipErrorInvalidValue;
+    return with_tuned(ctx->form.shape, ctx->form.field, hipErrorInvalidValue, [&](auto t) {
+        using T = decltype(t);
+        if (build == BUILD_DUO)
+            return launch_pbs_duo<DuoCfg<typename T::F, T::LOGN, T::K, T::L, false>>(ctx, jobs, count, wires, raw, tvs, out_big);
+        if (build == BUILD_DUO_STAG)
+            return launch_pbs_duo<DuoCfg<typename T::F, T::LOGN, T::K, T::L, true>>(ctx, jobs, count, wires, raw, tvs, out_big);
+        if (build != BUILD_WIDE) return hipErrorInvalidValue;
+        return launch_pbs_wide<WideCfg<typename T::F, T::LOGN, T::K, T::L>>(ctx, jobs, count, wires, raw, tvs, out_big);
+    });
 }
 #endif
 #if HELM_HIP_TU == 0 // ==== everything below: the main unit only ===============================================
-template <typename F, int LOGN, int K, int L>
-static hipError_t wide_launch(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires, const uint32_t *raw,
-                              const uint32_t *tvs, uint32_t *out_big, int build = 0)
-{
-#if HELM_HIP_SPLIT_TU
-    return helm_hip_tu1_launch_wide(ctx, build, bool_field_id<F>(), LOGN, K, L, jobs, count, wires, raw, tvs, out_big);
-#else
-    if (build == 1) return launch_pbs_duo<DuoCfg<F, LOGN, K, L, false>>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (build == 2) return launch_pbs_duo<DuoCfg<F, LOGN, K, L, true>>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (build) return hipErrorInvalidValue;
-    return launch_pbs_wide<WideCfg<F, LOGN, K, L>>(ctx, jobs, count, wires, raw, tvs, out_big);
-#endif
-}
 
 // Build choice by launch size (measured: profiles/r04/microbench.jsonl, profiles/r05/microbench*.jsonl; relative costs in
 // helm_hip_launch_costs).  A launch runs its full rounds of 4 bootstraps per CU on the lockstep k_pbs and the remainder by size:
@@ -2460,14 +2439,14 @@ static hipError_t launch_pbs_f(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t co
     // three forward transforms of a step: +1.9 % (profiles/r04/lockstep_twiddle_registers.txt).  N = 1024 (two waves per
     // bootstrap on one SIMD, 248 registers) reads the table.
     using Lock = PbsCfg<F, LOGN, K, L, LOGN == 9 ? TW_LANE_FREG : TW_LANE>;
-    constexpr bool HAS_TRIO = (LOGN == 9 && K == 2) || (LOGN == 10 && K == 1); // k_pbs_trio | k_pbs_tri10
+    const BoolForm &form = ctx->form;
     const int64_t cus = ctx->n_cus;
-    int v = ctx->pbs_variant;
+    int v = form.variant;
     if (v == 0) {
         const int64_t round = 4 * cus;
         int64_t full = count / round * round;
         // a remainder of more than three per CU (two where there is no three-per-CU build) is another lockstep round
-        const bool trio = HAS_TRIO && ctx->trio;
+        const bool trio = form.rem[2] == BUILD_TRIO;
         if (count - full > (trio ? 3 : 2) * cus) full = count;
         if (full) {
             hipError_t e;
@@ -2482,42 +2461,18 @@ static hipError_t launch_pbs_f(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t co
             out_big += (size_t)full * ((size_t)K * (1 << LOGN) + 1);
             count -= full;
         }
-        const int duo = LOGN == 9 ? ctx->duo_build : ctx->duo1024; // 0: no two-per-CU build (A/B): a lockstep round instead
-        v = count <= cus ? 4 : count > 2 * cus ? 9 : duo ? 5 + duo : 5;
+        v = form.rem[count <= cus ? 0 : count <= 2 * cus ? 1 : 2]; // (BUILD_LOCKSTEP: no build of that size - a lockstep round instead)
     }
-    if (v == 4) return wide_launch<F, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (v == 6 || v == 7) return wide_launch<F, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big, v - 5);
-    if (v == 9) {
+    if (v == BUILD_WIDE || v == BUILD_DUO || v == BUILD_DUO_STAG) // (the other translation unit's builds, of this same form)
+        return helm_hip_tu1_launch_wide(ctx, v, jobs, count, wires, raw, tvs, out_big);
+    if (v == BUILD_TRIO) {
         if constexpr (LOGN == 9 && K == 2) return launch_pbs_trio<TrioCfg<F, LOGN, K, L>>(ctx, jobs, count, wires, raw, tvs, out_big);
         else if constexpr (LOGN == 10 && K == 1) return launch_pbs_tri10<Tri10Cfg<F, L>>(ctx, jobs, count, wires, raw, tvs, out_big);
     }
-    if (v == 8) { // (N = 1024: HELM_HIP_DUO1024=3) k_pbs_tri10's waves, two bootstraps per workgroup
+    if (v == BUILD_TRI10_2) { // (N = 1024: HELM_HIP_DUO1024=3) k_pbs_tri10's waves, two bootstraps per workgroup
         if constexpr (LOGN == 10 && K == 1) return launch_pbs_tri10<Tri10Cfg<F, L, 2>>(ctx, jobs, count, wires, raw, tvs, out_big);
     }
     return launch_pbs_v<Lock>(ctx, jobs, count, wires, raw, tvs, out_big);
-}
-
-template <int LOGN, int K, int L>
-static hipError_t launch_pbs_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                               const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    if constexpr (LOGN == 9) {
-        if (ctx->field == 49) return launch_pbs_f<FpG, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big);
-    } else {
-        if (ctx->field == 50) return launch_pbs_f<FpI, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big);
-    }
-    return launch_pbs_f<FpH, LOGN, K, L>(ctx, jobs, count, wires, raw, tvs, out_big);
-}
-
-// the shapes the tuned builds cover (kernel class 0)
-static bool pbs_tuned(const helm_hip_params &P)
-{
-    if (P.N == 512 && P.k == 2 && P.pbs_l == 3) return true;
-    if (P.N == 512 && P.k == 1 && P.pbs_l == 3) return true;
-    if (P.N == 512 && P.k == 1 && P.pbs_l == 2) return true;
-    if (P.N == 1024 && P.k == 1 && P.pbs_l == 3) return true;
-    if (P.N == 1024 && P.k == 1 && P.pbs_l == 2) return true;
-    return false;
 }
 
 // the shapes k_pbs_generic takes (a superset of the tuned ones): its LDS budget is (k+1) N <= 8192 (helm_pbs_generic.inc)
@@ -2527,38 +2482,6 @@ static bool pbs_admitted(const helm_hip_params &P)
            P.pbs_l >= 1;
 }
 
-template <int LOGN>
-static hipError_t launch_pbs_generic_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                                       const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    // (the dynamic LDS attribute is set by helm_hip_ctx_create, at the largest layout of this N)
-    static std::atomic<bool> told[64];
-    auto kern = k_pbs_generic<LOGN>;
-    if (!told[ctx->device & 63]) {
-        told[ctx->device & 63] = true;
-        if (getenv("HELM_HIP_VERBOSE")) {
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "[helm_hip] k_pbs_generic N=%d D=%d: LDS %zu B, regs %d, scratch %zu B, max %d workgroups/CU\n", 1 << LOGN, ctx->gen_d,
-                    ctx->gen_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->gen_per_cu);
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(GEN_THREADS), ctx->gen_lds, ctx->stream, jobs, wires, raw, tvs, ctx->bsk,
-                       ctx->tw_fwd, ctx->tw_inv, out_big, ctx->P.n, ctx->P.k, ctx->P.pbs_l, ctx->P.pbs_logB, ctx->gen_d);
-    return hipGetLastError();
-}
-
-static hipError_t launch_pbs_generic(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                                     const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    switch (ctx->P.N) {
-    case 256: return launch_pbs_generic_t<8>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 512: return launch_pbs_generic_t<9>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 1024: return launch_pbs_generic_t<10>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 2048: return launch_pbs_generic_t<11>(ctx, jobs, count, wires, raw, tvs, out_big);
-    default: return hipErrorInvalidValue;
-    }
-}
 
 // the CRT domain, whole (helm_hip_ctx_create_ex under HELM_HIP_CREATE_ALLOW_CRT / FORCE_CRT, as include/helm_hip.h states
 // it): N stops at 2048 because FpG2 has 2-adicity 2^12; (k+1) N <= 4096 is the kernel's LDS budget (helm_pbs_crt.inc);
@@ -2579,49 +2502,45 @@ static_assert(((unsigned __int128)4096 * 31 << 61) < ((unsigned __int128)1 << 78
                   ((unsigned __int128)1 << 78) < (unsigned __int128)FpG::P_U64 * FpG2::P_U64 / 2,
               "the CRT domain's largest exact product is below p0 p1 / 2");
 
-[[maybe_unused]] static const void *crt_kernel(int logN)
+// k_pbs_generic / k_pbs_crt of a logN, as the occupancy and attribute calls take them (setup_generic, setup_crt)
+static const void *class_kernel(BoolClass run, int logN)
 {
-    return logN == 8    ? reinterpret_cast<const void *>(k_pbs_crt<8>)
-           : logN == 9  ? reinterpret_cast<const void *>(k_pbs_crt<9>)
-           : logN == 10 ? reinterpret_cast<const void *>(k_pbs_crt<10>)
-                        : reinterpret_cast<const void *>(k_pbs_crt<11>);
+    return with_logn<8, 11>(logN, (const void *)nullptr, [&](auto ln) {
+        constexpr int LOGN = decltype(ln)::value;
+        return run == BOOL_CRT ? reinterpret_cast<const void *>(k_pbs_crt<LOGN>) : reinterpret_cast<const void *>(k_pbs_generic<LOGN>);
+    });
 }
 
-template <int LOGN>
-static hipError_t launch_pbs_crt_t(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                                   const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    // (the dynamic LDS attribute is set by setup_crt, at the largest layout of this N)
-    hipLaunchKernelGGL(k_pbs_crt<LOGN>, dim3((unsigned)count), dim3(TP_THREADS), ctx->crt_lds, ctx->stream, jobs, wires, raw, tvs,
-                       ctx->bsk, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], out_big, ctx->P.n, ctx->P.k,
-                       ctx->P.pbs_l, ctx->P.pbs_logB, ctx->crt_d, ctx->crt_p0inv);
-    return hipGetLastError();
-}
-
-static hipError_t launch_pbs_crt(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
-                                 const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
-{
-    switch (ctx->P.N) {
-    case 256: return launch_pbs_crt_t<8>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 512: return launch_pbs_crt_t<9>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 1024: return launch_pbs_crt_t<10>(ctx, jobs, count, wires, raw, tvs, out_big);
-    case 2048: return launch_pbs_crt_t<11>(ctx, jobs, count, wires, raw, tvs, out_big);
-    default: return hipErrorInvalidValue;
-    }
-}
-
+// Every bootstrap launch of the engine: the context's record says which kernel runs it (one workgroup per bootstrap at the
+// setup step's (d, lds) for classes 1 and 2, whose dynamic-LDS attribute that step has set; launch_pbs_f's size dispatch for
+// a tuned form).
 static hipError_t launch_pbs(helm_hip_ctx *ctx, const PbsJob *jobs, int64_t count, const uint32_t *wires,
                              const uint32_t *raw, const uint32_t *tvs, uint32_t *out_big)
 {
     const helm_hip_params &P = ctx->P;
-    if (ctx->crt_path) return launch_pbs_crt(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (ctx->gen_path) return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (P.N == 512 && P.k == 2 && P.pbs_l == 3) return launch_pbs_t<9, 2, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (P.N == 512 && P.k == 1 && P.pbs_l == 3) return launch_pbs_t<9, 1, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (P.N == 512 && P.k == 1 && P.pbs_l == 2) return launch_pbs_t<9, 1, 2>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (P.N == 1024 && P.k == 1 && P.pbs_l == 3) return launch_pbs_t<10, 1, 3>(ctx, jobs, count, wires, raw, tvs, out_big);
-    if (P.N == 1024 && P.k == 1 && P.pbs_l == 2) return launch_pbs_t<10, 1, 2>(ctx, jobs, count, wires, raw, tvs, out_big);
-    return launch_pbs_generic(ctx, jobs, count, wires, raw, tvs, out_big);
+    const BoolForm &form = ctx->form;
+    switch (form.run) {
+    case BOOL_CRT:
+        return with_logn<8, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+            hipLaunchKernelGGL(k_pbs_crt<decltype(ln)::value>, dim3((unsigned)count), dim3(TP_THREADS), form.lds, ctx->stream, jobs,
+                               wires, raw, tvs, ctx->bsk, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], out_big, P.n,
+                               P.k, P.pbs_l, P.pbs_logB, form.d, ctx->crt_p0inv);
+            return hipGetLastError();
+        });
+    case BOOL_GENERIC:
+        return with_logn<8, 11>(ctx->logN, hipErrorInvalidValue, [&](auto ln) {
+            hipLaunchKernelGGL(k_pbs_generic<decltype(ln)::value>, dim3((unsigned)count), dim3(GEN_THREADS), form.lds, ctx->stream,
+                               jobs, wires, raw, tvs, ctx->bsk, ctx->tw_fwd, ctx->tw_inv, out_big, P.n, P.k, P.pbs_l, P.pbs_logB,
+                               form.d);
+            return hipGetLastError();
+        });
+    case BOOL_TUNED:
+        return with_tuned(form.shape, form.field, hipErrorInvalidValue, [&](auto t) {
+            using T = decltype(t);
+            return launch_pbs_f<typename T::F, T::LOGN, T::K, T::L>(ctx, jobs, count, wires, raw, tvs, out_big);
+        });
+    }
+    return hipErrorInvalidValue;
 }
 
 // What the boolean engine's keyswitch launches have of their own (helm_ks::launch): the matrix-core form whenever the key
@@ -2764,33 +2683,14 @@ static int run_level_device(helm_hip_ctx *ctx, const PbsJob *d_pbs, int64_t n_pb
     return 0;
 }
 
-// ------------------------------------------------------------------------------------
-// C ABI
-// ------------------------------------------------------------------------------------
-extern "C" {
-
-const char *helm_hip_last_error(void) { return g_err.c_str(); }
-
-int helm_hip_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-// The tables of the field the context computes in (ctx->field: 49 FpG, 50 FpI, 51 FpH): bit-reversed powers of psi and
-// psi^-1, 1/N.  Called by helm_hip_ctx_create and again by helm_hip_load_bootstrap_key when the key moves an N = 1024 set
-// into the lazy field.
-static int setup_field_tables(helm_hip_ctx *ctx)
+// The tables of the single-prime field F the context computes in: bit-reversed powers of psi and psi^-1, 1/N.
+template <typename F> static int setup_field_tables_of(helm_hip_ctx *ctx)
 {
     // twiddle tables: bit-reversed powers of psi (primitive 2N-th root) and of psi^-1
     const int N = ctx->P.N, logN = ctx->logN;
-    const uint64_t pm = ctx->field == 49 ? FpG::P_U64 : ctx->field == 50 ? FpI::P_U64 : FpH::P_U64;
-    const uint64_t gen = ctx->field == 49 ? FpG::GEN : ctx->field == 50 ? FpI::GEN : FpH::GEN;
-    uint64_t psi = powmod_u64(gen, (pm - 1) / (2 * (uint64_t)N), pm);
-    const double b1 = ctx->field == 49 ? FpG::B1 : ctx->field == 50 ? FpI::B1 : FpH::B1,
-                 b2 = ctx->field == 49 ? FpG::B2 : ctx->field == 50 ? FpI::B2 : FpH::B2,
-                 b3 = ctx->field == 49 ? FpG::B3 : ctx->field == 50 ? FpI::B3 : FpH::B3;
+    const uint64_t pm = F::P_U64;
+    uint64_t psi = powmod_u64(F::GEN, (pm - 1) / (2 * (uint64_t)N), pm);
+    const double b1 = F::B1, b2 = F::B2, b3 = F::B3;
     {
         // the kernels' first two forward stages assume psi^(N/4) = b (then psi^(N/2) = b^2, psi^(3N/4) = b^3): psi^(N/4) is
         // one of the four primitive eighth roots b, b^3, -b, -b^3 - an odd power of psi puts it on b
@@ -2811,6 +2711,32 @@ static int setup_field_tables(helm_hip_ctx *ctx)
     HIP_TRY(hipMemcpy(ctx->tw_fwd, tf.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ctx->tw_inv, ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// C ABI
+// ------------------------------------------------------------------------------------
+extern "C" {
+
+const char *helm_hip_last_error(void) { return g_err.c_str(); }
+
+int helm_hip_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+// The tables of form.field (49 FpG, 50 FpI, 51 FpH: setup_field_tables_of).  Called by helm_hip_ctx_create and again by helm_hip_load_bootstrap_key when
+// the key moves an N = 1024 set into or out of the lazy field.
+static int setup_field_tables(helm_hip_ctx *ctx)
+{
+    switch (ctx->form.field) {
+    case 49: return setup_field_tables_of<FpG>(ctx);
+    case 50: return setup_field_tables_of<FpI>(ctx);
+    case 51: return setup_field_tables_of<FpH>(ctx);
+    default: return fail(HELM_ERR_STATE, "internal: no single-prime tables for field " + std::to_string(ctx->form.field));
+    }
 }
 
 // A context whose launches run k_pbs_crt: the four twiddle tables of the pair FpG / FpG2 (any primitive 2N-th root serves:
@@ -2841,21 +2767,70 @@ static int setup_crt(helm_hip_ctx *ctx)
         HIP_TRY(hipMemcpy(ctx->crt_tw[2 + f], ti.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     }
     ctx->crt_p0inv = centred(powmod_u64(pm[0] % pm[1], pm[1] - 2, pm[1]), pm[1]);
-    const void *kern = crt_kernel(logN);
+    const void *kern = class_kernel(BOOL_CRT, logN);
     TwoPrimeFit fit;
     HIP_TRY(tp_fit<uint32_t>(kern, N, P.k, P.pbs_l, P.n, fit));
     if (fit.per_cu < 1) return fail(HELM_ERR_STATE, "k_pbs_crt: no workgroup of " + std::to_string(fit.lds) + " B LDS fits a CU");
-    ctx->crt_d = fit.d;
-    ctx->crt_lds = fit.lds;
-    ctx->crt_per_cu = fit.per_cu;
-    if (getenv("HELM_HIP_VERBOSE")) {
-        hipFuncAttributes fa{};
-        (void)hipFuncGetAttributes(&fa, kern);
-        fprintf(stderr, "[helm_hip] k_pbs_crt N=%d k=%d l=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n", N, P.k, P.pbs_l,
-                ctx->crt_d, ctx->crt_lds, fa.numRegs, (size_t)fa.localSizeBytes, ctx->crt_per_cu);
-    }
+    ctx->form.d = fit.d;
+    ctx->form.lds = fit.lds;
+    ctx->form.per_cu = fit.per_cu;
     return 0;
 #endif
+}
+
+// A context whose launches run k_pbs_generic (a shape no tuned build covers, or HELM_HIP_PBS_VARIANT=10): one workgroup of
+// GEN_THREADS per bootstrap; the kernel's LDS attribute, its occupancy - the launch quantum follows it - and the digit batch D.
+static int setup_generic(helm_hip_ctx *ctx)
+{
+    const helm_hip_params &P = ctx->P;
+    const int N = P.N;
+    const void *kern = class_kernel(BOOL_GENERIC, ctx->logN);
+    // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a
+    // context created later with a smaller one cannot lower it under an earlier context's launches
+    const int K1max = 8192 / N;
+    const size_t lds_max = GenLds(N, K1max, gen_batch(N, K1max - 1, 31), 1024).bytes;
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    // digit polynomials per batch: the most (<= gen_batch) that cost no resident workgroup against one per batch - a
+    // launch of more bootstraps than fit at once runs a partial second round (boolean_default's shape: D = 4 leaves
+    // 3 workgroups per CU, 2 leave 4, 1 leaves 5 - 51.9 against 44.7 ms for 1,024 bootstraps)
+    auto occupancy = [&](int d, int &nb) -> int {
+        nb = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, GEN_THREADS, GenLds(N, P.k + 1, d, P.n).bytes));
+        return 0;
+    };
+    int nb1 = 0;
+    if (int rc = occupancy(1, nb1)) return rc;
+    if (nb1 < 1) return fail(HELM_ERR_STATE, "k_pbs_generic: no workgroup of " + std::to_string(GenLds(N, P.k + 1, 1, P.n).bytes) +
+                                                 " B LDS fits a CU");
+    ctx->form.d = 1;
+    for (int d = gen_batch(N, P.k, P.pbs_l); d > 1; d--) {
+        int nb = 0;
+        if (int rc = occupancy(d, nb)) return rc;
+        if (nb == nb1) {
+            ctx->form.d = d;
+            break;
+        }
+    }
+    ctx->form.lds = GenLds(N, P.k + 1, ctx->form.d, P.n).bytes;
+    ctx->form.per_cu = nb1;
+    return 0;
+}
+
+// The setup step of the class that runs the launches, once the device is chosen: tables, and for classes 1 and 2 the
+// occupancy-dependent (d, lds, per_cu) of the record with the HELM_HIP_VERBOSE line.
+static int setup_class(helm_hip_ctx *ctx)
+{
+    const BoolForm &form = ctx->form;
+    if (form.run == BOOL_TUNED) return setup_field_tables(ctx);
+    if (int rc = form.run == BOOL_CRT ? setup_crt(ctx) : setup_generic(ctx)) return rc;
+    if (getenv("HELM_HIP_VERBOSE")) {
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, class_kernel(form.run, ctx->logN));
+        fprintf(stderr, "[helm_hip] %s N=%d k=%d l=%d D=%d: LDS %zu B, regs %d, scratch %zu B, %d workgroups/CU\n",
+                form.run == BOOL_CRT ? "k_pbs_crt" : "k_pbs_generic", ctx->P.N, ctx->P.k, ctx->P.pbs_l, form.d, form.lds, fa.numRegs,
+                (size_t)fa.localSizeBytes, form.per_cu);
+    }
+    return form.run == BOOL_GENERIC ? setup_field_tables(ctx) : 0;
 }
 
 int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_ctx **out)
@@ -2863,10 +2838,10 @@ int helm_hip_ctx_create(int device_id, const helm_hip_params *params, helm_hip_c
     return helm_hip_ctx_create_ex(device_id, params, 0, out);
 }
 
-int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_t flags, helm_hip_ctx **out)
+// What helm_hip_ctx_create_ex decides before it touches a device: the record of (params, flags) and of the environment's
+// switches, or the refusal - parameters and flags first, then HELM_HIP_PBS_VARIANT.
+static int bool_admit(const helm_hip_params &P, uint32_t flags, BoolForm *out)
 {
-    if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
-    *out = nullptr;
     // HELM_HIP_CREATE_KS_PBS admits pbs_order = 1 and changes nothing else: the CRT flags are judged on the remaining bits
     const bool ks_pbs = (flags & HELM_HIP_CREATE_KS_PBS) != 0;
     const uint32_t crt_flags = flags & ~(uint32_t)HELM_HIP_CREATE_KS_PBS;
@@ -2881,7 +2856,6 @@ int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_
     static const char *const crt_domain = "the CRT domain (HELM_HIP_CREATE_ALLOW_CRT / HELM_HIP_CREATE_FORCE_CRT) is N in {256, 512, 1024, "
                                           "2048}, k >= 1 with (k+1) N <= 4096, pbs_l >= 1 with pbs_logB pbs_l <= 31, n in [1,1024], "
                                           "pbs_order 0, grouping_factor 1";
-    const helm_hip_params &P = *params;
     if (P.torus_bits != 32) return fail(HELM_ERR_INVALID, "only torus_bits = 32 is implemented");
     if (P.pbs_order != 0 && !ks_pbs) return fail(HELM_ERR_INVALID, "only pbs_order = 0 (bootstrap then keyswitch)");
     if (P.pbs_order != 0 && P.pbs_order != 1)
@@ -2908,6 +2882,58 @@ int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_
                                                       "two-prime kernel's LDS budget: ") + crt_domain);
         crt_class = true; // (no capacity check of its own: see the static_assert at crt_admitted)
     }
+    BoolForm form;
+    form.shape = tuned_shape(P);
+    form.cls = crt_class ? BOOL_CRT : form.shape < 0 ? BOOL_GENERIC : BOOL_TUNED;
+    if (const char *v = getenv("HELM_HIP_PBS_VARIANT")) {
+        const int pv = form.variant = atoi(v);
+        if (!(pv == 0 || pv == 4 || pv == 5 || pv == 6 || pv == 7 || pv == 9 || pv == 10 || (pv == 8 && P.N == 1024)))
+            return fail(HELM_ERR_INVALID, std::string("HELM_HIP_PBS_VARIANT=") + v + ": builds are 4 wide, 5 lockstep, 6 / 7 duo in step / "
+                                          "staggered, 9 trio, 10 generic (1 latency, 2 balanced, 3 throughput, 8 sym were retired in round 6)");
+    }
+    // the CRT class (a shape beyond the single-prime bound under HELM_HIP_CREATE_ALLOW_CRT, or every launch of a shape of the
+    // CRT domain under HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout and tables, no single-prime table.  The
+    // generic class (a shape no tuned build covers, or every launch under HELM_HIP_PBS_VARIANT=10): always FpH, its own key
+    // layout.
+    form.run = crt_class || force_crt ? BOOL_CRT : form.cls == BOOL_GENERIC || form.variant == 10 ? BOOL_GENERIC : BOOL_TUNED;
+    if (form.run == BOOL_CRT && form.variant != 0)
+        return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(form.variant) +
+                                          " names a single-prime build: a CRT context runs the two-prime kernel only "
+                                          "(leave the variable unset, or 0)");
+    if (form.cls == BOOL_GENERIC && form.variant != 0 && form.variant != 10)
+        return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(form.variant) +
+                                          " names a tuned build, which this shape (N,k,pbs_l) has not: it runs the generic kernel "
+                                          "(variant 10, or leave the variable unset)");
+    // the 49-bit prime (no recentring inside transforms) when the set's exact products fit
+    // below its half and a lazy build exists (N = 512); HELM_HIP_FIELD=51 forces the other
+    // ("49": the lazy field of the boolean kernels is FpG, p = 5072^4 + 1 = 2^49.23, ntt_fp64.h; its first two forward stages
+    // on digits need 2^(logB-1) b^3 far below p/2: any logB <= 12).  N = 1024 starts in the 51-bit field; the key decides
+    // whether the lazy FpI serves (helm_hip_load_bootstrap_key)
+    form.field = (P.N == 512 && bound * 1.002 < FpG::P / 2 && P.pbs_logB <= 12) ? 49 : 51;
+    if (const char *v = getenv("HELM_HIP_FIELD")) if (atoi(v) == 51) form.field = 51;
+    if (form.run != BOOL_TUNED) form.field = form.run == BOOL_CRT ? 98 : 51;
+    // the remainder builds of a tuned shape (HELM_HIP_DUO at N = 512, HELM_HIP_DUO1024 at N = 1024: 0 or a build's number - 5;
+    // HELM_HIP_TRIO=0).  A value outside a switch's range: the default at N = 512, none at N = 1024
+    int duo = P.N == 512 ? 2 : 3;
+    if (const char *v = getenv(P.N == 512 ? "HELM_HIP_DUO" : "HELM_HIP_DUO1024")) {
+        duo = atoi(v);
+        if (P.N == 512 ? duo < 0 || duo > 2 : duo < 1 || duo > 3) duo = P.N == 512 ? 2 : 0;
+    }
+    const char *trio = getenv("HELM_HIP_TRIO");
+    const bool has_trio = form.shape >= 0 && TUNED[form.shape].trio;
+    form.rem[1] = duo ? BUILD_LOCKSTEP + duo : BUILD_LOCKSTEP;
+    form.rem[2] = has_trio && (!trio || atoi(trio) != 0) ? BUILD_TRIO : BUILD_LOCKSTEP;
+    *out = form;
+    return 0;
+}
+
+int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_t flags, helm_hip_ctx **out)
+{
+    if (!params || !out) return fail(HELM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const helm_hip_params &P = *params;
+    BoolForm form;
+    if (int rc = bool_admit(P, flags, &form)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(HELM_ERR_NO_DEVICE, "no HIP device visible (this engine has no CPU fallback)");
@@ -2924,87 +2950,15 @@ int helm_hip_ctx_create_ex(int device_id, const helm_hip_params *params, uint32_
     const int rc = [&]() -> int {
         ctx->device = device_id;
         ctx->P = P;
+        ctx->form = form;
         ctx->n_cus = prop.multiProcessorCount;
-        if (const char *v = getenv("HELM_HIP_PBS_VARIANT")) {
-            ctx->pbs_variant = atoi(v);
-            const int pv = ctx->pbs_variant;
-            if (!(pv == 0 || pv == 4 || pv == 5 || pv == 6 || pv == 7 || pv == 9 || pv == 10 || (pv == 8 && P.N == 1024)))
-                return fail(HELM_ERR_INVALID, std::string("HELM_HIP_PBS_VARIANT=") + v + ": builds are 4 wide, 5 lockstep, 6 / 7 duo in step / "
-                                              "staggered, 9 trio, 10 generic (1 latency, 2 balanced, 3 throughput, 8 sym were retired in round 6)");
-        }
-        if (const char *v = getenv("HELM_HIP_DUO")) ctx->duo_build = atoi(v) >= 0 && atoi(v) <= 2 ? atoi(v) : 2;
-        if (const char *v = getenv("HELM_HIP_DUO1024")) ctx->duo1024 = atoi(v) >= 1 && atoi(v) <= 3 ? atoi(v) : 0;
-        if (const char *v = getenv("HELM_HIP_TRIO")) ctx->trio = atoi(v) != 0;
         if (const char *v = getenv("HELM_HIP_CLOCK_PROBE")) ctx->clock_probe = atoi(v);
         if (const char *v = getenv("HELM_HIP_KS_MFMA")) ctx->ks_mfma = atoi(v);
         while ((1 << ctx->logN) < P.N) ctx->logN++;
         HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
         ctx->stream = ctx->own_stream;
-
-        // the 49-bit prime (no recentring inside transforms) when the set's exact products fit
-        // below its half and a lazy build exists (N = 512); HELM_HIP_FIELD=51 forces the other
-        // ("49": the lazy field of the boolean kernels is FpG, p = 5072^4 + 1 = 2^49.23, ntt_fp64.h; its first two forward stages
-        // on digits need 2^(logB-1) b^3 far below p/2: any logB <= 12).  N = 1024 starts in the 51-bit field; the key decides
-        // whether the lazy FpI serves (helm_hip_load_bootstrap_key)
+        if (int rc = setup_class(ctx)) return rc;
         const int N = P.N;
-        ctx->field = (N == 512 && bound * 1.002 < FpG::P / 2 && P.pbs_logB <= 12) ? 49 : 51;
-        if (const char *v = getenv("HELM_HIP_FIELD")) if (atoi(v) == 51) ctx->field = 51;
-        // the generic class (a shape no tuned build covers, or every launch under HELM_HIP_PBS_VARIANT=10): always FpH, its
-        // own key layout, one workgroup of GEN_THREADS per bootstrap; the quantum follows its occupancy
-        ctx->generic = !pbs_tuned(P);
-        // the CRT class (a shape beyond the single-prime bound under HELM_HIP_CREATE_ALLOW_CRT, or every launch of a shape of
-        // the CRT domain under HELM_HIP_CREATE_FORCE_CRT): FpG x FpG2, its own key layout and tables, no single-prime table
-        ctx->crt_class = crt_class;
-        ctx->crt_path = crt_class || force_crt;
-        if (ctx->crt_path) {
-            if (ctx->pbs_variant != 0)
-                return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(ctx->pbs_variant) +
-                                                  " names a single-prime build: a CRT context runs the two-prime kernel only "
-                                                  "(leave the variable unset, or 0)");
-            ctx->field = 98;
-            if (int rc = setup_crt(ctx)) return rc;
-        } else if (ctx->generic && ctx->pbs_variant != 0 && ctx->pbs_variant != 10)
-            return fail(HELM_ERR_INVALID, "HELM_HIP_PBS_VARIANT=" + std::to_string(ctx->pbs_variant) +
-                                              " names a tuned build, which this shape (N,k,pbs_l) has not: it runs the generic kernel "
-                                              "(variant 10, or leave the variable unset)");
-        ctx->gen_path = !ctx->crt_path && (ctx->generic || ctx->pbs_variant == 10);
-        if (ctx->gen_path) {
-            ctx->field = 51;
-            const void *kern = ctx->logN == 8    ? reinterpret_cast<const void *>(k_pbs_generic<8>)
-                               : ctx->logN == 9  ? reinterpret_cast<const void *>(k_pbs_generic<9>)
-                               : ctx->logN == 10 ? reinterpret_cast<const void *>(k_pbs_generic<10>)
-                                                 : reinterpret_cast<const void *>(k_pbs_generic<11>);
-            // the attribute is the kernel's, shared by every context of the process: the largest layout of this N, so that a
-            // context created later with a smaller one cannot lower it under an earlier context's launches
-            const int K1max = 8192 / N;
-            const size_t lds_max = GenLds(N, K1max, gen_batch(N, K1max - 1, 31), 1024).bytes;
-            HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            // digit polynomials per batch: the most (<= gen_batch) that cost no resident workgroup against one per batch - a
-            // launch of more bootstraps than fit at once runs a partial second round (boolean_default's shape: D = 4 leaves
-            // 3 workgroups per CU, 2 leave 4, 1 leaves 5 - 51.9 against 44.7 ms for 1,024 bootstraps)
-            auto occupancy = [&](int d, int &nb) -> int {
-                nb = 0;
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, GEN_THREADS, GenLds(N, P.k + 1, d, P.n).bytes));
-                return 0;
-            };
-            int nb1 = 0;
-            if (int rc = occupancy(1, nb1)) return rc;
-            if (nb1 < 1) return fail(HELM_ERR_STATE, "k_pbs_generic: no workgroup of " + std::to_string(GenLds(N, P.k + 1, 1, P.n).bytes) +
-                                                         " B LDS fits a CU");
-            ctx->gen_d = 1;
-            for (int d = gen_batch(N, P.k, P.pbs_l); d > 1; d--) {
-                int nb = 0;
-                if (int rc = occupancy(d, nb)) return rc;
-                if (nb == nb1) {
-                    ctx->gen_d = d;
-                    break;
-                }
-            }
-            ctx->gen_lds = GenLds(N, P.k + 1, ctx->gen_d, P.n).bytes;
-            ctx->gen_per_cu = nb1;
-        }
-        if (!ctx->crt_path)
-            if (int rc = setup_field_tables(ctx)) return rc;
         std::vector<uint32_t> tv(N, PT_TRUE);
         HIP_TRY(hipMalloc(&ctx->tv_bool, sizeof(uint32_t) * N));
         HIP_TRY(hipMemcpy(ctx->tv_bool, tv.data(), sizeof(uint32_t) * N, hipMemcpyHostToDevice));
@@ -3103,15 +3057,15 @@ int helm_hip_sync(helm_hip_ctx *ctx)
 int64_t helm_hip_launch_quantum(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null ctx");
-    if (ctx->crt_path) return (int64_t)ctx->crt_per_cu * ctx->n_cus; // k_pbs_crt: one bootstrap per workgroup, all resident
-    if (ctx->gen_path) return (int64_t)ctx->gen_per_cu * ctx->n_cus; // k_pbs_generic: one bootstrap per workgroup, all resident
+    // k_pbs_generic, k_pbs_crt: one bootstrap per workgroup, all resident
+    if (ctx->form.run != BOOL_TUNED) return (int64_t)ctx->form.per_cu * ctx->n_cus;
     return 4 * (int64_t)ctx->n_cus; // PbsCfg::NB bootstraps per workgroup, one workgroup per CU
 }
 
 int helm_hip_kernel_class(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->crt_class ? 2 : ctx->generic ? 1 : 0;
+    return ctx->form.cls;
 }
 
 int64_t helm_hip_wire_words(const helm_hip_ctx *ctx)
@@ -3123,13 +3077,13 @@ int64_t helm_hip_wire_words(const helm_hip_ctx *ctx)
 int helm_hip_digit_batch(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->crt_path ? ctx->crt_d : ctx->gen_path ? ctx->gen_d : 0;
+    return ctx->form.run != BOOL_TUNED ? ctx->form.d : 0;
 }
 
 int helm_hip_field_bits(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    return ctx->field;
+    return ctx->form.field;
 }
 
 #ifdef HELM_CHECK_BOUNDS
@@ -3168,19 +3122,20 @@ int helm_hip_bound_violations(helm_hip_ctx *ctx, uint32_t counts[8], int reset, 
 int helm_hip_short_root_stages(const helm_hip_ctx *ctx)
 {
     if (!ctx) return fail(HELM_ERR_INVALID, "null argument");
-    if (ctx->gen_path || ctx->crt_path) return 0; // k_pbs_generic, k_pbs_crt: plain radix-2 stages throughout
+    if (ctx->form.run != BOOL_TUNED) return 0; // k_pbs_generic, k_pbs_crt: plain radix-2 stages throughout
     return 2; // both fields of this engine (5072^4 + 1, 6432^4 + 1) have short eighth roots
 }
 
 int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4])
 {
     if (!ctx || !cost) return fail(HELM_ERR_INVALID, "null argument");
-    if (ctx->gen_path || ctx->crt_path) {
+    const BoolForm &form = ctx->form;
+    if (form.run != BOOL_TUNED) {
         // k_pbs_generic / k_pbs_crt, from its occupancy W (workgroups per CU, one wave of each on every SIMD): a launch of at most q/4 of
         // the quantum puts w = ceil(q W / 4) workgroups on a CU.  One wave per SIMD leaves the step's latencies (LDS round
         // trips, key loads, barriers) exposed; from two on, the SIMD's time grows with its waves.  Model: time ~ max(1, w / 2),
         // relative to the full round - non-decreasing, cost[3] = 1 (not measured; DESIGN.md "The generic kernel class")
-        const int W = ctx->crt_path ? ctx->crt_per_cu : ctx->gen_per_cu;
+        const int W = form.per_cu;
         const double full = std::max(1.0, W / 2.0);
         for (int q = 1; q <= 4; q++) cost[q - 1] = std::max(1.0, ((q * W + 3) / 4) / 2.0) / full;
         return 0;
@@ -3191,16 +3146,16 @@ int helm_hip_launch_costs(const helm_hip_ctx *ctx, double cost[4])
     // k_pbs_trio a lockstep round of three per CU 0.89 - 0.90 for <= 768)
     if (ctx->P.N == 512) {
         cost[0] = 0.42;
-        cost[1] = ctx->duo_build ? 0.66 : 1.0;
-        cost[2] = ctx->P.k == 2 && ctx->trio ? 0.86 : 0.89;
+        cost[1] = form.rem[1] != BUILD_LOCKSTEP ? 0.66 : 1.0;
+        cost[2] = form.rem[2] == BUILD_TRIO ? 0.86 : 0.89;
     } else { // N = 1024 (helm_cuda, round 5: 3.9 / 5.5 / 8.0 / 8.6 ms - wide, k_pbs_duo's compact layout (two-wave build: 6.05), lockstep rounds;
              // in the lazy field FpI: 3.41 / 5.11 / 7.55 / 7.76 ms, profiles/r05/ab_field1024.jsonl)
-        const bool lazy = ctx->field == 50;
+        const bool lazy = form.field == 50;
         cost[0] = lazy ? 0.44 : 0.45;
         // round 6 (profiles/r06/ab_tri10.jsonl, same process, alternating): k_pbs_tri10 with two / three bootstraps per workgroup -
         // FpI 4.41 / 6.19 of 7.80 ms, FpH 4.65 / 6.49 of 8.32 ms (k_pbs_duo: 5.11 of 7.80; a partial lockstep round: 7.49 / 7.94)
-        cost[1] = ctx->duo1024 == 3 ? 0.57 : ctx->duo1024 ? (lazy ? 0.66 : 0.64) : 1.0;
-        cost[2] = ctx->trio ? (lazy ? 0.80 : 0.78) : (lazy ? 0.97 : 0.93);
+        cost[1] = form.rem[1] == BUILD_TRI10_2 ? 0.57 : form.rem[1] != BUILD_LOCKSTEP ? (lazy ? 0.66 : 0.64) : 1.0;
+        cost[2] = form.rem[2] == BUILD_TRIO ? (lazy ? 0.80 : 0.78) : (lazy ? 0.97 : 0.93);
     }
     cost[3] = 1.0;
     return 0;
@@ -3216,7 +3171,8 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
         return fail(HELM_ERR_INVALID, "bootstrapping key: expected " + std::to_string(polys * P.N) + " words, got " +
                                           std::to_string(n_words));
     HIP_TRY(hipSetDevice(ctx->device));
-    if (P.N == 1024 && !ctx->gen_path && !ctx->crt_path) {
+    BoolForm &form = ctx->form;
+    if (P.N == 1024 && form.run == BOOL_TUNED) {
         // Round 5: which field serves THIS key.  The exact sum an external product can reach is at most B/2 x the l1-norm of
         // the key coefficients that meet in one output coefficient: the (k+1) l polynomials of one key column of one step (a
         // negacyclic product's output coefficient is a signed sum over ALL coefficients of each factor).  Both groupings of
@@ -3251,10 +3207,10 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
         // size, so a small-norm key with larger digits keeps the recentring 51-bit field
         int want = (key_bound * 1.002 < FpI::P / 2 && P.pbs_logB <= 7) ? 50 : 51;
         if (const char *v = getenv("HELM_HIP_FIELD")) if (atoi(v) == 51) want = 51;
-        if (want != ctx->field) {
+        if (want != form.field) {
             HIP_TRY(hipStreamSynchronize(ctx->stream)); // nothing in flight may still read the other field's tables
             if (ctx->xchg_stream) HIP_TRY(hipStreamSynchronize(ctx->xchg_stream));
-            ctx->field = want;
+            form.field = want; // (the one write of the record after creation)
             ctx->have_bsk = false;
             if (int rc = setup_field_tables(ctx)) return rc;
         }
@@ -3262,41 +3218,35 @@ int helm_hip_load_bootstrap_key(helm_hip_ctx *ctx, const uint32_t *bsk_std, size
     Scratch<uint32_t> d_std;
     HIP_TRY(d_std.alloc(n_words));
     // (a CRT context keeps every key word in both fields: 16 bytes per word)
-    if (!ctx->bsk) HIP_TRY(hipMalloc(&ctx->bsk, n_words * sizeof(double) * (ctx->crt_path ? 2 : 1)));
+    if (!ctx->bsk) HIP_TRY(hipMalloc(&ctx->bsk, n_words * sizeof(double) * (form.run == BOOL_CRT ? 2 : 1)));
     HIP_TRY(hipMemcpyAsync(d_std.p, bsk_std, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->crt_path) {
-        // the CRT class's layout: [i][r][c][lev][f][N], bit-reversed transform order (k_bsk_convert_crt)
-#define CRT_CONVERT(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_bsk_convert_crt<LN>, dim3((unsigned)polys), dim3(TP_THREADS), 0, ctx->stream, d_std.p, ctx->bsk,   \
-                       ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_n_inv[0], ctx->crt_n_inv[1], (int)K1, P.pbs_l)
-        if (P.N == 256) CRT_CONVERT(8);
-        else if (P.N == 512) CRT_CONVERT(9);
-        else if (P.N == 1024) CRT_CONVERT(10);
-        else CRT_CONVERT(11);
-#undef CRT_CONVERT
-    } else if (ctx->gen_path) {
-        // the generic class's layout: [i][r][c][lev][N], bit-reversed transform order (k_bsk_convert_generic)
-#define GEN_CONVERT(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_bsk_convert_generic<LN>, dim3((unsigned)polys), dim3(GEN_THREADS), 0, ctx->stream, d_std.p, ctx->bsk, \
-                       ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l)
-        if (P.N == 256) GEN_CONVERT(8);
-        else if (P.N == 512) GEN_CONVERT(9);
-        else if (P.N == 1024) GEN_CONVERT(10);
-        else GEN_CONVERT(11);
-#undef GEN_CONVERT
-    } else if (P.N == 512 && ctx->field == 49)
-        hipLaunchKernelGGL((k_bsk_convert<FpG, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p, ctx->bsk,
-                           ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
-    else if (P.N == 1024 && ctx->field == 50)
-        hipLaunchKernelGGL((k_bsk_convert<FpI, 10>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p, ctx->bsk,
-                           ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
-    else if (P.N == 512)
-        hipLaunchKernelGGL((k_bsk_convert<FpH, 9>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p, ctx->bsk,
-                           ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
-    else
-        hipLaunchKernelGGL((k_bsk_convert<FpH, 10>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p, ctx->bsk,
-                           ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
-    HIP_TRY(hipGetLastError());
+    hipError_t e = hipErrorInvalidValue;
+    switch (form.run) {
+    case BOOL_CRT: // the CRT class's layout: [i][r][c][lev][f][N], bit-reversed transform order (k_bsk_convert_crt)
+        e = with_logn<8, 11>(ctx->logN, e, [&](auto ln) {
+            hipLaunchKernelGGL(k_bsk_convert_crt<decltype(ln)::value>, dim3((unsigned)polys), dim3(TP_THREADS), 0, ctx->stream,
+                               d_std.p, ctx->bsk, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_n_inv[0], ctx->crt_n_inv[1], (int)K1,
+                               P.pbs_l);
+            return hipGetLastError();
+        });
+        break;
+    case BOOL_GENERIC: // the generic class's layout: [i][r][c][lev][N], bit-reversed transform order (k_bsk_convert_generic)
+        e = with_logn<8, 11>(ctx->logN, e, [&](auto ln) {
+            hipLaunchKernelGGL(k_bsk_convert_generic<decltype(ln)::value>, dim3((unsigned)polys), dim3(GEN_THREADS), 0, ctx->stream,
+                               d_std.p, ctx->bsk, ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
+            return hipGetLastError();
+        });
+        break;
+    case BOOL_TUNED:
+        e = with_tuned(form.shape, form.field, e, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_bsk_convert<typename T::F, T::LOGN>), dim3((unsigned)polys), dim3(64), 0, ctx->stream, d_std.p,
+                               ctx->bsk, ctx->tw_fwd, ctx->n_inv, (int)K1, P.pbs_l);
+            return hipGetLastError();
+        });
+        break;
+    }
+    HIP_TRY(e);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->have_bsk = true;
     return 0;
@@ -4070,38 +4020,34 @@ int helm_hip_ntt_roundtrip(helm_hip_ctx *ctx, const uint32_t *poly_in, uint32_t 
     HIP_TRY(d_in.alloc((size_t)count * N));
     HIP_TRY(d_out.alloc((size_t)count * N));
     HIP_TRY(hipMemcpyAsync(d_in.p, poly_in, (size_t)count * N * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->crt_path) {
-#define CRT_ROUNDTRIP(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_ntt_roundtrip_crt<LN>, dim3((unsigned)count), dim3(TP_THREADS), 0, ctx->stream, d_in.p, d_out.p,     \
-                       ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], ctx->crt_n_inv[0], ctx->crt_n_inv[1],  \
-                       ctx->crt_p0inv)
-        if (N == 256) CRT_ROUNDTRIP(8);
-        else if (N == 512) CRT_ROUNDTRIP(9);
-        else if (N == 1024) CRT_ROUNDTRIP(10);
-        else CRT_ROUNDTRIP(11);
-#undef CRT_ROUNDTRIP
-    } else if (ctx->gen_path) {
-#define GEN_ROUNDTRIP(LN)                                                                                                     \
-    hipLaunchKernelGGL(k_ntt_roundtrip_generic<LN>, dim3((unsigned)count), dim3(GEN_THREADS), 0, ctx->stream, d_in.p, d_out.p, \
-                       ctx->tw_fwd, ctx->tw_inv, ctx->n_inv)
-        if (N == 256) GEN_ROUNDTRIP(8);
-        else if (N == 512) GEN_ROUNDTRIP(9);
-        else if (N == 1024) GEN_ROUNDTRIP(10);
-        else GEN_ROUNDTRIP(11);
-#undef GEN_ROUNDTRIP
-    } else if (N == 512 && ctx->field == 49)
-        hipLaunchKernelGGL((k_ntt_roundtrip<FpG, 9>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p, d_out.p,
-                           ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
-    else if (N == 1024 && ctx->field == 50)
-        hipLaunchKernelGGL((k_ntt_roundtrip<FpI, 10>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p, d_out.p,
-                           ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
-    else if (N == 512)
-        hipLaunchKernelGGL((k_ntt_roundtrip<FpH, 9>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p, d_out.p,
-                           ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
-    else
-        hipLaunchKernelGGL((k_ntt_roundtrip<FpH, 10>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p, d_out.p,
-                           ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
-    HIP_TRY(hipGetLastError());
+    const BoolForm &form = ctx->form;
+    hipError_t e = hipErrorInvalidValue;
+    switch (form.run) {
+    case BOOL_CRT:
+        e = with_logn<8, 11>(ctx->logN, e, [&](auto ln) {
+            hipLaunchKernelGGL(k_ntt_roundtrip_crt<decltype(ln)::value>, dim3((unsigned)count), dim3(TP_THREADS), 0, ctx->stream,
+                               d_in.p, d_out.p, ctx->crt_tw[0], ctx->crt_tw[1], ctx->crt_tw[2], ctx->crt_tw[3], ctx->crt_n_inv[0],
+                               ctx->crt_n_inv[1], ctx->crt_p0inv);
+            return hipGetLastError();
+        });
+        break;
+    case BOOL_GENERIC:
+        e = with_logn<8, 11>(ctx->logN, e, [&](auto ln) {
+            hipLaunchKernelGGL(k_ntt_roundtrip_generic<decltype(ln)::value>, dim3((unsigned)count), dim3(GEN_THREADS), 0,
+                               ctx->stream, d_in.p, d_out.p, ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
+            return hipGetLastError();
+        });
+        break;
+    case BOOL_TUNED:
+        e = with_tuned(form.shape, form.field, e, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_ntt_roundtrip<typename T::F, T::LOGN>), dim3((unsigned)count), dim3(64), 0, ctx->stream, d_in.p,
+                               d_out.p, ctx->tw_fwd, ctx->tw_inv, ctx->n_inv);
+            return hipGetLastError();
+        });
+        break;
+    }
+    HIP_TRY(e);
     HIP_TRY(hipMemcpyAsync(poly_out, d_out.p, (size_t)count * N * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;

@@ -19,6 +19,7 @@
 #include "ntt_fp64.h"
 #include "many_lut_rule.h"
 #include "keyswitch.h"
+#include "with_logn.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -1673,15 +1674,6 @@ auto with_group(int group, F &&f)
     return f(std::integral_constant<int, 0>{});
 }
 
-// The run-time logN as the kernels' compile-time LOGN: f(std::integral_constant<int, LOGN>) for LO <= logN <= HI - the call
-// site names the range, so it instantiates the kernels of that range and no other - and `outside` for any other logN.
-template <int LO, int HI, class R, class F>
-R with_logn(int logN, R outside, F &&f)
-{
-    if (logN == LO) return f(std::integral_constant<int, LO>{});
-    if constexpr (LO < HI) return with_logn<LO + 1, HI>(logN, outside, f);
-    else return outside;
-}
 // Two translation units from this one source (Makefile).  The compiler's max-ILP scheduling strategy
 // (-mllvm -amdgpu-sched-strategy=max-ilp; there is no per-function switch) is worth +3.7 % on k_pbs64k and +2.0 % on the
 // multi-bit k_pbs64s, and costs the classical k_pbs64s 0.8 % and its two-level build 1.8 % (same box, alternating,
