@@ -16,6 +16,7 @@
 #include "ntt_fp64.h"
 #include "shard_rule.h"
 #include "keyswitch.h"
+#include "pbs_frame.h"
 #include "with_logn.h"
 
 #include <hip/hip_runtime.h>
@@ -64,16 +65,6 @@ int helm_hip_runtime_guard_(const char *where); // helm_comm.cpp: one HIP runtim
 // ------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------
-#define PT_TRUE 0x20000000u  // +1/8, reference src/circuit.rs:29
-#define PT_FALSE 0xE0000000u // -1/8, reference src/circuit.rs:33
-
-struct PbsJob {
-    int32_t op;    // helm_gate_op, or -1: raw LWE taken from `raw_in`
-    int32_t which; // MUX: 0 -> AND(sel, in0) half, 1 -> AND(!sel, in1) half
-    int32_t in0, in1, in2;
-    int32_t tv;    // test-vector row
-};
-
 struct KsJob {
     int32_t big0, big1; // rows of the big-LWE buffer to add (big1 = -1: single)
     int32_t out;        // destination row (wire index, or staging row)
@@ -83,28 +74,6 @@ struct KsJob {
 struct LinJob {
     int32_t op, in0, out;
 };
-
-// Gate linear step, tfhe boolean engine formulas (see oracle/tfhe_oracle.c header).
-__device__ __forceinline__ uint32_t gate_lincomb(int op, int which, uint32_t l, uint32_t r, uint32_t c, bool body)
-{
-    const uint32_t t = body ? PT_TRUE : 0u, f = body ? PT_FALSE : 0u;
-    switch (op) {
-    case HELM_GATE_AND: return l + r + f;
-    case HELM_GATE_OR: return l + r + t;
-    case HELM_GATE_NAND: return 0u - (l + r) + t;
-    case HELM_GATE_NOR: return 0u - (l + r) + f;
-    case HELM_GATE_XOR: return 2u * (l + r + t);
-    case HELM_GATE_XNOR: return 2u * (0u - (l + r + t));
-    case HELM_GATE_MUX: return which == 0 ? (c + l + f) : (0u - c + r + f);
-    default: return 0u;
-    }
-}
-
-__device__ __forceinline__ uint32_t modswitch(uint32_t x, int log2_2N)
-{
-    uint32_t r = (x >> (32 - log2_2N - 1)) + 1u;
-    return (r >> 1) & ((1u << log2_2N) - 1u);
-}
 
 // Signed gadget decomposition, closest representable + balanced digits (tfhe's SignedDecomposer:
 //   d = state & (B-1); state >>= logB; carry = (((d-1) | state) & d) >> (logB-1); state += carry;
@@ -273,21 +242,7 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
     const size_t row = (size_t)n + 1;
 
     // ---- gate linear step + modulus switch (whole workgroup) ------------------------
-    {
-        const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
-        if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
-        else {
-            if (job.in0 >= 0) a0 = wires + row * (size_t)job.in0;
-            if (job.in1 >= 0) a1 = wires + row * (size_t)job.in1;
-            if (job.in2 >= 0) a2 = wires + row * (size_t)job.in2;
-        }
-        for (int i = tid; i <= n; i += 64 * K1) {
-            uint32_t v;
-            if (job.op < 0) v = a0[i];
-            else v = gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, i == n);
-            MS[i] = (uint16_t)modswitch(v, LOGN + 1);
-        }
-    }
+    switch_row(MS, GateRows(job, wires, raw_in, row), n, tid, 64 * K1, LOGN + 1);
     // ---- twiddles: the lane-major LDS table (block A: lane-uniform scalars) ---------------
     // C::BLK8 (N = 512 in FpG): blocks B and C of both transforms in the 8-point block form - the lane's seven powers w^t of
     // its group root per block in registers (forward), the w^-t in the LDS table (inverse), the same 14 rows
@@ -300,14 +255,10 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
     TwI twi;
     {
         double *TW = reinterpret_cast<double *>(smem + C::TW_OFF);
-        for (int r = p; r < C::TW_ROWS; r += K1) {
-            if constexpr (C::BLK8) TW[r * 64 + lane] = tw_blk8_row<LOGN, -1>(tw_fwd, r, lane);
-            else TW[r * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(r, lane)];
-        }
-        twf0.base = TW + lane;
-        twi.base = TW + (63 - lane);
-        twf0.fill_uniform(tw_fwd);
-        twi.fill_uniform(tw_fwd);
+        if constexpr (C::BLK8) {
+            for (int r = p; r < C::TW_ROWS; r += K1) TW[r * 64 + lane] = tw_blk8_row<LOGN, -1>(tw_fwd, r, lane);
+        } else tw_lane_fill<LOGN>(TW, tw_fwd, p, K1, C::TW_ROWS, lane);
+        tw_lane_views(twf0, twi, TW, tw_fwd, lane);
         if constexpr (C::BLK8) {
             twi.row = TW + lane;
             twf.load(tw_fwd, lane);
@@ -327,26 +278,11 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
         const uint32_t *tv = tvs + (size_t)job.tv * N;
 #pragma unroll
         for (int e = 0; e < E; e++) {
-            const int j = G::jA(lane, e);
-            uint32_t v = 0;
-            if (p == K) {
-                const int idx = (j + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0u - v;
-            }
+            const uint32_t v = p == K ? lut_rotated(tv, G::jA(lane, e), bt, N) : 0u;
             nacc[e] = 0u - v;
         }
     }
-    auto acc_store = [&]() { // acc3[j] = v, acc3[j + N] = -v, acc3[j + 2N] = v (j < N - 64)
-        uint32_t *aw = acc_p + lane;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const uint32_t v = 0u - nacc[e];
-            aw[64 * e] = v;
-            aw[64 * e + N] = nacc[e];
-            if (e < E - 1) aw[64 * e + 2 * N] = v;
-        }
-    };
+    auto acc_store = [&]() { acc3_store<N, E, true, true>(acc_p + lane, nacc); };
     acc_store();
     lds_wave_sync();
 
@@ -506,18 +442,7 @@ __global__ __launch_bounds__(64 * (C::K + 1) * C::NB, 1) void k_pbs(const PbsJob
         g_clock_probe[3] = __builtin_amdgcn_s_memrealtime();
     }
     // ---- sample extract (coefficient 0): wave p writes its own polynomial -------------
-    uint32_t *ob = out_big + (size_t)jix * ((size_t)K * N + 1);
-    if (p < K) {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int j = G::jA(lane, e); // nacc[e] = -A_p[j]
-            // out[p*N + t] = (t == 0) ? A[0] : -A[N - t]
-            if (j == 0) ob[p * N] = 0u - nacc[e];
-            else ob[p * N + (N - j)] = nacc[e];
-        }
-    } else if (lane == 0) {
-        ob[K * N] = 0u - nacc[0]; // body = B[0]
-    }
+    sample_extract0<K, N, -1>(out_big, jix, p, lane == 0, nacc, lane); // nacc[e] = -A_p[jA(lane, e)]
 }
 
 // ------------------------------------------------------------------------------------
@@ -593,22 +518,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     }
     const PbsJob job = jobs[blockIdx.x];
     const size_t row = (size_t)n + 1;
-    {
-        const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
-        if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
-        else {
-            if (job.in0 >= 0) a0 = wires + row * (size_t)job.in0;
-            if (job.in1 >= 0) a1 = wires + row * (size_t)job.in1;
-            if (job.in2 >= 0) a2 = wires + row * (size_t)job.in2;
-        }
-        for (int i = tid; i <= n; i += 64 * NW) {
-            uint32_t v;
-            if (job.op < 0) v = a0[i];
-            else v = gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, i == n);
-            MS[i] = (uint16_t)modswitch(v, LOGN + 1);
-        }
-    }
-    for (int q = w; q < C::TW_ROWS; q += NW) TW[q * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(q, lane)];
+    switch_row(MS, GateRows(job, wires, raw_in, row), n, tid, 64 * NW, LOGN + 1);
+    tw_lane_fill<LOGN>(TW, tw_fwd, w, NW, C::TW_ROWS, lane);
     for (int j = tid; j < K1 * N; j += 64 * NW) COL[j] = 0.0;
     // Round 4: at N = 512 the lane's block-B / block-C twiddles of BOTH directions are copied into registers once per
     // kernel (2 x 14 doubles: 110 -> 166 registers, the limit for the three waves of SIMD 0 is 168) instead of read from the
@@ -618,10 +529,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     constexpr int TWR = LOGN == 9 ? 3 : 0; // bit 0: forward twiddles in registers, bit 1: inverse
     TwLane<LOGN, false> twf0;
     TwLane<LOGN, true> twi0;
-    twf0.base = TW + lane;
-    twi0.base = TW + (63 - lane);
-    twf0.fill_uniform(tw_fwd);
-    twi0.fill_uniform(tw_fwd);
+    tw_lane_views(twf0, twi0, TW, tw_fwd, lane);
     __syncthreads();
     typename std::conditional<(TWR & 1) != 0, TwLaneReg<LOGN, false>, TwLane<LOGN, false>>::type twf;
     typename std::conditional<(TWR & 2) != 0, TwLaneReg<LOGN, true>, TwLane<LOGN, true>>::type twi;
@@ -634,28 +542,12 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     // and publishes the negacyclically unrolled u32 copy every wave of the polynomial reads
     uint32_t *acc_r = ACC + (size_t)r * C::ACC3;
     uint32_t accr[E];
-    auto acc_store = [&]() {
-        uint32_t *aw = acc_r + lane;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            aw[64 * e] = accr[e];
-            aw[64 * e + N] = 0u - accr[e];
-            if (e < E - 1) aw[64 * e + 2 * N] = accr[e];
-        }
-    };
+    auto acc_store = [&]() { acc3_store<N, E, false, true>(acc_r + lane, accr); };
     if (lev == 0) {
         const int bt = (int)MS[n];
         const uint32_t *tv = tvs + (size_t)job.tv * N;
 #pragma unroll
-        for (int e = 0; e < E; e++) {
-            uint32_t v = 0;
-            if (r == K) {
-                const int idx = (G::jA(lane, e) + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0u - v;
-            }
-            accr[e] = v;
-        }
+        for (int e = 0; e < E; e++) accr[e] = r == K ? lut_rotated(tv, G::jA(lane, e), bt, N) : 0u;
         acc_store();
     }
     __syncthreads();
@@ -759,19 +651,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_wide(const PbsJob *__rest
     }
     STAMP_END(w)
 
-    uint32_t *ob = out_big + (size_t)blockIdx.x * ((size_t)K * N + 1);
-    if (lev == 0) {
-        if (r < K) {
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const int j = G::jA(lane, e);
-                if (j == 0) ob[r * N] = accr[e];
-                else ob[r * N + (N - j)] = 0u - accr[e];
-            }
-        } else if (lane == 0) {
-            ob[K * N] = accr[0];
-        }
-    }
+    if (lev == 0) sample_extract0<K, N, 1>(out_big, blockIdx.x, r, lane == 0, accr, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -883,30 +763,13 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     const int tid = wb * 64 + lane;      // thread index within the bootstrap
     const PbsJob job = jobs[jix];
     const size_t row = (size_t)n + 1;
-    {
-        const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
-        if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
-        else {
-            if (job.in0 >= 0) a0 = wires + row * (size_t)job.in0;
-            if (job.in1 >= 0) a1 = wires + row * (size_t)job.in1;
-            if (job.in2 >= 0) a2 = wires + row * (size_t)job.in2;
-        }
-        for (int i = tid; i <= n; i += 64 * NWB) {
-            uint32_t v;
-            if (job.op < 0) v = a0[i];
-            else v = gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, i == n);
-            MS[i] = (uint16_t)modswitch(v, LOGN + 1);
-        }
-    }
-    for (int q = wb; q < C::TW_ROWS; q += NWB) TW[q * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(q, lane)];
+    switch_row(MS, GateRows(job, wires, raw_in, row), n, tid, 64 * NWB, LOGN + 1);
+    tw_lane_fill<LOGN>(TW, tw_fwd, wb, NWB, C::TW_ROWS, lane);
     for (int j = tid; j < K1 * N; j += 64 * NWB) COL[j] = 0.0;
     // the forward direction's per-lane twiddles in registers (123 -> 151): 1.5 % (same-box A/B with the wide kernel's)
     TwLane<LOGN, false> twf0;
     TwLane<LOGN, true> twi;
-    twf0.base = TW + lane;
-    twi.base = TW + (63 - lane);
-    twf0.fill_uniform(tw_fwd);
-    twi.fill_uniform(tw_fwd);
+    tw_lane_views(twf0, twi, TW, tw_fwd, lane);
     __syncthreads();
     TwLaneReg<LOGN, false> twf;
     twf.load(twf0);
@@ -914,28 +777,12 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     // accumulator (0, ..., 0, X^{-b~} tv): part B of polynomial r owns it (registers) and publishes the unrolled u32 copy
     uint32_t *acc_r = ACC + (size_t)r * C::ACC3;
     uint32_t accr[E];
-    auto acc_store = [&]() {
-        uint32_t *aw = acc_r + lane;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            aw[64 * e] = accr[e];
-            aw[64 * e + N] = 0u - accr[e];
-            if (!C::COMPACT && e < E - 1) aw[64 * e + 2 * N] = accr[e];
-        }
-    };
+    auto acc_store = [&]() { acc3_store<N, E, false, !C::COMPACT>(acc_r + lane, accr); };
     if (g == 1) {
         const int bt = (int)MS[n];
         const uint32_t *tv = tvs + (size_t)job.tv * N;
 #pragma unroll
-        for (int e = 0; e < E; e++) {
-            uint32_t v = 0;
-            if (r == K) {
-                const int idx = (G::jA(lane, e) + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0u - v;
-            }
-            accr[e] = v;
-        }
+        for (int e = 0; e < E; e++) accr[e] = r == K ? lut_rotated(tv, G::jA(lane, e), bt, N) : 0u;
         acc_store();
     }
     __syncthreads();
@@ -1059,19 +906,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void k_pbs_duo(const PbsJob 
     }
     STAMP_END(w)
 
-    uint32_t *ob = out_big + (size_t)jix * ((size_t)K * N + 1);
-    if (g == 1) {
-        if (r < K) {
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const int j = G::jA(lane, e);
-                if (j == 0) ob[r * N] = accr[e];
-                else ob[r * N + (N - j)] = 0u - accr[e];
-            }
-        } else if (lane == 0) {
-            ob[K * N] = accr[0];
-        }
-    }
+    if (g == 1) sample_extract0<K, N, 1>(out_big, jix, r, lane == 0, accr, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1132,7 +967,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
     double *TW = reinterpret_cast<double *>(smem_wg);
     // the lane table of the forward twiddles, one for the workgroup: filled by every wave BEFORE the waves without a
     // bootstrap leave (the hardware barrier counts the surviving waves only)
-    for (int r = wv; r < C::TW_ROWS; r += C::NW) TW[r * 64 + lane] = tw_fwd[tw_lane_index<LOGN>(r, lane)];
+    tw_lane_fill<LOGN>(TW, tw_fwd, wv, C::NW, C::TW_ROWS, lane);
     __syncthreads();
     if (jix >= count) return;
     unsigned char *smem = smem_wg + C::TW_BYTES + (size_t)(wv % NB) * C::BOOT_BYTES;
@@ -1145,28 +980,11 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
     const int tid = role * 64 + lane;
 
     // ---- gate linear step + modulus switch (the bootstrap's four waves) ----------------
-    {
-        const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
-        if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
-        else {
-            if (job.in0 >= 0) a0 = wires + row * (size_t)job.in0;
-            if (job.in1 >= 0) a1 = wires + row * (size_t)job.in1;
-            if (job.in2 >= 0) a2 = wires + row * (size_t)job.in2;
-        }
-        for (int i = tid; i <= n; i += 64 * C::NWB) {
-            uint32_t v;
-            if (job.op < 0) v = a0[i];
-            else v = gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, i == n);
-            MS[i] = (uint16_t)modswitch(v, LOGN + 1);
-        }
-    }
+    switch_row(MS, GateRows(job, wires, raw_in, row), n, tid, 64 * C::NWB, LOGN + 1);
     TwLane<LOGN, false> twf0;
     TwLane<LOGN, true> twi;
     TwLaneFwdReg<LOGN> twf;
-    twf0.base = TW + lane;
-    twi.base = TW + (63 - lane);
-    twf0.fill_uniform(tw_fwd);
-    twi.fill_uniform(tw_fwd);
+    tw_lane_views(twf0, twi, TW, tw_fwd, lane);
     twf.load(twf0); // this lane's forward twiddles of blocks B and C in registers (as the lockstep build)
     __syncthreads(); // MS complete
 
@@ -1260,26 +1078,9 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
         const int bt = (int)MS[n];
         const uint32_t *tv = tvs + (size_t)job.tv * N;
 #pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int j = G::jA(lane, e);
-            uint32_t v = 0;
-            if (p == K) {
-                const int idx = (j + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0u - v;
-            }
-            accr[e] = v;
-        }
+        for (int e = 0; e < E; e++) accr[e] = p == K ? lut_rotated(tv, G::jA(lane, e), bt, N) : 0u;
     }
-    auto acc_store = [&]() {
-        uint32_t *aw = acc_p + lane;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            aw[64 * e] = accr[e];
-            aw[64 * e + N] = 0u - accr[e];
-            if (e < E - 1) aw[64 * e + 2 * N] = accr[e];
-        }
-    };
+    auto acc_store = [&]() { acc3_store<N, E, false, true>(acc_p + lane, accr); };
     acc_store();
     lds_wave_sync();
     const unsigned row_off = (unsigned)(p * K1 * L) * poly_bytes;
@@ -1391,17 +1192,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_trio(const PbsJob *__rest
     STAMP_END(wv)
 
     // ---- sample extract (coefficient 0): wave p writes its own polynomial -------------
-    uint32_t *ob = out_big + (size_t)jix * ((size_t)K * N + 1);
-    if (p < K) {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const int j = G::jA(lane, e);
-            if (j == 0) ob[p * N] = accr[e];
-            else ob[p * N + (N - j)] = 0u - accr[e];
-        }
-    } else if (lane == 0) {
-        ob[K * N] = accr[0];
-    }
+    sample_extract0<K, N, 1>(out_big, jix, p, lane == 0, accr, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1499,7 +1290,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs_tri10(const PbsJob *__res
     const int tid = wb * 64 + lane;
     const PbsJob job = jobs[jix];
     const size_t row = (size_t)n + 1;
-    {
+    { // (this kernel keeps its own prologue, initialisation and extract: profiles/README.md r27)
         const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
         if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
         else {
@@ -1770,28 +1561,14 @@ __global__ __launch_bounds__(256) void k_ks_zero(const KsJob *__restrict__ jobs,
 // them (the +-1/8 on the body word, index k*N); k_ks_mfma runs behind k_ks_gate_digits with the identity job list.  The small
 // row of job i is row i of the context's staging buffer (`out`); the blind-rotate kernels then take those rows as raw LWEs.
 // ------------------------------------------------------------------------------------
-struct GateRows {
-    const uint32_t *a0, *a1, *a2;
-    __device__ __forceinline__ GateRows(const PbsJob &job, const uint32_t *wires, size_t row)
-        : a0(job.in0 >= 0 ? wires + row * (size_t)job.in0 : nullptr), a1(job.in1 >= 0 ? wires + row * (size_t)job.in1 : nullptr),
-          a2(job.in2 >= 0 ? wires + row * (size_t)job.in2 : nullptr)
-    {
-    }
-    __device__ __forceinline__ uint32_t word(const PbsJob &job, int i, bool body) const
-    {
-        return gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, body);
-    }
-};
-
-// PbsJob rows: the gate's linear combination of its wire rows; job g writes row g
+// PbsJob rows: the gate's linear combination of its wire rows (GateRows, pbs_frame.h); job g writes row g
 struct GateKsRows {
     using Job = PbsJob;
     using Word = uint32_t;
-    const PbsJob &job;
     const GateRows rows;
-    __device__ __forceinline__ GateKsRows(const PbsJob &job, const uint32_t *wires, size_t row) : job(job), rows(job, wires, row) {}
-    __device__ __forceinline__ uint32_t word(int t) const { return rows.word(job, t, false); }
-    __device__ __forceinline__ uint32_t body(int kN) const { return rows.word(job, kN, true); }
+    __device__ __forceinline__ GateKsRows(const PbsJob &job, const uint32_t *wires, size_t row) : rows(job, wires, row) {}
+    __device__ __forceinline__ uint32_t word(int t) const { return rows.word(t, false); }
+    __device__ __forceinline__ uint32_t body(int kN) const { return rows.word(kN, true); }
     static __device__ __forceinline__ int out_row(const PbsJob &, int g) { return g; }
 };
 

@@ -74,22 +74,14 @@ __global__ __launch_bounds__(TP_THREADS) void k_pbs64_generic(const Pbs64Job *__
     const Pbs64Job job = jobs[blockIdx.x];
 
     // ---- modulus switch --------------------------------------------------------------------
-    const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
-    for (int i = tid; i <= n; i += TP_THREADS) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
+    switch_row(MS, job_row(job, small, n), n, tid, TP_THREADS, LOGN + 1);
     __syncthreads();
     // ---- accumulator: (0, ..., 0, X^{-b~} lut) ---------------------------------------------
     {
         const int bt = (int)MS[n];
         const uint64_t *tv = luts + (size_t)job.lut * N;
-        for (int idx = tid; idx < K1 * N; idx += TP_THREADS) {
-            uint64_t v = 0;
-            if (idx >= K * N) {
-                const int s = ((idx - K * N) + bt) & (2 * N - 1);
-                v = tv[s & (N - 1)];
-                if (s >= N) v = 0ull - v;
-            }
-            acc[idx] = v;
-        }
+        for (int idx = tid; idx < K1 * N; idx += TP_THREADS)
+            acc[idx] = idx >= K * N ? lut_rotated(tv, idx - K * N, bt, N) : 0ull;
     }
     __syncthreads();
 
@@ -209,15 +201,8 @@ __global__ __launch_bounds__(TP_THREADS) void k_pbs64_generic(const Pbs64Job *__
 
     // ---- sample extract: every output of the job (extract_put; pad = 0: the one at coefficient 0) ----------
     const int n_out = pbs64_job_outputs(job.pad), ls = pbs64_job_log_stride(job.pad);
-    for (int x = 0; x < n_out; x++) {
-        const int h = x << ls;
-        uint64_t *ob = out + (size_t)(job.out_row + x) * ((size_t)K * N + 1);
-        for (int idx = tid; idx < K * N; idx += TP_THREADS) {
-            const int r = idx >> LOGN, j = idx & (N - 1);
-            extract_put(ob + (size_t)r * N, N, h, j, acc[idx]);
-        }
-        if (tid == 0) ob[(size_t)K * N] = acc[(size_t)K * N + h]; // body = B[h]
-    }
+    for (int x = 0; x < n_out; x++)
+        sample_extract_lds<LOGN>(big_row(out, job.out_row + x, K, N), acc, K, x << ls, tid, TP_THREADS);
 }
 
 // One workgroup per key polynomial: standard-domain u64 coefficients (taken as signed) -> both fields -> tp_convert:

@@ -166,17 +166,15 @@ __device__ __forceinline__ void l64_prologue(Acc acc, uint16_t *MS, const Pbs64J
 {
     constexpr int N = 1 << LOGN, PT = L64_PT<LOGN>;
     const int tid = (int)threadIdx.x;
-    const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
-    for (int i = tid; i <= n; i += L64_THREADS) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
+    switch_row(MS, job_row(job, small, n), n, tid, L64_THREADS, LOGN + 1);
     __syncthreads();
     const int bt = (int)MS[n];
     const uint64_t *tv = luts + (size_t)job.lut * N;
 #pragma unroll
     for (int m = 0; m < PT; m++) {
-        const int j = tid + m * L64_THREADS, s = (j + bt) & (2 * N - 1);
-        const uint64_t v = tv[s & (N - 1)];
+        const uint64_t v = lut_rotated(tv, tid + m * L64_THREADS, bt, N);
         acc.own(0, m) = 0;
-        acc.own(1, m) = s >= N ? 0ull - v : v;
+        acc.own(1, m) = v;
     }
 }
 
@@ -286,7 +284,7 @@ __device__ __forceinline__ void l64_sample_extract(Acc acc, const Pbs64Job &job,
     const int n_out = pbs64_job_outputs(job.pad), ls = pbs64_job_log_stride(job.pad);
     for (int x = 0; x < n_out; x++) {
         const int h = x << ls;
-        uint64_t *ob = out + (size_t)(job.out_row + x) * ((size_t)N + 1);
+        uint64_t *ob = big_row(out, job.out_row + x, 1, N);
 #pragma unroll
         for (int m = 0; m < PT; m++) extract_put(ob, N, h, tid + m * L64_THREADS, acc.own(0, m));
         if (tid == 0) ob[N] = acc.at(1, h); // body = B[h]

@@ -60,21 +60,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_pbs_crt(const PbsJob *__restrict
     const size_t row = (size_t)n + 1;
 
     // ---- gate linear step + modulus switch ---------------------------------------------------
-    {
-        const uint32_t *a0 = nullptr, *a1 = nullptr, *a2 = nullptr;
-        if (job.op < 0) a0 = raw_in + row * (size_t)job.in0;
-        else {
-            if (job.in0 >= 0) a0 = wires + row * (size_t)job.in0;
-            if (job.in1 >= 0) a1 = wires + row * (size_t)job.in1;
-            if (job.in2 >= 0) a2 = wires + row * (size_t)job.in2;
-        }
-        for (int i = tid; i <= n; i += TP_THREADS) {
-            uint32_t v;
-            if (job.op < 0) v = a0[i];
-            else v = gate_lincomb(job.op, job.which, a0 ? a0[i] : 0u, a1 ? a1[i] : 0u, a2 ? a2[i] : 0u, i == n);
-            MS[i] = (uint16_t)modswitch(v, LOGN + 1);
-        }
-    }
+    switch_row(MS, GateRows(job, wires, raw_in, row), n, tid, TP_THREADS, LOGN + 1);
     __syncthreads();
     // ---- accumulator init: (0, ..., 0, X^{-b~} tv) -----------------------------------------
     {
@@ -82,13 +68,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_pbs_crt(const PbsJob *__restrict
         const uint32_t *tv = tvs + (size_t)job.tv * N;
         for (int idx = tid; idx < K1 * N; idx += TP_THREADS) {
             const int r = idx >> LOGN, j = idx & (N - 1);
-            uint32_t v = 0;
-            if (r == K) {
-                const int s = (j + bt) & (2 * N - 1);
-                v = tv[s & (N - 1)];
-                if (s >= N) v = 0u - v;
-            }
-            acc[idx] = v;
+            acc[idx] = r == K ? lut_rotated(tv, j, bt, N) : 0u;
         }
     }
     __syncthreads();
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_pbs_crt(const PbsJob *__restrict
     }
 
     // ---- sample extract (coefficient 0) ----------------------------------------------------
-    uint32_t *ob = out_big + (size_t)blockIdx.x * ((size_t)K * N + 1);
+    uint32_t *ob = big_row(out_big, blockIdx.x, K, N);
     for (int idx = tid; idx < K * N; idx += TP_THREADS) {
         const int r = idx >> LOGN, t = idx & (N - 1);
         // out[r N + t] = (t == 0) ? A_r[0] : -A_r[N - t]

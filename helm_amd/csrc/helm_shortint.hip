@@ -19,6 +19,7 @@
 #include "ntt_fp64.h"
 #include "many_lut_rule.h"
 #include "keyswitch.h"
+#include "pbs_frame.h"
 #include "with_logn.h"
 
 #include <hip/hip_runtime.h>
@@ -109,10 +110,10 @@ struct Ks64Job {
     int32_t out_row; // row of the small-LWE buffer
 };
 
-__device__ __forceinline__ uint32_t modswitch64(uint64_t x, int log2_2N)
+// the input row of a job: row in_row of `small` as it is
+__device__ __forceinline__ PlainRow<uint64_t> job_row(const Pbs64Job &job, const uint64_t *small, int n)
 {
-    uint32_t r = (uint32_t)(x >> (64 - log2_2N - 1)) + 1u;
-    return (r >> 1) & ((1u << log2_2N) - 1u);
+    return PlainRow<uint64_t>(small, job.in_row, n);
 }
 
 // exact integer in a double (|v| < 2^51) -> two's complement int64
@@ -122,15 +123,6 @@ __device__ __forceinline__ int64_t to_int64(double v)
     const uint32_t lo = (uint32_t)__double2loint(m);
     const int32_t hi = (int32_t)((uint32_t)__double2hiint(m) & 0xFFFFFu) - 0x80000;
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | lo);
-}
-
-// Sample extract at coefficient h of the accumulator (A_0 .. A_{k-1}, B): mask word r N + u is A_r[h - u] for u <= h and
-// -A_r[N + h - u] for u > h, the body is B[h].  Seen from accumulator coefficient j of polynomial r: it goes to word
-// u = (h - j) mod N, with its own sign for j <= h and negated for j > h - a permutation of the row's words for every h, so a
-// wave that holds a set of coefficients writes as many words for any h (h = 0: word 0 is A_r[0], word N - j is -A_r[j]).
-__device__ __forceinline__ void extract_put(uint64_t *__restrict__ row_r, int N, int h, int j, uint64_t v)
-{
-    row_r[(h - j) & (N - 1)] = j <= h ? v : 0ull - v;
 }
 
 // The epilogue of the tuned bootstrap kernels: every output of the job (pbs64_job_outputs(pad), pad = 0: the one at
@@ -145,7 +137,7 @@ __device__ __forceinline__ void sample_extract_outputs(uint64_t *__restrict__ ou
     const int n_out = pbs64_job_outputs(pad), ls = pbs64_job_log_stride(pad);
     for (int x = 0; x < n_out; x++) {
         const int h = x << ls;
-        uint64_t *ob = out + (size_t)(out_row + x) * ((size_t)K * N + 1);
+        uint64_t *ob = big_row(out, out_row + x, K, N);
         if (p < K) {
 #pragma unroll
             for (int e = 0; e < CNT; e++) {
@@ -357,10 +349,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64(const Pbs64Job *__restr
     const Pbs64Job job = jobs[blockIdx.x];
     if constexpr (MODE == 2) {
         if (tid == 0) MS[0] = 1, MS[1] = 0;
-    } else {
-        const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
-        for (int i = tid; i <= n; i += 64 * C::NW) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
-    }
+    } else switch_row(MS, job_row(job, small, n), n, tid, 64 * C::NW, LOGN + 1);
     for (int i = tid; i < C::TW_IDX; i += 64 * C::NW) {
         TW[i] = tw0[i];
         TW[C::TW_FIELD + i] = tw1[i];
@@ -375,15 +364,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64(const Pbs64Job *__restr
     if constexpr (MODE == 0) {
         const int bt = (int)MS[n];
         const uint64_t *tv = luts + (size_t)job.lut * N;
-        for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) {
-            uint64_t v = 0;
-            if (j >= K * N) {
-                const int idx = ((j - K * N) + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0ull - v;
-            }
-            ACC[j] = v;
-        }
+        for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) ACC[j] = j >= K * N ? lut_rotated(tv, j - K * N, bt, N) : 0ull;
     } else {
         const uint64_t *c0 = luts + (size_t)job.lut * ((size_t)(K + 1) * N);
         for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) ACC[j] = c0[j];
@@ -618,8 +599,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int p = w >> 1, f = w & 1;
     const Pbs64Job job = jobs[blockIdx.x];
-    const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
-    for (int i = tid; i <= n; i += 64 * C::NW) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
+    switch_row(MS, job_row(job, small, n), n, tid, 64 * C::NW, LOGN + 1);
     for (int i = tid; i < C::TW_IDX; i += 64 * C::NW) {
         TW[i] = tw0[i];
         TW[C::TW_FIELD + i] = tw1[i];
@@ -634,12 +614,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 2) void k_pbs64k(const Pbs64Job
         const int bt = (int)MS[n];
         const uint64_t *tv = luts + (size_t)job.lut * N;
         for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) {
-            uint64_t v = 0;
-            if (j >= K * N) {
-                const int idx = ((j - K * N) + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0ull - v;
-            }
+            const uint64_t v = j >= K * N ? lut_rotated(tv, j - K * N, bt, N) : 0ull;
             const int pp = j / N, jj = j - pp * N;
             if constexpr (C::ACC_X) reinterpret_cast<uint64_t *>(smem + C::X_OFF)[C::acc_x(pp, jj)] = v;
             else {
@@ -1018,7 +993,6 @@ __device__ __forceinline__ void pbs64s_mb_body(unsigned char *smem, const double
 #pragma unroll
         for (int q = 0; q < 3; q++) bq[q] = psi_pow[(c_lane * am[q]) & (2 * N - 1)];
         // ---- (1) digits of this wave's quarter of polynomial p ----------------------------------
-        // ---- (1) digits of this wave's quarter of polynomial p ----------------------------------
 #pragma unroll
         for (int u = 0; u < Q; u++) {
             const int j = G::jA(lane, quarter * Q + u);
@@ -1150,8 +1124,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64s(const Pbs64Job *__rest
     // (+1.2 %, profiles/r03/si_kernel_experiments.txt)
     const int p = w >> 2, f = (w >> 1) & 1, h = (w & 1) ^ p;
     const Pbs64Job job = jobs[blockIdx.x];
-    const uint64_t *lwe = small + (size_t)job.in_row * ((size_t)n + 1);
-    for (int i = tid; i <= n; i += 64 * C::NW) MS[i] = (uint16_t)modswitch64(lwe[i], LOGN + 1);
+    switch_row(MS, job_row(job, small, n), n, tid, 64 * C::NW, LOGN + 1);
     if (tid < 2 * C::NW) reinterpret_cast<uint32_t *>(smem + C::FLAG_OFF)[tid] = 0u;
     // derived tables: index part for blocks A, B and lane table for block C, per (field, half)
     for (int q = 0; q < 4; q++) {
@@ -1164,15 +1137,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void k_pbs64s(const Pbs64Job *__rest
     {
         const int bt = (int)MS[n];
         const uint64_t *tv = luts + (size_t)job.lut * N;
-        for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) {
-            uint64_t v = 0;
-            if (j >= K * N) {
-                const int idx = ((j - K * N) + bt) & (2 * N - 1);
-                v = tv[idx & (N - 1)];
-                if (idx >= N) v = 0ull - v;
-            }
-            ACC[j] = v;
-        }
+        for (int j = tid; j < (K + 1) * N; j += 64 * C::NW) ACC[j] = j >= K * N ? lut_rotated(tv, j - K * N, bt, N) : 0ull;
     }
     __syncthreads();
     // psi^(N/2): entry 1 of the full forward table of this wave's field
