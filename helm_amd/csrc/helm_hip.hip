@@ -1962,9 +1962,15 @@ static bool needs_pbs(int op)
 {
     switch (op) {
     case HELM_GATE_AND: case HELM_GATE_NAND: case HELM_GATE_OR: case HELM_GATE_NOR:
-    case HELM_GATE_XOR: case HELM_GATE_XNOR: case HELM_GATE_MUX: return true;
+    case HELM_GATE_XOR: case HELM_GATE_XNOR: case HELM_GATE_MUX:
+    case HELM_GATE_MAJ3: case HELM_GATE_XOR3: case HELM_GATE_XNOR3: return true;
     default: return false;
     }
+}
+// gates whose third operand is required (the others read in0 and in1 alone)
+static bool needs_in2(int op)
+{
+    return op == HELM_GATE_MUX || op == HELM_GATE_MAJ3 || op == HELM_GATE_XOR3 || op == HELM_GATE_XNOR3;
 }
 static bool is_linear(int op)
 {
@@ -1986,7 +1992,7 @@ static int plan_level(const int32_t *op, const int32_t *in0, const int32_t *in1,
     for (int64_t g = 0; g < count; g++) {
         const int o = op[g];
         if (needs_pbs(o)) {
-            if (in0[g] < 0 || in1[g] < 0 || (o == HELM_GATE_MUX && in2[g] < 0))
+            if (in0[g] < 0 || in1[g] < 0 || (needs_in2(o) && in2[g] < 0))
                 return fail(HELM_ERR_INVALID, "gate " + std::to_string(g) + ": missing operand");
             KsJob k;
             k.big0 = (int32_t)pl.pbs.size();

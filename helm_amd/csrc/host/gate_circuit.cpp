@@ -310,7 +310,7 @@ std::unique_ptr<EncWireMap> GateCircuit::evaluate_encrypted(const EncWireMap &en
                 const auto &ins = gate.get_input_wires();
                 auto in_row = [&](size_t i) -> int32_t { return i < ins.size() ? eval_values->row(ins[i]) : -1; };
                 const GateType t = gate.get_gate_type();
-                if ((t == GateType::Mux && ins.size() < 3) ||
+                if (((t == GateType::Mux || t == GateType::Maj3 || t == GateType::Xor3 || t == GateType::Xnor3) && ins.size() < 3) ||
                     ((t == GateType::And || t == GateType::Nand || t == GateType::Or || t == GateType::Nor ||
                       t == GateType::Xor || t == GateType::Xnor) && ins.size() < 2) ||
                     ((t == GateType::Not || t == GateType::Buf || t == GateType::Dff) && ins.empty()))

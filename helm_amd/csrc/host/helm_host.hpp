@@ -53,7 +53,9 @@ struct PtxtType {
 // reference src/gates.rs:23-45 (declaration order = helm_gate_op)
 enum class GateType : int {
     And = 0, Dff, Lut, Mux, Nand, Nor, Not, Or, Xnor, Xor, Buf, ConstOne, ConstZero,
-    Mult, Add, Sub, Div, Shl, Shr, Copy
+    Mult, Add, Sub, Div, Shl, Shr, Copy,
+    // extensions (not discriminants of the reference's GateType): the three-input boolean gates of helm_hip.h
+    Maj3 = 20, Xor3 = 21, Xnor3 = 22
 };
 const char *gate_type_name(GateType t);
 
@@ -151,6 +153,10 @@ class Circuit {
 // Raw synthesis output (Yosys structural Verilog; with `arithmetic`, behavioural assign statements) -> the
 // netlist dialect read_verilog_file accepts (preprocessor.cpp; reference README.md:116-120,133-137).
 std::string preprocess(const std::string &text, bool arithmetic);
+
+// Three-input fusion (fuse3.cpp): dialect text -> dialect text in which xor/xnor pairs have become xor3 / xnor3 and the
+// and-and-or carry of a full adder maj.  stats = {bootstraps before, after, bootstrapped levels before, after}.
+std::string fuse3(const std::string &text, int64_t stats[4]);
 
 // Launch packing (level_pack.cpp): the level map of circuit.rs:174-239 as index arrays -> `order`
 // (new position -> gate) and `new_off` (launch boundaries) such that every launch but the last few

@@ -27,8 +27,9 @@ static int pbs_cost(int op)
     switch (op) {
     case HELM_GATE_AND: case HELM_GATE_NAND: case HELM_GATE_OR: case HELM_GATE_NOR:
     case HELM_GATE_XOR: case HELM_GATE_XNOR: return 1;
+    case HELM_GATE_MAJ3: case HELM_GATE_XOR3: case HELM_GATE_XNOR3: return 1; // one bootstrap on the sum of three rows
     case HELM_GATE_MUX: return 2; // two bootstraps, one keyswitch (tfhe's mux)
-    default: return 0;
+    default: return 0; // (an op this list does not name costs nothing here: the three-input gates must be named)
     }
 }
 

@@ -35,7 +35,8 @@ std::string PtxtType::to_string() const
 const char *gate_type_name(GateType t)
 {
     static const char *names[] = {"And", "Dff", "Lut", "Mux", "Nand", "Nor", "Not", "Or", "Xnor", "Xor", "Buf",
-                                  "ConstOne", "ConstZero", "Mult", "Add", "Sub", "Div", "Shl", "Shr", "Copy"};
+                                  "ConstOne", "ConstZero", "Mult", "Add", "Sub", "Div", "Shl", "Shr", "Copy",
+                                  "Maj3", "Xor3", "Xnor3"};
     return names[(int)t];
 }
 
@@ -81,6 +82,10 @@ PtxtType Gate::evaluate(const std::vector<PtxtType> &in)
     case GateType::Buf: output_ = in.at(0); break;
     case GateType::ConstOne: output_ = PtxtType::boolean(true); break;
     case GateType::ConstZero: output_ = PtxtType::boolean(false); break;
+    // the three-input extensions: exactly three operands (the parser and GateCircuit check the arity)
+    case GateType::Maj3: (void)in.at(2); output_ = PtxtType::boolean(ones() >= 2); break;
+    case GateType::Xor3: (void)in.at(2); output_ = PtxtType::boolean(ones() % 2 == 1); break;
+    case GateType::Xnor3: (void)in.at(2); output_ = PtxtType::boolean(ones() % 2 != 1); break;
     }
     return output_;
 }
@@ -183,7 +188,9 @@ Gate parse_gate(const std::vector<std::string> &tokens)
         {"nand", GateType::Nand}, {"nor", GateType::Nor},   {"not", GateType::Not},     {"or", GateType::Or},
         {"xnor", GateType::Xnor}, {"xor", GateType::Xor},   {"buf", GateType::Buf},     {"czero", GateType::ConstZero},
         {"cone", GateType::ConstOne}, {"add", GateType::Add}, {"mult", GateType::Mult}, {"div", GateType::Div},
-        {"sub", GateType::Sub},   {"shl", GateType::Shl},   {"shr", GateType::Shr},     {"copy", GateType::Copy}};
+        {"sub", GateType::Sub},   {"shl", GateType::Shl},   {"shr", GateType::Shr},     {"copy", GateType::Copy},
+        // not in the reference's dialect: written by the opt-in fusion pass, `maj g(in0, in1, in2, out);`
+        {"maj", GateType::Maj3},  {"xor3", GateType::Xor3}, {"xnor3", GateType::Xnor3}};
     auto it = kw.find(tokens.at(0));
     if (it == kw.end()) throw Panic("Invalid gate type \"" + tokens[0] + "\"");
     const GateType gate_type = it->second;
@@ -218,6 +225,12 @@ Gate parse_gate(const std::vector<std::string> &tokens)
     case GateType::Copy:
         input_wires = {nai(1)};
         output_wire = out_tok(tok(2));
+        break;
+    case GateType::Maj3: case GateType::Xor3: case GateType::Xnor3:
+        if (tokens.size() != 5)
+            throw Panic("gate " + gate_name + ": " + tokens[0] + " takes exactly three inputs and one output");
+        input_wires = {nai(1), trim(trim_end_matches(tok(2), ',')), trim(trim_end_matches(tok(3), ','))};
+        output_wire = out_tok(tok(4));
         break;
     default:
         input_wires = {nai(1), trim(trim_end_matches(tok(2), ','))};

@@ -60,6 +60,11 @@ __device__ __forceinline__ uint32_t gate_lincomb(int op, int which, uint32_t l, 
     case HELM_GATE_XOR: return 2u * (l + r + t);
     case HELM_GATE_XNOR: return 2u * (0u - (l + r + t));
     case HELM_GATE_MUX: return which == 0 ? (c + l + f) : (0u - c + r + f);
+    // the three-input extensions (helm_hip.h): the sum of three +-1/8 is +-1/8 or +-3/8, its sign their majority; twice
+    // the sum is +-2/8 and carries their parity (-6/8 = +2/8).  No constant: the phase is never 0 or 1/2.
+    case HELM_GATE_MAJ3: return l + r + c;
+    case HELM_GATE_XOR3: return 0u - 2u * (l + r + c);
+    case HELM_GATE_XNOR3: return 2u * (l + r + c);
     default: return 0u;
     }
 }

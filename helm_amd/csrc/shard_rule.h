@@ -15,7 +15,8 @@
 
 namespace helm_shard {
 
-// HELM_GATE_* of include/helm_hip.h: DFF 1, MUX 3, NOT 6, BUF 10, constants 11 / 12 cost no bootstrap.
+// HELM_GATE_* of include/helm_hip.h: DFF 1, MUX 3, NOT 6, BUF 10, constants 11 / 12 cost no bootstrap.  Every other op
+// weighs 1 by the default below - the three-input gates MAJ3 20, XOR3 21, XNOR3 22 (one bootstrap each) among them.
 inline int gate_weight(int op)
 {
     switch (op) {

@@ -303,7 +303,8 @@ def pack_levels(opcode, in0, in1, in2, out, level_offsets, quantum, quarter_cost
 
 
 def gate_pbs(opcode):
-    """Bootstraps of each gate: MUX 2, NOT / BUF / DFF / constants 0, every other gate 1 (helm_hip_program_level_pbs)."""
+    """Bootstraps of each gate: MUX 2, NOT / BUF / DFF / constants 0, every other gate - the three-input MAJ3 / XOR3 / XNOR3
+    among them - 1 (helm_hip_program_level_pbs)."""
     op = np.asarray(opcode)
     w = np.ones(len(op), dtype=np.int64)
     w[op == 3] = 2                                   # HELM_GATE_MUX

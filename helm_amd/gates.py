@@ -27,6 +27,11 @@ class GateType(enum.IntEnum):
     Shl = 17
     Shr = 18
     Copy = 19
+    # extensions, not discriminants of the reference's GateType: three-input boolean gates, one bootstrap each
+    # (HELM_GATE_MAJ3 / XOR3 / XNOR3; netlist keywords maj / xor3 / xnor3)
+    Maj3 = 20
+    Xor3 = 21
+    Xnor3 = 22
 
 
 @dataclass(frozen=True)

@@ -94,7 +94,12 @@ def _full_adder(nb, a, b, c, s_out=None, c_out=None):
     return s, co
 
 
-def ripple_adder(nbits):
+def ripple_adder(nbits, fused=False):
+    """fused=True: the same adder through the opt-in three-input fusion pass (verilog_parser.fuse3): nbits xor3 + nbits
+    maj gates, keywords the reference's parser does not know."""
+    if fused:
+        from ..verilog_parser import fuse3
+        return fuse3(ripple_adder(nbits))[0]
     nb = NetlistBuilder(f"adder{nbits}")
     a, b = nb.input("a", nbits), nb.input("b", nbits)
     c = nb.input("cin")

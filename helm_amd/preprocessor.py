@@ -2,9 +2,13 @@
 --arithmetic behavioural arithmetic Verilog, to the dialect verilog_parser reads.  Thin binding of
 helm_host_preprocess (helm_amd/csrc/host/preprocessor.cpp).
 
-    python -m helm_amd.preprocessor --input raw.v --output processed.v [--arithmetic]
+    python -m helm_amd.preprocessor --input raw.v --output processed.v [--arithmetic] [--fuse3]
+
+--fuse3 (opt-in, gates mode only) runs the three-input fusion pass over the result (verilog_parser.fuse3): its output
+uses the keywords maj / xor3 / xnor3, which the reference's parser does not know.
 """
 import argparse
+import sys
 
 from . import _host as H
 
@@ -18,11 +22,19 @@ def main(argv=None):
     ap.add_argument("--input", required=True)
     ap.add_argument("--output", required=True)
     ap.add_argument("--arithmetic", action="store_true")
+    ap.add_argument("--fuse3", action="store_true", help="fuse xor pairs and full-adder carries into three-input gates")
     a = ap.parse_args(argv)
+    if a.fuse3 and a.arithmetic:
+        ap.error("--fuse3 works on gates-mode netlists, not with --arithmetic")
     with open(a.input) as f:
         text = f.read()
+    text = preprocess(text, a.arithmetic)
+    if a.fuse3:
+        from .verilog_parser import fuse3
+        text, stats = fuse3(text)
+        print(f"fuse3: bootstraps {stats[0]} -> {stats[1]}, bootstrapped levels {stats[2]} -> {stats[3]}", file=sys.stderr)
     with open(a.output, "w") as f:
-        f.write(preprocess(text, a.arithmetic))
+        f.write(text)
 
 
 if __name__ == "__main__":

@@ -51,6 +51,15 @@ def read_verilog_text(text, is_arith):
     return _wrap(h)
 
 
+def fuse3(text):
+    """Opt-in three-input fusion of a gates-mode netlist (helm_host_fuse3, helm_amd/csrc/host/fuse3.cpp): xor / xnor pairs
+    become xor3 / xnor3, the and-and-or carry of a full adder becomes maj - one bootstrap each.  Keywords outside the
+    reference's dialect.  -> (text, (bootstraps before, after, bootstrapped levels before, after))"""
+    p, stats = H.vp(), (C.c_int64 * 4)()
+    H.check(H.host.helm_host_fuse3(text.encode(), C.byref(p), stats))
+    return H.take(p.value), tuple(int(x) for x in stats)
+
+
 def read_input_wires(file_name, ptxt_type):
     """reference src/verilog_parser.rs:278-317"""
     return text_to_map(H.out_text(H.host.helm_host_read_input_wires, str(file_name).encode(), ptxt_type.encode()))

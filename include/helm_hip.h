@@ -97,7 +97,12 @@ typedef enum {
     HELM_GATE_XNOR = 8, HELM_GATE_XOR = 9, HELM_GATE_BUF = 10,
     HELM_GATE_CONST_ONE = 11, HELM_GATE_CONST_ZERO = 12,
     HELM_GATE_MULT = 13, HELM_GATE_ADD = 14, HELM_GATE_SUB = 15, HELM_GATE_DIV = 16,
-    HELM_GATE_SHL = 17, HELM_GATE_SHR = 18, HELM_GATE_COPY = 19
+    HELM_GATE_SHL = 17, HELM_GATE_SHR = 18, HELM_GATE_COPY = 19,
+    /* Extensions: NOT discriminants of the reference's GateType.  Three-input
+     * boolean gates, one bootstrap + one keyswitch each, all three operands
+     * required; the linear step is the same on every word and adds no constant:
+     * MAJ3 in0+in1+in2, XOR3 -2*(in0+in1+in2), XNOR3 2*(in0+in1+in2). */
+    HELM_GATE_MAJ3 = 20, HELM_GATE_XOR3 = 21, HELM_GATE_XNOR3 = 22
 } helm_gate_op;
 
 const char *helm_hip_last_error(void);
@@ -254,7 +259,8 @@ int helm_hip_wires_device_ptr(helm_hip_ctx *ctx, helm_hip_wires *w, void **dev_p
 /* Replaces the body of the level loop, reference src/circuit.rs:531-541:
  * `count` independent gates; gate g reads wires in0[g], in1[g], in2[g] (-1 =
  * unused) and writes wire out[g].  Operand meaning follows gates.rs:255-274:
- * binary gates use (in0,in1); MUX is sel=in2 ? in0 : in1; NOT/BUF/DFF use in0.
+ * binary gates use (in0,in1); MUX is sel=in2 ? in0 : in1; NOT/BUF/DFF use in0;
+ * MAJ3 / XOR3 / XNOR3 (extensions) use (in0,in1,in2), all three required.
  * No gate of the level may read a wire written in the same level (guaranteed by
  * Circuit::compute_levels, circuit.rs:174-239).  Index arrays are host memory. */
 int helm_hip_eval_gate_level(helm_hip_ctx *ctx, helm_hip_wires *w, const int32_t *opcode,
@@ -277,8 +283,8 @@ int helm_hip_program_run(helm_hip_ctx *ctx, helm_hip_program *prog, helm_hip_wir
 /* Multi-GPU: this rank evaluates the contiguous slice `rank` of `world` of the
  * level's gates and packs the slice's output ciphertexts into `staging`
  * (device memory, chunk_rows(level, world) rows of n+1 words, zero padded).
- * The level is cut by BOOTSTRAP WEIGHT, not by gate count (binary gate 1, MUX 2,
- * NOT / BUF / DFF / constants 0: SURVEY 8(d)'s count), so that every rank gets
+ * The level is cut by BOOTSTRAP WEIGHT, not by gate count (binary gate and
+ * MAJ3 / XOR3 / XNOR3 1, MUX 2, NOT / BUF / DFF / constants 0: SURVEY 8(d)'s count), so that every rank gets
  * the same number of bootstraps to within one gate whatever the mix of a level:
  * helm_hip_program_chunk_bounds() returns the cut (bounds[r] .. bounds[r+1] are
  * rank r's gates, world + 1 entries), chunk_rows() the largest chunk = the rows
@@ -324,7 +330,8 @@ int helm_hip_program_run_sharded_comm(helm_hip_ctx *ctx, helm_hip_program *prog,
                                       int64_t replicate_below, int overlap);
 /* 1 when the overlapped exchange applies to this program (no wire written twice per pass), 0 otherwise. */
 int helm_hip_program_overlap_applies(helm_hip_program *prog);
-/* Number of programmable bootstraps a level costs (binary gate 1, MUX 2, others 0). */
+/* Number of programmable bootstraps a level costs (binary gate and MAJ3 / XOR3 /
+ * XNOR3 1, MUX 2, others 0). */
 int64_t helm_hip_program_level_pbs(helm_hip_program *prog, int64_t level);
 
 /* -- primitive batch ops (tests, LUT / integer layers) ---------------------- */

@@ -66,6 +66,17 @@ int helm_host_circuit_evaluate(helm_circuit *c, const char *wire_map, char **out
  * over + - * / << >> - to the dialect helm_host_read_verilog_* reads.  *out is malloc'd text. */
 int helm_host_preprocess(const char *text, int arithmetic, char **out);
 
+/* Three-input fusion, opt-in (helm_amd/csrc/host/fuse3.cpp): dialect text -> dialect text in which
+ *   R1  a two-input xor / xnor one of whose inputs is driven by another two-input xor / xnor becomes xor3 (xnor3 when an
+ *       odd number of the two are xnor) on the inner gate's two operands followed by the other operand;
+ *   R2  or(p, q) with p = and(a, b), q = and(x, c), x = xor(a, b) or or(a, b) becomes maj(a, b, c); x stays.
+ * A gate is deleted only when exactly one gate reads its output and that output is no module output; the surviving gate
+ * keeps its name and output wire.  Applied to a fixed point in netlist order; idempotent.  The keywords maj / xor3 / xnor3
+ * (HELM_GATE_MAJ3 / XOR3 / XNOR3, one bootstrap each) are not part of the reference's dialect.
+ * stats = {bootstraps before, bootstraps after, bootstrapped levels before, bootstrapped levels after}.
+ * *out is malloc'd text. */
+int helm_host_fuse3(const char *text, char **out, int64_t stats[4]);
+
 /* Launch packing of a level schedule (the level loop of circuit.rs:524-543 made GPU-shaped): gates in level
  * order as index arrays (helm_hip_program_create's arguments) -> `order[total]` (new position -> gate index)
  * and `new_offsets` (room for total + 1 entries; *n_launches + 1 are written): dependency order is kept, a
@@ -86,9 +97,9 @@ int helm_host_pack_levels_costed(const int32_t *opcode, const int32_t *in0, cons
                                  const double *quarter_cost, int64_t *order, int64_t *new_offsets, int64_t *n_launches);
 
 /* The engine's cut of one launch into `world` contiguous chunks, one per GPU (helm_amd/csrc/shard_rule.h; what
- * helm_hip_program_chunk_bounds() returns for an uploaded program): by BOOTSTRAP weight - binary gate 1, MUX 2, NOT / BUF /
- * DFF / constants 0 - so that a sharded launch gives every rank the same number of bootstraps to within one gate
- * (the reference balances the level dynamically, circuit.rs:531 `par_iter_mut`).  bounds has world + 1 entries;
+ * helm_hip_program_chunk_bounds() returns for an uploaded program): by BOOTSTRAP weight - binary gate and the three-input
+ * MAJ3 / XOR3 / XNOR3 1, MUX 2, NOT / BUF / DFF / constants 0 - so that a sharded launch gives every rank the same number
+ * of bootstraps to within one gate (the reference balances the level dynamically, circuit.rs:531 `par_iter_mut`).  bounds has world + 1 entries;
  * returns the largest chunk (rows of one rank's slot in the all-gather), -1 on bad arguments. */
 int64_t helm_host_shard_bounds(const int32_t *opcode, int64_t count, int world, int64_t *bounds);
 

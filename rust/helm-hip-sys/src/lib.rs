@@ -59,6 +59,10 @@ pub const HELM_GATE_XOR: i32 = 9;
 pub const HELM_GATE_BUF: i32 = 10;
 pub const HELM_GATE_CONST_ONE: i32 = 11;
 pub const HELM_GATE_CONST_ZERO: i32 = 12;
+// extensions, no discriminants of the reference's GateType: three-input boolean gates, one bootstrap each
+pub const HELM_GATE_MAJ3: i32 = 20;
+pub const HELM_GATE_XOR3: i32 = 21;
+pub const HELM_GATE_XNOR3: i32 = 22;
 
 // include/helm_hip.h: flags of helm_hip_ctx_create_ex (an importer that meets a boolean key shape beyond the single-prime
 // capacity bound - few, wide decomposition levels - passes ALLOW_CRT)
@@ -168,6 +172,9 @@ extern "C" {
                           rccl_version: *mut c_int) -> c_int;
     pub fn helm_comm_all_reduce_f64(comm: *mut helm_comm, value: *mut f64, op: c_int) -> c_int;
     pub fn helm_comm_barrier(comm: *mut helm_comm) -> c_int;
+
+    // ---- include/helm_host.h: opt-in three-input fusion of a gates-mode netlist (dialect text in and out) ----
+    pub fn helm_host_fuse3(text: *const c_char, out: *mut *mut c_char, stats: *mut i64) -> c_int;
 
     // ---- include/helm_host.h: launch packing of the level map -------------------------------
     pub fn helm_host_pack_levels(opcode: *const i32, in0: *const i32, in1: *const i32, in2: *const i32, out: *const i32,
