@@ -455,11 +455,17 @@ static std::vector<RadixOp> to_radix_ops(const helm_radix_op *ops, int64_t count
     }
     return v;
 }
+// 1 .. 64 blocks: a plaintext operand is 128 bits, so its digits end at block 63
+static void check_radix_blocks(int32_t blocks)
+{
+    if (blocks < 1 || blocks > 64) throw Panic("radix level: blocks = " + std::to_string(blocks) + " is outside 1 .. 64");
+}
 int64_t helm_host_radix_scratch_rows(helm_si_ctx *ctx, int32_t blocks, const helm_radix_op *ops, int64_t count)
 {
     int64_t rows = -1;
     guard([&] {
-        if (!ctx || blocks < 1) throw Panic("radix level: bad argument");
+        if (!ctx) throw Panic("radix level: bad argument");
+        check_radix_blocks(blocks);
         RadixEngine eng(ctx, blocks);
         rows = eng.scratch_rows(to_radix_ops(ops, count));
     });
@@ -469,7 +475,8 @@ int helm_host_radix_level(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blocks
                           int32_t scratch_first_row, int64_t *pbs_out, int64_t *rounds_out)
 {
     return guard([&] {
-        if (!ctx || !wires || blocks < 1 || scratch_first_row < 0) throw Panic("radix level: bad argument");
+        if (!ctx || !wires || scratch_first_row < 0) throw Panic("radix level: bad argument");
+        check_radix_blocks(blocks);
         RadixEngine eng(ctx, blocks);
         eng.run_level(wires, to_radix_ops(ops, count), scratch_first_row);
         if (pbs_out) *pbs_out = eng.pbs_count();
@@ -480,7 +487,8 @@ int helm_host_radix_level_ex(helm_si_ctx *ctx, helm_si_wires *wires, int32_t blo
                              int32_t scratch_first_row, int64_t *pbs_out, int64_t *rounds_out, int flags)
 {
     return guard([&] {
-        if (!ctx || !wires || blocks < 1 || scratch_first_row < 0) throw Panic("radix level: bad argument");
+        if (!ctx || !wires || scratch_first_row < 0) throw Panic("radix level: bad argument");
+        check_radix_blocks(blocks);
         if (flags & ~HELM_RADIX_MANY_LUT) throw Panic("radix level: unknown flag bits");
         RadixEngine eng(ctx, blocks);
         eng.set_many_lut((flags & HELM_RADIX_MANY_LUT) != 0);

@@ -445,8 +445,14 @@ class RadixEngine {
   public:
     RadixEngine(helm_si_ctx *ctx, int blocks);
     void attach(RoundMerger *merger, int chain) { merger_ = merger, chain_ = chain; }
-    int64_t scratch_rows(const std::vector<RadixOp> &ops) const;
-    void run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch);
+    // Scratch rows one level of `ops` spends: the level's own walk (walk()) run dry - every row is taken, no device call is
+    // made - so the budget is counted by the code that spends it.
+    int64_t scratch_rows(const std::vector<RadixOp> &ops);
+    // Needs scratch_rows(ops_in) rows from `scratch` on; taking a row past them is an error, not a write.  `rows`: that
+    // budget where the caller has it already (an evaluator sizes its table with it), else it is counted here.  It must be
+    // scratch_rows(ops_in) of THIS engine as it is set now (block count, many-LUT setting): it is the bound of take(), so a
+    // smaller one fails the level and a larger one moves the bound past what the caller reserved.
+    void run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch, int64_t rows = -1);
     void propagate(helm_si_wires *w, const std::vector<int32_t> &bases, int scratch, int width,
                    const std::vector<int32_t> *carry_out_rows);
     int64_t pbs_count() const { return pbs_count_; } // blind rotations
@@ -467,6 +473,9 @@ class RadixEngine {
     Carries carries(helm_si_wires *w, const std::vector<int32_t> &states, int G, int n, int need, bool add_const, int &sp,
                     bool want_bit);
     static int prop_rows(int W); // scratch rows of propagate() per integer
+    int64_t walk(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch); // the level; returns the rows taken
+    int take(int &sp, int rows); // the next `rows` scratch rows; panics past scratch_end_
+    void set_trivial(helm_si_wires *w, const std::vector<int32_t> &idx, const std::vector<uint64_t> &val);
     void shift_scalar(helm_si_wires *w, const std::vector<RadixOp> &ops);
     void shift_encrypted(helm_si_wires *w, const std::vector<RadixOp> &ops, int &scratch_pos);
     void divide(helm_si_wires *w, const std::vector<RadixOp> &ops, int &scratch_pos);
@@ -479,6 +488,8 @@ class RadixEngine {
         lut_cout_ = 0; // carry propagation, see propagate()
     int lut_bit0_ = 0, lut_bit1_ = 0, lut_shl1_ = 0, lut_shr1_ = 0, lut_sel_ = 0;
     bool many_lut_ = false;
+    bool dry_ = false;            // walk() only takes rows: lincomb / apply / set_trivial return at once
+    int64_t scratch_end_ = -1;    // one past the last scratch row of the level being run (-1: unbounded, the dry walk)
     int lut_pair_[4] = {-1, -1, -1, -1}; // (message, carry state x 2^p) of a block sum <= 7: built by set_many_lut(true)
     int64_t pbs_count_ = 0, pbs_rounds_ = 0;
     std::vector<int32_t> pend_in_, pend_lut_, pend_out_; // look-ups waiting for the level's next batch

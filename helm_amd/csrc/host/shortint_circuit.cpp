@@ -535,7 +535,9 @@ RadixEngine::RadixEngine(helm_si_ctx *ctx, int nb) : ctx_(ctx), nb_(nb)
     auto add_lut = [&](auto f) {
         std::vector<uint64_t> vals((size_t)t);
         for (int v = 0; v < 16; v++) {
-            const int e = (int)f(v), sv = e >= 16 ? e - 32 : e; // the entry as a signed value
+            // the entry as a signed value: 32 - x is -x.  16 itself (lut_t_[3]'s weighted "generates", 2 << 3) is + 16: at
+            // t = 16 the two are the same residue, at t = 32 a - 16 would turn V_3 = 30 into - 2 and the look-up's sign over
+            const int e = (int)f(v), sv = e > 16 ? e - 32 : e;
             vals[(size_t)v] = (uint64_t)((sv + 2 * t) % (2 * t));
             if (t == 32) vals[(size_t)v + 16] = (uint64_t)((2 * t - sv) % (2 * t));
         }
@@ -709,10 +711,27 @@ void RoundMerger::finish(int chain)
     issue_locked(); // the others may all be waiting now
 }
 
+int RadixEngine::take(int &sp, int rows)
+{
+    const int b = sp;
+    if (rows < 0 || (scratch_end_ >= 0 && (int64_t)sp + rows > scratch_end_))
+        throw Panic("internal error: radix level takes scratch rows " + std::to_string(sp) + " .. " + std::to_string((int64_t)sp + rows - 1) +
+                    " past the end of its region (" + std::to_string(scratch_end_) + ")");
+    sp += rows;
+    return b;
+}
+
+void RadixEngine::set_trivial(helm_si_wires *w, const std::vector<int32_t> &idx, const std::vector<uint64_t> &val)
+{
+    if (idx.empty() || dry_) return;
+    auto guard = device_lock();
+    si_ok(helm_si_wires_set_trivial(ctx_, w, idx.data(), val.data(), (int64_t)idx.size()), "set_trivial");
+}
+
 void RadixEngine::lincomb(helm_si_wires *w, const std::vector<int32_t> &in_idx, const std::vector<int64_t> &coef,
                           const std::vector<int64_t> &cadd, const std::vector<int32_t> &out, int terms)
 {
-    if (out.empty()) return;
+    if (out.empty() || dry_) return;
     auto guard = device_lock();
     si_ok(helm_si_lincomb(ctx_, w, in_idx.data(), coef.data(), cadd.empty() ? nullptr : cadd.data(), out.data(), terms,
                           (int64_t)out.size()),
@@ -722,6 +741,10 @@ void RadixEngine::lincomb(helm_si_wires *w, const std::vector<int32_t> &in_idx, 
 void RadixEngine::apply(helm_si_wires *w, const std::vector<int32_t> &in, const std::vector<int32_t> &lut,
                         const std::vector<int32_t> &out, const std::vector<int32_t> *out2)
 {
+    if (dry_) {
+        pend_in_.clear(), pend_lut_.clear(), pend_out_.clear();
+        return;
+    }
     // look-ups that wait for a batch to ride in (shift_scalar): independent rows, so any batch of the level will do
     if (!pend_in_.empty()) {
         std::vector<int32_t> i2(in), l2(lut), o2(out), p2;
@@ -779,7 +802,7 @@ int RadixEngine::prop_rows(int W) { return 5 * W + 16; }
 RadixEngine::Carries RadixEngine::carries(helm_si_wires *w, const std::vector<int32_t> &st, int G, int n, int need,
                                          bool add_const, int &sp, bool want_bit)
 {
-    auto take = [&](int rows) { const int b = sp; sp += rows; return b; };
+    auto take = [&](int rows) { return this->take(sp, rows); };
     Carries R;
     R.bit = true;
     R.row.assign((size_t)G * (size_t)(need + 1), -1);
@@ -891,7 +914,13 @@ void RadixEngine::propagate(helm_si_wires *w, const std::vector<int32_t> &bases,
     if (G == 0) return;
     if (W <= 0) W = nb_;
     int sp = scratch;
-    auto take = [&](int rows) { const int b = sp; sp += rows; return b; };
+    auto take = [&](int rows) { return this->take(sp, rows); };
+    // its own region inside the level's: what carries() takes below must stay inside the prop_rows(W) rows per integer
+    auto check_own = [&]() {
+        if ((int64_t)sp > (int64_t)scratch + (int64_t)prop_rows(W) * G)
+            throw Panic("internal error: carry propagation of " + std::to_string(W) + " blocks takes " + std::to_string(sp - scratch) +
+                        " scratch rows, more than its prop_rows");
+    };
     const int need = flags ? W : W - 1; // carries into blocks 1..W-1, and out of the top block
     // round 1: weighted carry states, and the messages (in place)
     const int tbase = take(G * W);
@@ -918,6 +947,7 @@ void RadixEngine::propagate(helm_si_wires *w, const std::vector<int32_t> &bases,
     }
     if (need == 0) return;
     Carries C = carries(w, st, G, W, need, false, sp, false);
+    check_own();
     // last round: message + 4 c -> (message + [c >= 2]) & 3; bit-form carries are c = 1 + bit
     std::vector<int32_t> li, lo;
     std::vector<int64_t> lc, ca;
@@ -997,7 +1027,7 @@ void RadixEngine::shift_encrypted(helm_si_wires *w, const std::vector<RadixOp> &
     const int G = (int)sh.size();
     int nbits = 0;
     while ((1 << nbits) < 2 * nb_) nbits++;
-    auto take = [&](int rows) { const int b = sp; sp += rows; return b; };
+    auto take = [&](int rows) { return this->take(sp, rows); };
     const int bits0 = take(G * nbits), cur0 = take(G * nb_), shf0 = take(G * nb_), selA0 = take(G * nb_), selB0 = take(G * nb_);
     auto BIT = [&](int g, int t) { return bits0 + g * nbits + t; };
     std::vector<int32_t> li, lo, in, lut, out;
@@ -1076,7 +1106,7 @@ void RadixEngine::divide(helm_si_wires *w, const std::vector<RadixOp> &ops, int 
         if (op.kind == RadixOp::Div || op.kind == RadixOp::DivScalar) dv.push_back(&op);
     if (dv.empty()) return;
     const int G = (int)dv.size(), W = nb_ + 1, bits = 2 * nb_;
-    auto take = [&](int rows) { const int b = sp; sp += rows; return b; };
+    auto take = [&](int rows) { return this->take(sp, rows); };
     const int abit0 = take(G * bits), qbit0 = take(G * bits), B0 = take(G * W), R0 = take(G * W), D0 = take(G * W),
               selA0 = take(G * W), selB0 = take(G * W), st0 = take(prop_rows(W) * G);
     std::vector<int32_t> li, lo, in, lut, out, idx;
@@ -1097,10 +1127,7 @@ void RadixEngine::divide(helm_si_wires *w, const std::vector<RadixOp> &ops, int 
             val.push_back(0);
         }
     lincomb(w, li, lc, {}, lo, 2);
-    {
-        auto guard = device_lock();
-        si_ok(helm_si_wires_set_trivial(ctx_, w, idx.data(), val.data(), (int64_t)idx.size()), "set_trivial");
-    }
+    set_trivial(w, idx, val);
     // bits of the numerators
     for (int g = 0; g < G; g++)
         for (int t = 0; t < bits; t++) {
@@ -1174,25 +1201,35 @@ void RadixEngine::divide(helm_si_wires *w, const std::vector<RadixOp> &ops, int 
     lincomb(w, li, lc, {}, lo, 2);
 }
 
-int64_t RadixEngine::scratch_rows(const std::vector<RadixOp> &ops) const
+// The budget is the level's own walk run dry: same planning, same takes, no device call (the terms of a scalar product
+// with digits 3 are reduced one by one; the closed form of "about 4 nb vectors" this replaced fell short in vectors from 16
+// blocks on and, past what propagate leaves unused of its rows, in rows from 32 blocks on).
+namespace {
+struct WalkMode { // sets the engine's walk mode and puts back what it found, on every way out
+    bool &dry;
+    int64_t &end;
+    const bool dry0;
+    const int64_t end0;
+    WalkMode(bool &d, int64_t &e, bool dry_now, int64_t end_now) : dry(d), end(e), dry0(d), end0(e) { dry = dry_now, end = end_now; }
+    ~WalkMode() { dry = dry0, end = end0; }
+};
+} // namespace
+
+int64_t RadixEngine::scratch_rows(const std::vector<RadixOp> &ops)
 {
-    int64_t rows = 0;
-    for (auto &op : ops) {
-        rows += prop_rows(nb_); // propagate scratch
-        // partial-product vectors (2 nb - 1) plus the message / carry vectors of the reduction
-        // rounds (about 1.5 nb): 4 nb + 4 vectors of nb rows bound both
-        if (op.kind == RadixOp::Mul || op.kind == RadixOp::MulScalar) rows += (int64_t)(4 * nb_ + 4) * nb_;
-        if (op.kind == RadixOp::AddScalar || op.kind == RadixOp::SubScalar) rows += nb_;
-        if (op.a2 >= 0 || op.b2 >= 0 || ((op.kind == RadixOp::Add || op.kind == RadixOp::Sub) && op.out2 >= 0))
-            rows += 6 * nb_; // complemented terms and one reduction round of a carry-save sum
-        if (op.kind == RadixOp::Shl || op.kind == RadixOp::Shr) rows += 4 * nb_ + 8;
-        if (op.kind == RadixOp::Div || op.kind == RadixOp::DivScalar) rows += 4 * 2 * nb_ + 5 * (nb_ + 1) + prop_rows(nb_ + 1);
-    }
-    return rows;
+    WalkMode mode(dry_, scratch_end_, true, -1);
+    return walk(nullptr, ops, 0);
+}
+
+void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch, int64_t rows)
+{
+    if (rows < 0) rows = scratch_rows(ops_in);
+    WalkMode mode(dry_, scratch_end_, false, (int64_t)scratch + rows);
+    walk(w, ops_in, scratch);
 }
 
 // One netlist level of integer operators (independent of each other), batched stage by stage.
-void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch)
+int64_t RadixEngine::walk(helm_si_wires *w, const std::vector<RadixOp> &ops_in, int scratch)
 {
     // a multiplication by a plaintext power of two IS a left shift: whole blocks move for free and an odd bit costs one
     // look-up per block, where the digit-wise product (block values up to 6) would need a full carry propagation
@@ -1218,7 +1255,7 @@ void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in
     std::vector<MulState> muls;
     std::vector<int32_t> prop_bases; // integers waiting for the final propagation
     int sp = scratch;
-    auto take = [&](int rows) { const int b = sp; sp += rows; return b; };
+    auto take = [&](int rows) { return this->take(sp, rows); };
 
     {
         std::vector<int32_t> li, lo;
@@ -1354,11 +1391,7 @@ void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in
                 }
             }
         }
-        if (!zero_rows.empty()) {
-            std::vector<uint64_t> z(zero_rows.size(), 0);
-            auto guard = device_lock();
-            si_ok(helm_si_wires_set_trivial(ctx_, w, zero_rows.data(), z.data(), (int64_t)zero_rows.size()), "set_trivial");
-        }
+        set_trivial(w, zero_rows, std::vector<uint64_t>(zero_rows.size(), 0));
         // one batch: the keyswitch of every ciphertext of a call finishes before any bootstrap writes,
         // so the lo look-ups may overwrite the packed rows the hi look-ups also read
         in.insert(in.end(), in2.begin(), in2.end());
@@ -1450,11 +1483,7 @@ void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in
         }
         if (!any) break;
         lincomb(w, li, lc, {}, lo, T);
-        if (!zero_rows.empty()) {
-            std::vector<uint64_t> z(zero_rows.size(), 0);
-            auto guard = device_lock();
-            si_ok(helm_si_wires_set_trivial(ctx_, w, zero_rows.data(), z.data(), (int64_t)zero_rows.size()), "set_trivial");
-        }
+        set_trivial(w, zero_rows, std::vector<uint64_t>(zero_rows.size(), 0));
         // carries and (in place) messages of every summed row in one batch (see above)
         for (auto r : lo) { in.push_back(r); lut.push_back(lut_msg_); out.push_back(r); }
         apply(w, in, lut, out);
@@ -1496,6 +1525,7 @@ void RadixEngine::run_level(helm_si_wires *w, const std::vector<RadixOp> &ops_in
     shift_encrypted(w, ops, sp);
     divide(w, ops, sp);
     apply(w, {}, {}, {}); // shift look-ups no batch has taken along
+    return (int64_t)sp - scratch;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1811,7 +1841,11 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
         }
         for (size_t l = 0; l < plan.size(); l++) plan[l].insert(plan[l].end(), finish[l].begin(), finish[l].end());
     }
-    for (auto &ops : plan) max_scratch = std::max(max_scratch, eng.scratch_rows(ops));
+    std::vector<int64_t> plan_rows; // every level's own budget: the bound of its run_level
+    for (auto &ops : plan) {
+        plan_rows.push_back(eng.scratch_rows(ops));
+        max_scratch = std::max(max_scratch, plan_rows.back());
+    }
     const size_t total_levels = circuit_.level_map().size();
     // Lanes by default: an operator graph with two or more connected components runs them concurrently on the server key
     // and ONE lane forked from it (identical ciphertexts, the rounds of the longest component in a row instead of the sum
@@ -1917,12 +1951,16 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
         }
         std::vector<std::unique_ptr<RadixEngine>> engines;
         std::vector<int64_t> lane_scratch(n_ctx, 0);
+        std::vector<std::vector<int64_t>> lane_rows(n_ctx); // per level of a lane
         int64_t total_scratch = 0;
         for (size_t lane = 0; lane < n_ctx; lane++) {
             engines.emplace_back(new RadixEngine(ctx_of(lane), nb));
             engines.back()->set_many_lut(many_lut_);
             if (merger) engines.back()->attach(merger.get(), (int)lane);
-            for (auto &ops : lane_plan[lane]) lane_scratch[lane] = std::max(lane_scratch[lane], engines[lane]->scratch_rows(ops));
+            for (auto &ops : lane_plan[lane]) {
+                lane_rows[lane].push_back(engines[lane]->scratch_rows(ops));
+                lane_scratch[lane] = std::max(lane_scratch[lane], lane_rows[lane].back());
+            }
             total_scratch += lane_scratch[lane];
         }
         int base = eval_values->scratch(aux_total + total_scratch) + (int)aux_total; // carry-save terms first
@@ -1935,8 +1973,9 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
         std::vector<std::string> errors(n_ctx);
         auto run_lane = [&](size_t lane) {
             try {
-                for (auto &ops : lane_plan[lane])
-                    if (!ops.empty()) engines[lane]->run_level(eval_values->table(), ops, lane_base[lane]);
+                for (size_t l = 0; l < lane_plan[lane].size(); l++)
+                    if (!lane_plan[lane][l].empty())
+                        engines[lane]->run_level(eval_values->table(), lane_plan[lane][l], lane_base[lane], lane_rows[lane][l]);
                 if (!merger) si_ok(helm_si_sync(ctx_of(lane)), "sync");
             } catch (const std::exception &e) {
                 errors[lane] = e.what();
@@ -1967,7 +2006,8 @@ std::unique_ptr<SiEncWireMap> ArithCircuit::evaluate_encrypted(const SiEncWireMa
     const int scratch = eval_values->scratch(aux_total + max_scratch) + (int)aux_total; // carry-save terms first
     size_t li = 0;
     for (auto &kv : circuit_.level_map()) {
-        eng.run_level(eval_values->table(), plan[li++], scratch);
+        eng.run_level(eval_values->table(), plan[li], scratch, plan_rows[li]);
+        li++;
         std::ostringstream os;
         os << "  Evaluated gates in level [" << kv.first << "/" << total_levels << "]\n";
         log_ += os.str();

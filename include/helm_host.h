@@ -220,7 +220,8 @@ int helm_host_si_circuit_set_timing_lines(helm_si_circuit *c, int on);
 /* One level of arithmetic-mode operators as ONE batched call on a table of radix integers - what the reference does
  * gate by gate with the FheUintN operators (src/gates.rs:306-702: evaluate_encrypted_{copy,mul,div,add,sub,shift}_block
  * and their _plain forms; level loop src/circuit.rs:1320-1441).  An integer is `blocks` consecutive rows (2 message bits
- * per block, least significant first; 4..64 blocks for FheUint8..128); a, b, out are FIRST rows; an operator with a
+ * per block, least significant first; 4..64 blocks for FheUint8..128, and every count from 1 to 64 is accepted - the
+ * 128-bit plaintext operand ends at block 63, so blocks < 1 or > 64 is an error); a, b, out are FIRST rows; an operator with a
  * plaintext operand (an all-digit wire name, circuit.rs:1328-1334) carries it in scalar_lo / scalar_hi.  The call needs
  * helm_host_radix_scratch_rows() rows of the same table from scratch_first_row on (beyond every integer).  What a Rust
  * `impl EvalCircuit<FheType> for HipArithCircuit` forwards each level to. */
